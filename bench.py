@@ -1,6 +1,11 @@
 """Driver benchmark.  `python bench.py --gpus N --steps K --warmup W` (N>1: one rank per GPU under
 torch.distributed.run, RCCL).  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the step's
+configuration).  `--full` adds every other record below (roofline pass, f32 MFMA step, secondary chains, CPU baselines,
+entry points); the `--no-*` options trim a `--full` run.  `--dump-outputs DIR` writes what the last timed step left
+for its caller as DIR/<name>.npy (see dump_outputs).
+
 step      = one MoCo-3D training step (BASELINE.json configs[1]): q forward + EMA + k forward +
             InfoNCE + backward + SGD on a batch of 64 pairs of 32^3 sub-tomogram views cut from a
             synthetic 128x512x512 tomogram; inputs are resident in HBM before the timed region.
@@ -47,6 +52,36 @@ def build_views(tomo_dev, n_crops, crop, seed):
     pq = S.crop_znorm(tomo_dev, centres, (crop,) * 3)
     pk = S.crop_znorm(tomo_dev, centres + shift, (crop,) * 3, flip_x=True)
     return pq, pk
+
+
+DUMP_K_SAMPLE = 1 << 20          # encoder_k parameters in the dump: a fixed, seeded sample of the arena
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, engine, moco):
+    """What the last timed step leaves for its caller, as <dirname>/<name>.npy: the loss, the (B, 1 + r) logits, the
+    key queue and its pointer, encoder_q's parameters (the whole SGD-updated arena) and a fixed sample of encoder_k's
+    (EMA-updated) arena - about 45 MB.  The inputs are seeded, so two builds run with the same arguments compare
+    output for output."""
+    torch.cuda.synchronize()
+    n_k = engine.arena_k.flat.numel()
+    idx = np.sort(np.random.default_rng(317).choice(n_k, min(n_k, DUMP_K_SAMPLE), replace=False))
+    arrays = {
+        "loss": engine.loss.detach().float(),
+        "logits": engine.logits.float(),
+        "queue": moco.queue.detach().float(),
+        "queue_ptr": moco.queue_ptr.detach().double(),
+        "params_q": engine.arena_q.flat.detach(),
+        "params_k_sample": engine.arena_k.flat.detach()[torch.as_tensor(idx, device=engine.arena_k.flat.device)],
+    }
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes over the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return total
 
 
 def conv_profile(engine, pq, pk, batch, steps):
@@ -433,6 +468,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-conv-profile", action="store_true", help="skip the per-launch roofline pass (clean rocprofv3 runs of the step)")
     ap.add_argument("--no-entry-point", action="store_true", help="skip the moco_main entry-point record (MRC file -> loader -> run_epoch)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the roofline pass, the f32 MFMA step, the secondary records, the CPU baselines "
+                         "and the entry-point records (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -542,23 +582,42 @@ def main():
         dist.all_reduce(ones)                                     # took part in the collectives of the timed steps
         ranks_seen = int(ones.item())
     log("timed region: %d steps in %.3f s" % (args.steps, dt))
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, engine, moco)
+        log("outputs of the last timed step: %.1f MB in %s" % (nbytes / 1e6, args.dump_outputs))
 
     out = None
     # the roofline pass runs three more steps: EVERY rank takes them (they contain the step's collectives)
     step_nodes = engine.node_counts() if engine.use_graph else None
-    if args.no_conv_profile:
+    arith = "f32" if os.environ.get("MI_CONV_ARITH", "")[:1] == "f" else "bf16x3"
+    config = {"workload": "moco_main.py moco3d_18: 3D encoder, synthetic 512x512x128 tomogram, 32^3 subtomo "
+                          "crops, batch 64 per GPU, r=1024, dim=128, m=0.999, T=0.1, SGD lr 1e-3",
+              "inputs": "the crop pairs of the run are cut once and stay resident in HBM (no host-to-device copy "
+                        "inside the timed region; the CPU baseline is timed the same way)",
+              "global_batch": B * world, "parallelism": "dp%d" % world,
+              "conv_arithmetic": ("f32 products as 6 bf16 MFMA products of a 3-way bf16 cut, f32 accumulate "
+                                  "(f32-equivalent; MI_CONV_ARITH=f32 for the f32 MFMA)" if arith == "bf16x3"
+                                  else "v_mfma_f32_32x32x2_f32"),
+              "hipgraph": bool(engine.use_graph), "final_loss": final_loss}
+    if not args.full or args.no_conv_profile:
+        # the headline only: the step's rate, its time and configuration (no pass after the timed region)
         if rank == 0:
-            emit({"metric": "subtomograms/sec (MoCo-3D train) + voxels/sec (heatmap+NMS) at 1/2/4/8 GPU",
-                  "value": B * world * args.steps / dt, "unit": "subtomograms/sec", "n_gpus": world,
-                  "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-                  "step_graph_nodes": step_nodes, "note": "--no-conv-profile: no roofline pass"})
+            rec = {"metric": "subtomograms/sec (MoCo-3D train) + voxels/sec (heatmap+NMS) at 1/2/4/8 GPU",
+                   "value": B * world * args.steps / dt, "unit": "subtomograms/sec", "n_gpus": world,
+                   "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+                   "higher_is_better": True, "rccl_ranks": ranks_seen,
+                   "dist_backend": (dist.get_backend() if dist_active else None),
+                   "scaling": "weak", "dtype": "f32", "data": "synthetic", "config": config,
+                   "step_graph_nodes": step_nodes}
+            if args.full:
+                rec["note"] = "--no-conv-profile: no roofline pass"
+            emit(rec)
         if dist_active:
-            dist.barrier()
-            engine.close()
-            dist.destroy_process_group()
+            rc = teardown(engine, dist)
+            if rc:
+                sys.exit(rc)
         return
     flop, ms, n_launch, by = conv_profile(engine, pq, pk, B, 3)
-    arith = "f32" if os.environ.get("MI_CONV_ARITH", "")[:1] == "f" else "bf16x3"
     # the same step on the f32 MFMA instruction (fresh graph capture; N = 1 only: a reported comparison, not `value`)
     f32_ms = None
     if not dist_active and arith == "bf16x3" and not args.no_secondary:
@@ -584,15 +643,7 @@ def main():
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             "rccl_ranks": ranks_seen, "dist_backend": (dist.get_backend() if dist_active else None),
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "moco_main.py moco3d_18: 3D encoder, synthetic 512x512x128 tomogram, 32^3 subtomo "
-                                   "crops, batch 64 per GPU, r=1024, dim=128, m=0.999, T=0.1, SGD lr 1e-3",
-                       "inputs": "the crop pairs of the run are cut once and stay resident in HBM (no host-to-device copy "
-                                 "inside the timed region; the CPU baseline is timed the same way)",
-                       "global_batch": B * world, "parallelism": "dp%d" % world,
-                       "conv_arithmetic": ("f32 products as 6 bf16 MFMA products of a 3-way bf16 cut, f32 accumulate "
-                                           "(f32-equivalent; MI_CONV_ARITH=f32 for the f32 MFMA)" if arith == "bf16x3"
-                                           else "v_mfma_f32_32x32x2_f32"),
-                       "hipgraph": bool(engine.use_graph), "final_loss": final_loss},
+            "config": config,
             "step_graph_nodes": step_nodes,
             "step_mfma_frac_of_peak": value / world * FLOP_PER_SUBTOMO / 1e12 / peak,
             "roofline": {"bound": "mfma", "kernel": "the conv family: direct3 / direct3s / direct3_wgrad / cube2 / pair_wgrad / stem_fwd_bf3 / stem_wgrad_bf3 / conv_igemm (+ split-K reduces): all 75 conv calls of a step, forward / data gradient / weight gradient",
@@ -692,21 +743,26 @@ def main():
         out = head
         emit(out)                                    # the line is out before any tear-down
     if dist_active:
-        # tear-down in dependency order: the captured hipGraph (it holds the RCCL kernels and the events of the async
-        # work handles recorded during capture) goes before the communicator it refers to
-        rc = 0
-        try:
-            dist.barrier()
-            engine.close()
-            dist.destroy_process_group()
-        except Exception:
-            import traceback
-            traceback.print_exc()
-            rc = 3                                   # a failed tear-down is a failed run, never a silent exit 0
-        sys.stdout.flush()
-        sys.stderr.flush()
+        rc = teardown(engine, dist)
         if rc:
             sys.exit(rc)
+
+
+def teardown(engine, dist):
+    """Data parallel: tear-down in dependency order - the captured hipGraph (it holds the RCCL kernels and the events of
+    the async work handles recorded during capture) goes before the communicator it refers to.  Returns the exit code."""
+    rc = 0
+    try:
+        dist.barrier()
+        engine.close()
+        dist.destroy_process_group()
+    except Exception:
+        import traceback
+        traceback.print_exc()
+        rc = 3                                       # a failed tear-down is a failed run, never a silent exit 0
+    sys.stdout.flush()
+    sys.stderr.flush()
+    return rc
 
 
 if __name__ == "__main__":

@@ -95,7 +95,8 @@ def test_bench_n_gt_1_path_on_one_rank_rccl_group_tears_down():
     import json
     env = dict(os.environ, CETPICK_BENCH_REHEARSE_RCCL="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "10", "--warmup", "4", "--no-secondary", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "10", "--warmup", "4", "--full", "--no-secondary",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     # no retry: a failure here is reported with the child's output (profiles/r04_watchdog_abort.txt was found that way)
     assert r.returncode == 0, "exit %d\nstdout tail: %s\nstderr tail: %s" % (r.returncode, r.stdout[-1500:], r.stderr[-6000:])

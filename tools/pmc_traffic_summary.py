@@ -1,4 +1,5 @@
-"""profiles/r01_conv_traffic.json from the two PMC passes of tools/pmc_traffic.sh (gpurun_out/pmc_traffic/{FETCH_SIZE,WRITE_SIZE})."""
+"""profiles/r01_conv_traffic.json from the two PMC passes of tools/pmc_traffic.sh: `python tools/pmc_traffic_summary.py <its output dir>`
+(<dir>/FETCH_SIZE, <dir>/WRITE_SIZE)."""
 import csv, glob, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,7 +8,7 @@ AUX = ("splitk_reduce_kernel", "stem_wgrad_reduce_kernel", "stem_wprep_kernel")
 
 
 def total(counter):
-    f = glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_traffic", counter, "**", "*counter_collection.csv"), recursive=True)
+    f = glob.glob(os.path.join(sys.argv[1], counter, "**", "*counter_collection.csv"), recursive=True)
     assert f, "no counter_collection.csv for " + counter
     tot, calls, disp = 0.0, 0, 0
     for r in csv.DictReader(open(f[0])):
@@ -25,7 +26,7 @@ write_kb, calls_w, _ = total("WRITE_SIZE")
 assert calls == calls_w, (calls, calls_w)
 hbm = 2 * fetch_kb * 1024 + write_kb * 1024
 out = {
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/pmc_traffic.sh) over `bench.py --no-secondary "
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/pmc_traffic.sh) over `bench.py --full --no-secondary "
               "--no-cpu-baseline --steps 6 --warmup 2 --no-graph`; kernels conv_igemm / stem_* / splitk_reduce; a conv call = one "
               "dispatch of the main kernel (its reduce / weight-preparation dispatches are counted into it)",
     "fetch_size_kb_raw": fetch_kb, "write_size_kb": write_kb, "dispatches": disp, "conv_calls": calls,
