@@ -5,6 +5,8 @@ the reference datasets, without their per-pick Python loops.
 for a whole list of picks at once; `crop_znorm` makes the z-normalised 3-D crops the MoCo-3D encoder
 consumes.  The volume stays resident on the device; centres are (x, y, z) like the picker returns.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -144,3 +146,81 @@ def crop_znorm_rescale_znorm(v, tomo_coords, size, flip_x=False):
     """datasets/tomo_pre.py:57-60 (deterministic tail of the torchio chain) for every window: (n, 1, cz, cy, cx) =
     ZNormalization(RescaleIntensity(-3, 3)(ZNormalization(crop)))."""
     return _crop(v, tomo_coords, size, ZNORM_RESCALE_ZNORM, flip_x).unsqueeze(1)
+
+
+def tilt_border(crop):
+    """datasets/tomo_pre_proj_angle_select_new2d3d.py:117,:189 `crop // 1.8`: Python float floor division (36 -> 19.0)."""
+    return int(crop) // 1.8
+
+
+def check_tilt_crop(crop_x, crop_y, H, W):
+    """The 2d3d tilt windows need an even crop (the reference's `t -/+ c//2` slice has c - 1 pixels for an odd c and its
+    CenterCrop pads them back); with an even crop the skip rule keeps every window inside the (H, W) image - checked here,
+    not trusted.  Raises ValueError before any device work."""
+    cx, cy = int(crop_x), int(crop_y)
+    if cx <= 0 or cy <= 0 or cx % 2 or cy % 2:
+        raise ValueError("the 2d3d mode needs an even --bbox (got %d x %d): the reference's tilt windows are c - 1 pixels "
+                         "wide for an odd c" % (cx, cy))
+    if cx * cy * 4 > 48 * 1024:
+        raise ValueError("2d3d tilt patches of %d x %d exceed the kernel's 48 KiB window" % (cx, cy))
+    for c, n in ((cx, W), (cy, H)):
+        b = tilt_border(c)
+        lo, hi = math.floor(b) + 1, math.ceil(n - b) - 1          # first / last centre the skip rule lets through
+        if lo <= hi:
+            assert lo - c // 2 >= 0 and hi + c // 2 <= n, (c, n, b)
+
+
+class TiltStacks:
+    """The tilt series of a dataset resident on the device, with their descriptors (struct mi_tilt_desc: stack pointer,
+    cos / sin of the tilt angles, T, H, W, the full-resolution tomogram depth).  `stacks`: [(tilts (T, H, W) fp32 cuda,
+    angles in degrees (T,), Zfull)]."""
+
+    def __init__(self, stacks):
+        if not stacks:
+            raise L.HipExtensionError("TiltStacks: no tilt series")
+        dev = L.require_cuda(stacks[0][0], "tilts").device
+        self.tilts, self.cos_sin, self.shapes = [], [], []
+        desc = np.zeros((len(stacks), 4), dtype=np.int64)
+        for i, (tilts, angles, zfull) in enumerate(stacks):
+            t = L.require_cuda(tilts, "tilts").contiguous()
+            if t.dim() != 3:
+                raise L.HipExtensionError("TiltStacks: tilt series must be (T, H, W), got %s" % (tuple(t.shape),))
+            a = [float(v) for v in np.asarray(angles, dtype=np.float64).ravel()]
+            if len(a) != t.shape[0]:
+                raise L.HipExtensionError("TiltStacks: %d angles for %d tilts" % (len(a), t.shape[0]))
+            # the reference's `angle*np.pi/180` through math.cos / math.sin, on the host: a device cos may differ in the
+            # last ulp and flip an int() at a window boundary
+            cs = [math.cos(v * math.pi / 180) for v in a] + [math.sin(v * math.pi / 180) for v in a]
+            cs = torch.tensor(cs, dtype=torch.float64).to(dev)
+            T, H, W = (int(s) for s in t.shape)
+            desc[i] = (t.data_ptr(), cs.data_ptr(), T | (H << 32), W | (int(zfull) << 32))
+            self.tilts.append(t)                                    # (kept alive: the table holds raw pointers)
+            self.cos_sin.append(cs)
+            self.shapes.append((T, H, W))
+        self.desc = torch.as_tensor(desc).to(dev)
+
+    def patches(self, centres, crop_x, crop_y, owner=None):
+        """`extract_patches` (:110-133) for every centre (x, y, z_full) of stack owner[i] (owner None: stack 0), one launch.
+        -> (patches (n, 1, crop_y, crop_x) fp32 in [0, 1], valid (n,) bool): valid False where the reference returns None."""
+        cx, cy = int(crop_x), int(crop_y)
+        for _, h, w in self.shapes:
+            check_tilt_crop(cx, cy, h, w)
+        dev = self.desc.device
+        c = _centres(centres, dev).reshape(-1, 3)
+        n = int(c.shape[0])
+        own = None
+        if owner is not None:
+            own = _centres(owner, dev).reshape(-1)
+            if int(own.numel()) != n:
+                raise L.HipExtensionError("TiltStacks.patches: %d owners for %d centres" % (int(own.numel()), n))
+        out = torch.empty((n, 1, cy, cx), dtype=torch.float32, device=dev)
+        valid = torch.empty((n,), dtype=torch.uint8, device=dev)
+        L.check(L.lib().mi_tilt_patches(L.ptr(self.desc), len(self.shapes), L.ptr(own), L.ptr(c), n, cy, cx,
+                                        float(tilt_border(cx)), float(tilt_border(cy)), L.ptr(out), L.ptr(valid), L.stream()),
+                "mi_tilt_patches")
+        return out, valid.bool()
+
+
+def tilt_patches(tilts, angles, zfull, centres, crop_x, crop_y):
+    """One tilt series: `TiltStacks([(tilts, angles, zfull)]).patches(centres, crop_x, crop_y)`."""
+    return TiltStacks([(tilts, angles, zfull)]).patches(centres, crop_x, crop_y)

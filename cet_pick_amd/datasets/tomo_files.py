@@ -46,6 +46,37 @@ def read_image_list(path):
     return out
 
 
+COLUMNS_2D3D = ("image_name", "rec_path", "tilt_path", "angle_path")
+
+
+def read_image_list_2d3d(path):
+    """The 2d3d list (docs/explore.md:20-37; read at datasets/tomo_pre_proj_angle_select_new2d3d.py:155-156): the
+    tab-separated columns image_name, rec_path, tilt_path and angle_path, in any order.  Relative paths are taken relative
+    to the list's directory, as `read_image_list` takes them.  -> [(name, rec_path, tilt_path, angle_path)]"""
+    if not os.path.isfile(path):
+        raise FileNotFoundError("image list %s not found (--train_img_txt / --test_img_txt under <cwd>/data; --dataset "
+                                "simsiam2d3d without a list trains on a synthetic tomogram and tilt series)" % path)
+    with open(path) as f:
+        lines = [ln.rstrip("\n").rstrip("\r") for ln in f if ln.strip()]
+    header = lines[0].split("\t") if lines else []
+    missing = [c for c in COLUMNS_2D3D if c not in header]
+    if missing:
+        raise ValueError("%s: the 2d3d list needs the tab-separated columns %s; missing %s (header %s)"
+                         % (path, " ".join(COLUMNS_2D3D), " ".join(missing), header))
+    idx = [header.index(c) for c in COLUMNS_2D3D]
+    base = os.path.dirname(os.path.abspath(path))
+    out = []
+    for k, ln in enumerate(lines[1:], start=2):
+        cols = ln.split("\t")
+        if len(cols) <= max(idx):
+            raise ValueError("%s line %d: %d columns, the header names %d" % (path, k, len(cols), len(header)))
+        name, *paths = [cols[i] for i in idx]
+        out.append((name,) + tuple(p if os.path.isabs(p) else os.path.join(base, p) for p in paths))
+    if not out:
+        raise ValueError("%s lists no tomogram" % path)
+    return out
+
+
 def use_files(opt, split="train"):
     """True when the run reads tomograms from files: any `--dataset` other than 'synthetic' whose image list exists.  A
     missing list is announced (one line on stdout) and the synthetic tomogram takes its place - the plumbing configurations

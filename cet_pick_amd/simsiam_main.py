@@ -5,8 +5,9 @@ One process per GPU; under torch.distributed.run the ranks shard the crops (Dist
 drop_last) and exchange gradients over RCCL (hipops.GradExchange: one bucketed all-reduce of the flat gradient arena)
 with SyncBN statistics.
 
-The reference datasets (MRC lists, torchvision augmentation) are out of scope: the crops come from the DoG picker and
-the crop kernels on synthetic tomograms (datasets/synthetic_datasets.py), same batch contract.
+The crops come from the DoG picker and the crop kernels, on listed MRC files (datasets/tomo_files.py) or synthetic tomograms
+(datasets/synthetic_datasets.py); task simsiam2d3d pairs tilt-series and tomogram patches (datasets/simsiam2d3d.py).  The
+reference's random torchvision augmentations are out of scope.
 """
 import os
 import random
@@ -53,6 +54,8 @@ def build(opt):
     rank, world = init_distributed(opt)
     opt.rank_, opt.world_ = rank, world
     Dataset = SyntheticSimSiamDataset
+    if opt.task == "simsiam2d3d":                   # tilt-series + tomogram patch pairs (datasets/simsiam2d3d.py)
+        from .datasets.simsiam2d3d import SyntheticSimSiam2D3DDataset as Dataset
     opt = opts().update_dataset_info_and_set_heads(opt, Dataset)
 
     print("Creating model...")
@@ -73,7 +76,10 @@ def build(opt):
     print("Setting up data...")
     from .datasets.tomo_files import use_files
     if use_files(opt):
-        from .datasets.tomo_files import TomoFileSimSiamDataset as Dataset
+        if opt.task == "simsiam2d3d":
+            from .datasets.simsiam2d3d import TomoFileSimSiam2D3DDataset as Dataset
+        else:
+            from .datasets.tomo_files import TomoFileSimSiamDataset as Dataset
     dataset = Dataset(opt, "train", (3, opt.bbox, opt.bbox), sigma1=opt.dog, device=opt.device, rank=rank, world=world)
     return opt, model, optimizer, trainer, dataset
 

@@ -4,6 +4,8 @@ SURVEY.md §8(d) defines the synthetic tomogram: fp32 N(0,1) noise plus Gaussian
 centres keep a minimum pairwise distance so greedy-NMS results are tie-free.  Stored (Z, H, W),
 i.e. the in-memory order the reference holds after ``load_rec`` (utils/loader.py:27-88).
 """
+import math
+
 import numpy as np
 
 
@@ -41,6 +43,34 @@ def make_tomo(shape, seed=317, blob_spacing=16, margin_xy=40, margin_z=12, dtype
         vol[z0:z1, y0:y1, x0:x1] += (amp * g).astype(np.float32)
         centres.append((px, py, pz))
     return vol.astype(dtype, copy=False), np.asarray(centres, dtype=np.int32).reshape(-1, 3)
+
+
+def make_tilt_series(vol, angles):
+    """A crude tilt series of `vol` (Z, H, W) for the 2d3d mode's tests: tilt t is the ray sum of the volume along the
+    direction the 2d3d datasets assume (datasets/tomo_pre_proj_angle_select_new2d3d.py:91-96), voxel (x, y, z) landing on
+    tilt column round((x - W//2) cos a + ((Z - z) - Z//2) sin a + W//2) of row y; columns outside [0, W) are dropped.
+    -> (T, H, W) float32."""
+    vol = np.asarray(vol, dtype=np.float32)
+    z, h, w = vol.shape
+    zz, yy, xx = np.meshgrid(np.arange(z), np.arange(h), np.arange(w), indexing="ij")
+    vals = vol.astype(np.float64).ravel()
+    out = np.zeros((len(angles), h, w), dtype=np.float64)
+    for t, a in enumerate(np.asarray(angles, dtype=np.float64).ravel()):
+        r = float(a) * math.pi / 180                  # (scalar libm cos / sin, not numpy's SIMD ones: the same on every CPU)
+        tx = np.rint((xx - w // 2) * math.cos(r) + ((z - zz) - z // 2) * math.sin(r) + w // 2).astype(np.int64).ravel()
+        m = (tx >= 0) & (tx < w)
+        # (bincount adds in voxel order: the same sums on every machine)
+        out[t] = np.bincount(yy.ravel()[m] * w + tx[m], weights=vals[m], minlength=h * w).reshape(h, w)
+    return out.astype(np.float32)
+
+
+def tilt2d3d_inputs(seed=71):
+    """The regenerated inputs of tests/golden/tilt2d3d.npz: a (44, 96, 96) tomogram, its z-pair-max compressed twin
+    (22, 96, 96), the tilt series projected from the full tomogram at -60..60 degrees in steps of 3 (41 tilts, 13 of them
+    inside the 2d3d mode's [-20, 20] selection) and the angles.  -> (vol, vol_compressed, tilts, angles)"""
+    vol, _ = make_tomo((44, 96, 96), seed=seed, margin_xy=20, margin_z=10)
+    angles = np.arange(-60, 61, 3).astype(np.float64)
+    return vol, np.maximum(vol[0::2], vol[1::2]), make_tilt_series(vol, angles), angles
 
 
 def make_logits(shape, seed=317, n_peaks=None):

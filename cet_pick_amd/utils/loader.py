@@ -128,3 +128,50 @@ def cutup(data, blck, strd):
 
 def load_tlt(path):
     return np.loadtxt(path, ndmin=2)
+
+
+def _ordered_hw(shape, order):
+    """(H, W) of `rec_to_device(data of `shape`, order)` - the in-plane extents load_rec returns - from the shape alone."""
+    d0, d1, d2 = (int(s) for s in shape)
+    return {"xyz": (d0, d1), "xzy": (d0, d2), "yxz": (d1, d0), "zxy": (d1, d2)}[order]
+
+
+def _mrc_shape(path):
+    h = _mrc.parse_header(path)
+    return int(h["nz"]), int(h["ny"]), int(h["nx"])
+
+
+def check_tilt_rec_sizes(names, tilt_paths, rec_paths, angle_paths=None, order_tilt="zxy", order_rec="xzy"):
+    """Header-only check of a 2d3d list (no device work): every tilt series must have its tomogram's (H, W) - the docs
+    require equal sizes (docs/explore.md:46-50), the reference would read wrong pixels without a word - and, when the
+    angle files are given, one angle per tilt."""
+    for name, tp, rp, ap in zip(names, tilt_paths, rec_paths, angle_paths if angle_paths is not None else [None] * len(names)):
+        ts, rs = _mrc_shape(tp), _mrc_shape(rp)
+        thw, rhw = _ordered_hw(ts, order_tilt), _ordered_hw(rs, order_rec)
+        if thw != rhw:
+            raise ValueError("%s: the tilt series %s is %d x %d (H x W) but its tomogram %s is %d x %d; the 2d3d mode needs "
+                             "tilt images of the tomogram's size" % (name, tp, thw[0], thw[1], rp, rhw[0], rhw[1]))
+        if ap is not None:
+            n_ang = len(load_tlt(ap))
+            if n_ang != ts[0]:
+                raise ValueError("%s: %s lists %d angles for the %d tilts of %s" % (name, ap, n_ang, ts[0], tp))
+
+
+def load_tomo_all_and_angles_from_list(names, tilt_paths, rec_paths, angle_paths, order_tilt="zxy", order_rec="xzy",
+                                       compress=False, denoise=0):
+    """loader.py:139-152: ({name: tilt series (T, H, W)}, {name: tomogram (Z', H, W)}, {name: angles (T, 1)}); the images
+    preprocessed as `load_tomos_from_list` does them (tilts slice by slice), device tensors in [0, 1].
+
+    As in the reference the orders are fixed - 'zxy' for the tilt series, 'xzy' for the tomograms - and `--order` does not
+    reach this function; `compress` applies to the tomograms only.  Raises ValueError (before any device work) when a tilt
+    series and its tomogram differ in (H, W) or the angle file does not list one angle per tilt."""
+    names, tilt_paths, rec_paths, angle_paths = list(names), list(tilt_paths), list(rec_paths), list(angle_paths)
+    check_tilt_rec_sizes(names, tilt_paths, rec_paths, angle_paths, order_tilt, order_rec)
+    tilt_ims, rec_ims, angles = {}, {}, {}
+    for name, tp, rp, ap in zip(names, tilt_paths, rec_paths, angle_paths):
+        tilt = load_rec(tp, order=order_tilt, compress=False, is_tilt=True)
+        rec = load_rec(rp, order=order_rec, compress=compress, is_tilt=False)
+        tilt_ims[name] = preprocess(tilt, denoise=denoise, is_tilt=True)
+        rec_ims[name] = preprocess(rec, denoise=denoise, is_tilt=False)
+        angles[name] = load_tlt(ap)
+    return tilt_ims, rec_ims, angles

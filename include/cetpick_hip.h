@@ -164,6 +164,24 @@ int mi_crop_normalize_table(const mi_vol_desc* vols, const int32_t* owner, const
  * Normalize; mean / std = the dataset statistics of tomo_pre_proj_angle_select_new3d_vol.py:238-239).  y may alias x. */
 int mi_u8_roundtrip_normalize(const float* x, float* y, size_t n, float mean, float std, mi_stream_t stream);
 
+/* Tilt-series patches of the 2d3d exploration mode (datasets/tomo_pre_proj_angle_select_new2d3d.py:91-133
+ * `convert_tomo_to_tilt` + `extract_patches`), one per centre.  Centre i = (x, y, z_full) of stack owner[i]
+ * (owner == NULL: stack 0).  For every tilt t of that stack, in order:
+ *     tx = (int)((x - W/2) cos a_t + ((Zfull - z_full) - Zfull/2) sin a_t + W/2)      (fp64, no contraction, trunc)
+ *     ty = y;  the tilt is skipped when tx <= bx || tx >= W - bx || ty <= by || ty >= H - by
+ * patch = fp32 sum in tilt order of tilts[t, ty-cy/2 : ty+cy/2, tx-cx/2 : tx+cx/2]; out[i] = (p - min) / (max - min)
+ * (cy, cx) and valid[i] = 1, or out[i] = 0 and valid[i] = 0 when no tilt survived or min == max.  cos_sin holds
+ * cos a_t for t < T and sin a_t at T + t (host-computed fp64).  A tilt whose window would leave the stack is skipped
+ * too (never the case for even crops with bx >= cx/2 - 1, by >= cy/2 - 1).  cx, cy even; n <= (2^32 - 1) / 256 (one
+ * 256-thread workgroup per centre; MI_E_UNSUPPORTED above).  All arrays device memory. */
+typedef struct mi_tilt_desc {
+    const float* tilts;       /* (T, H, W) fp32 */
+    const double* cos_sin;    /* (2, T) */
+    int32_t T, H, W, Zfull;
+} mi_tilt_desc;
+int mi_tilt_patches(const mi_tilt_desc* stacks, int n_stacks, const int32_t* owner, const int32_t* centres_xyz, int64_t n,
+                    int cy, int cx, double bx, double by, float* out, uint8_t* valid, mi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training path: channels-last fp32 activations (N,D,H,W,C),
  * weights [tap][Cin][Cout] with tap = (kd*k + kh)*k + kw.
