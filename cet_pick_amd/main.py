@@ -6,7 +6,10 @@ drops of `--lr_step` and the `log.txt` line.  One process per GPU; under torch.d
 ranks draw different crop pairs and exchange gradients over RCCL (hipops.GradExchange) with SyncBN statistics
 (main.py:34-56).
 
-The reference datasets are out of scope: labelled synthetic tomograms (datasets/synthetic_datasets.py), same batch contract.
+Data: with `--dataset semi` (any dataset but 'synthetic') and an image list at `--train_img_txt`, the listed tomograms and the
+coordinate table `--train_coord_txt` (datasets/semi_files.py `TomoFileDetectorDataset`: the reference's TOMOMoco +
+ParticleMocoDataset); validation then runs on `--val_img_txt` / `--val_coord_txt` (default: the train files).  Without a list,
+or with `--dataset synthetic`, labelled synthetic tomograms (datasets/synthetic_datasets.py), same batch contract.
 """
 import os
 
@@ -14,6 +17,8 @@ import torch
 import torch.distributed as dist
 
 from . import hipops as H
+from .datasets import tomo_files
+from .datasets.semi_files import TomoFileDetectorDataset
 from .datasets.synthetic_datasets import SyntheticDetectorDataset
 from .models.model import create_model, load_model, save_model
 from .opts import opts
@@ -25,7 +30,12 @@ from .utils.utils import TextLog
 def main(opt):
     torch.manual_seed(opt.seed)
     rank, world = init_distributed(opt)
-    Dataset = SyntheticDetectorDataset
+    files = tomo_files.use_files(opt)
+    Dataset = TomoFileDetectorDataset if files else SyntheticDetectorDataset
+    coord_path = os.path.join(opt.data_dir, opt.train_coord_txt)
+    if files and not os.path.isfile(coord_path):
+        raise FileNotFoundError("coordinate file %s not found: training on the listed tomograms needs --train_coord_txt"
+                                % coord_path)
     opt = opts().update_dataset_info_and_set_heads(opt, Dataset)
     logger = TextLog(opt, enabled=rank == 0)
 
@@ -45,8 +55,11 @@ def main(opt):
         trainer.set_device(opt.gpus, opt.chunk_sizes, opt.device)
 
     print("Setting up data...")
-    val_set = Dataset(opt, "train", device=opt.device, per_epoch=4 * max(1, opt.batch_size), rank=0, world=1)
-    val_set.set_epoch(10 ** 6)                    # a fixed held-out draw of crop pairs
+    if files:
+        val_set = Dataset(opt, "val", device=opt.device) if opt.val_img_txt else None    # whole listed val tomograms
+    else:
+        val_set = Dataset(opt, "train", device=opt.device, per_epoch=4 * max(1, opt.batch_size), rank=0, world=1)
+        val_set.set_epoch(10 ** 6)                # a fixed held-out draw of crop pairs
     if opt.test:
         log_dict_val, _ = trainer.val(0, val_set)
         print(log_dict_val)

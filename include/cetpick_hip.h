@@ -182,6 +182,27 @@ typedef struct mi_tilt_desc {
 int mi_tilt_patches(const mi_tilt_desc* stacks, int n_stacks, const int32_t* owner, const int32_t* centres_xyz, int64_t n,
                     int cy, int cx, double bx, double by, float* out, uint8_t* valid, mi_stream_t stream);
 
+/* Label volume of one tomogram for the detector training on coordinate files (datasets/tomo_moco.py:77-130 `load_data`):
+ * hm (D, H, W) fp32 is zeroed, then the (2r+1)^3 fp32 stencil (host-computed: gaussian3D or gaussian3D_discrete of
+ * utils/image.py, cast once to fp32) is max-combined at each of the n centres (x, y, z) int32, clipped by box intersection
+ * with the volume (`draw_umich_gaussian_3d`; centres outside the volume stamp what of their box is inside).  Stencil values
+ * must be >= 0: the max is an unsigned atomic max on the fp32 bits (deterministic).  fill_unlabeled != 0: every exact 0
+ * becomes -1 afterwards (the train split, :121-123).  Up to three operations on the stream (zero, scatter, fill).  r <= 64;
+ * all arrays device memory. */
+int mi_semi_labels(float* hm, int D, int H, int W, const int32_t* centres_xyz, int64_t n, const float* stencil, int r,
+                   int fill_unlabeled, mi_stream_t stream);
+/* The crop pairs of one training batch of the detector (datasets/particle_moco.py:34-163 at down_ratio 2): crop i of the
+ * launch is table entry s = first + i, cut around the downscaled centre (x, y, z) = centres_xyz[s] from tomogram
+ * tomos[owner[s]] and its label volume labels[owner[s]] (same depth, half the height and width):
+ *     input[i]     = tomo[z-3 : z+3, 2y-32 : 2y+32, 2x-32 : 2x+32]        (n, 6, 64, 64)
+ *     input_aug[i] = input[i] mirrored along y (flip_y != 0, flip_ud) or x (flip_lr)
+ *     hm[i]        = label[z-3 : z+3, y-16 : y+16, x-16 : x+16]           (n, 1, 6, 32, 32)
+ * The host draws windows inside both volumes; an entry whose window is not (or whose owner is out of range) reads nothing and
+ * gives zeros.  One 256-thread workgroup per crop; all arrays device memory. */
+int mi_semi_pairs(const mi_vol_desc* tomos, const mi_vol_desc* labels, int n_tomos, const int32_t* owner,
+                  const int32_t* centres_xyz, int64_t first, int n, int flip_y, float* input, float* input_aug, float* hm,
+                  mi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training path: channels-last fp32 activations (N,D,H,W,C),
  * weights [tap][Cin][Cout] with tap = (kd*k + kh)*k + kw.
