@@ -1315,6 +1315,9 @@ size_t dog_ws_layout(int D, int H, int W, DogWs* w, char* base) {
 
 extern "C" size_t mi_dog_pick_workspace_bytes(int D, int H, int W, int n_sigmas) {
     (void)n_sigmas;
+    // a volume mi_dog_pick refuses (2^31 voxels and up) needs no workspace: a token size, so that a caller makes the call and
+    // reads the refusal instead of allocating ~15 volumes first (117 GiB at 2048 x 1024 x 1024)
+    if (D > 0 && H > 0 && W > 0 && (size_t)D * H * W >= (1ull << 31)) return 256;
     return dog_ws_layout(D, H, W, nullptr, nullptr);
 }
 

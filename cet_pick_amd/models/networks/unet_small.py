@@ -24,6 +24,32 @@ def _xavier_normal_(w):
         w.normal_(0.0, (2.0 / (fan_in + fan_out)) ** 0.5)
 
 
+# The kernels address an operand with 32-bit byte offsets: each of them declines (or refuses) one of 0x7fff0000 bytes or more
+# (conv_d32.hip, conv_direct3.hip, conv_igemm.hip - the last for a batch of one, which it cannot split).
+HEAD_OPERAND_LIMIT = 0x7fff0000
+HEAD_HALO = 3                       # z-planes a head output reads on either side: two 3 x 3 x 3 layers and the (3, 1, 1) heads
+
+
+def head_z_slabs(b, d, plane_bytes, slab=0):
+    """The launches of the 3-D head at inference, or None when it runs once on the whole (b, d) volume.
+    plane_bytes: one z-plane of one batch item of the widest head operand (4 * hh * ww * channels).  Otherwise a list of
+    (item, z0, n, lo, hi): batch item `item`, output planes [z0, z0 + n) computed from input planes [lo, hi) - the slab
+    and its halo, clipped at the volume's ends.  Every launch's operands stay under HEAD_OPERAND_LIMIT; `slab` > 0 forces
+    slabs of at most that many planes even where the whole volume fits."""
+    if not slab and b * d * plane_bytes < HEAD_OPERAND_LIMIT:
+        return None
+    fit = (HEAD_OPERAND_LIMIT - 1) // plane_bytes - 2 * HEAD_HALO          # planes of a slab whose halo'd operand fits
+    if d * plane_bytes >= HEAD_OPERAND_LIMIT and fit < 1:
+        raise L.HipExtensionError("3-D head: one z-plane with its %d-plane halo is %d bytes, at or above the kernels' "
+                                  "%#x-byte operand limit" % (2 * HEAD_HALO, (1 + 2 * HEAD_HALO) * plane_bytes,
+                                                              HEAD_OPERAND_LIMIT))
+    step = d if d * plane_bytes < HEAD_OPERAND_LIMIT else fit
+    if slab:
+        step = min(step, slab)
+    return [(i, z0, min(step, d - z0), max(0, z0 - HEAD_HALO), min(d, z0 + step + HEAD_HALO))
+            for i in range(b) for z0 in range(0, d, step)]
+
+
 class DownConv(nn.Module):
     """unet.py:198-249: two 3x3 convolutions (+BN+ReLU) and a 2x2 ceil-mode max-pool."""
 
@@ -169,26 +195,26 @@ class TomoConvUNet(nn.Module):
             y = self.unet(H.conv_bn(self.conv1, self.bn1, x, relu=True))
         _, hh, ww, ch = y.shape
         v = y.view(b, d, hh, ww, ch)                                              # slices are the z axis again
-        slab = int(getattr(self, "head_slab", 0)) or (64 if 4 * v.numel() >= 0x7fff0000 else 0)
-        if slab and b == 1 and d > slab and not self.training and not torch.is_grad_enabled():
-            return [self._heads_in_z_slabs(v, slab)]
+        if not self.training and not torch.is_grad_enabled():
+            width = max([ch, self.feature_head[0].co] + list(self.heads.values()))
+            launches = head_z_slabs(b, d, 4 * hh * ww * width, int(getattr(self, "head_slab", 0)))
+            if launches is not None:
+                return [self._heads_in_z_slabs(v, launches)]
         return [self._heads(v)]
 
-    def _heads_in_z_slabs(self, v, slab):
-        """Inference on a volume whose 32-channel feature map reaches 2 GiB (256 x 512 x 512 in: 256 x 256 x 256 x 32 floats - the
-        kernels address an operand with 32-bit byte offsets): the 3-D head runs on z-slabs with a halo of three planes - one per
-        3 x 3 x 3 layer (z dilation 1) and one for the (3, 1, 1) heads -, whose interior planes are exactly the whole-volume result
-        (at the volume's own ends the zero padding IS the reference's)."""
+    def _heads_in_z_slabs(self, v, launches):
+        """Inference on a volume whose head operands reach 2 GiB (256 x 512 x 512 in: 256 x 256 x 256 x 32 floats - the kernels
+        address an operand with 32-bit byte offsets): the 3-D head runs per batch item on z-slabs with a halo of three planes - one
+        per 3 x 3 x 3 layer (z dilation 1) and one for the (3, 1, 1) heads -, whose interior planes are exactly the whole-volume
+        result (at the volume's own ends the zero padding IS the reference's).  launches: `head_z_slabs`."""
         b, d, hh, ww, _ = v.shape
         outs = {}
-        for z0 in range(0, d, slab):
-            lo, hi = max(0, z0 - 3), min(d, z0 + slab + 3)
-            part = self._heads(v[:, lo:hi])
-            n = min(slab, d - z0)
-            for k, t in part.items():                                             # logical (B, C, D, H, W)
+        for i, z0, n, lo, hi in launches:
+            part = self._heads(v[i:i + 1, lo:hi])
+            for k, t in part.items():                                             # logical (1, C, D, H, W)
                 if k not in outs:
                     outs[k] = torch.empty((b, d, hh, ww, t.shape[1]), dtype=t.dtype, device=t.device)
-                outs[k][:, z0:z0 + n] = t.permute(0, 2, 3, 4, 1)[:, z0 - lo:z0 - lo + n]
+                outs[k][i:i + 1, z0:z0 + n] = t.permute(0, 2, 3, 4, 1)[:, z0 - lo:z0 - lo + n]
             del part
         return {k: t.permute(0, 4, 1, 2, 3) for k, t in outs.items()}
 

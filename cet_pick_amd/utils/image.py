@@ -96,7 +96,9 @@ def dog_pick(rec, sigmas, kernel=3, border_z=10, nms_d=14, max_out=None, return_
     lib = L.lib()
     ws = L.workspace(lib.mi_dog_pick_workspace_bytes(D, H, W, len(sigmas)), v.device, "dog")
     if max_out is None:
-        max_out = min(D * H * W // 4 + 1024, 1 << 17)   # picks are >= d apart: 128 Ki covers a 512x512x512 volume at d=14
+        # picks are >= d apart: 128 Ki covers a 512x512x512 volume at d=14; a 520 x 1024 x 1024 tomogram gives ~133 Ki picks
+        # (synthetic, d=14), so past 2^27 voxels the room grows with the volume (one slot per 1024 voxels)
+        max_out = min(D * H * W // 4 + 1024, max(1 << 17, (D * H * W) >> 10))
     scores = torch.empty((max_out,), dtype=torch.float32, device=v.device)
     coords = torch.empty((max_out, 3), dtype=torch.int32, device=v.device)
     n = torch.empty((1,), dtype=torch.int32, device=v.device)          # (both written by the chain on every path: the pick
@@ -110,9 +112,10 @@ def dog_pick(rec, sigmas, kernel=3, border_z=10, nms_d=14, max_out=None, return_
     return scores, coords, n, cutoff, heat
 
 
-def get_potential_coords_pyramid(rec, sigmas=[2, 4], num_pyramid=3, kernel=3, border_z=10):
-    """utils/image.py:138-183.  (border_z is the reference's hard-coded 10 slices, exposed.)"""
-    scores, coords, n, cutoff, _ = dog_pick(rec, sigmas, kernel=kernel, border_z=border_z)
+def get_potential_coords_pyramid(rec, sigmas=[2, 4], num_pyramid=3, kernel=3, border_z=10, max_out=None):
+    """utils/image.py:138-183.  (border_z is the reference's hard-coded 10 slices, exposed; max_out: `dog_pick`'s - more
+    picks than that raise, they are never truncated.)"""
+    scores, coords, n, cutoff, _ = dog_pick(rec, sigmas, kernel=kernel, border_z=border_z, max_out=max_out)
     k = int(n.item())
     if k < 0:
         raise L.HipExtensionError("DoG picker overflow (code %d)" % k)

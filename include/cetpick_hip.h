@@ -120,7 +120,8 @@ int mi_zscore_quantize_minmax(const float* x, float* y, long n_slices, long slic
  * cutoff = mean(pos)+0.5*std(pos) -> greedy 3-D NMS (`non_maximum_suppression_3d`, distance d).
  * Outputs (device): scores[max_out] fp32, coords[max_out][3] int32 as (x,y,z), n_out int32,
  * cutoff_out fp32 (may be NULL).  Picks are emitted in greedy order (score descending).
- * heat_out (may be NULL) receives the dense NMS'd DoG map (D*H*W). */
+ * heat_out (may be NULL) receives the dense NMS'd DoG map (D*H*W).  Volumes of 2^31 voxels or more are
+ * refused (MI_E_UNSUPPORTED); their workspace size is a token 256 bytes. */
 size_t mi_dog_pick_workspace_bytes(int D, int H, int W, int n_sigmas);
 int mi_dog_pick(const float* rec, int D, int H, int W, const float* sigmas_host, int n_sigmas,
                 int k, int border_z, int nms_d, float* heat_out, float* scores, int32_t* coords,

@@ -71,3 +71,48 @@ def test_factory_and_checkpoint_layout(tmp_path, capsys):
     assert m2.conv1.weight.stride() == m.conv1.weight.stride()            # kernel layout survives loading
     with pytest.raises(NotImplementedError):
         create_model("res_18", {"hm": 1}, 64)                             # exists in the reference, outside the hot path
+
+
+@pytest.mark.parametrize("plane", [512, 1024, 2048])
+@pytest.mark.parametrize("head_conv", [32, 64])
+def test_head_z_slabs_keep_every_operand_under_the_offset_limit(plane, head_conv):
+    """The detector's 3-D head at inference (unet_small.head_z_slabs): every launch's operand - the slab with its halo, of the
+    widest of the 32-channel feature map and the head_conv-channel layers - stays under the kernels' 0x7fff0000-byte limit, and
+    the slabs tile [0, d) of every batch item exactly once, with the three-plane halo clipped at the volume's ends."""
+    from cet_pick_amd.models.networks.unet_small import HEAD_OPERAND_LIMIT, head_z_slabs
+    assert HEAD_OPERAND_LIMIT == 0x7fff0000
+    hh = ww = plane // 2                                  # the stride-2 stem: the feature plane is half the tomogram's
+    plane_bytes = 4 * hh * ww * max(32, head_conv)
+    for d in (1, 63, 64, 65, 70, 200, 512):
+        for b in (1, 2):
+            launches = head_z_slabs(b, d, plane_bytes)
+            if b * d * plane_bytes < HEAD_OPERAND_LIMIT:
+                assert launches is None, (plane, head_conv, d, b)
+                continue
+            assert launches, (plane, head_conv, d, b)
+            covered = {i: [] for i in range(b)}
+            for i, z0, n, lo, hi in launches:
+                assert 0 <= i < b and n >= 1
+                assert (lo, hi) == (max(0, z0 - 3), min(d, z0 + n + 3))
+                assert (hi - lo) * plane_bytes < HEAD_OPERAND_LIMIT, (plane, head_conv, d, b, z0, n)
+                covered[i].append((z0, n))
+            for i, runs in covered.items():
+                ends = [0]
+                for z0, n in runs:
+                    assert z0 == ends[-1]
+                    ends.append(z0 + n)
+                assert ends[-1] == d, (plane, head_conv, d, b, i)
+    # the smallest head launch - one plane and its halo - of a 2048^2 feature plane at 64 channels no longer fits: refused
+    from cet_pick_amd._lib import HipExtensionError
+    with pytest.raises(HipExtensionError, match="0x7fff0000"):
+        head_z_slabs(1, 64, 4 * 2048 * 2048 * 64)
+    assert head_z_slabs(1, 1, 4 * 2048 * 2048 * 64) is None                # (one such plane alone is a 1 GiB operand)
+
+
+def test_head_z_slabs_forced_slab():
+    """`head_slab` forces slabs where the volume fits (the GPU test pins slabbed against whole-volume outputs with it)."""
+    from cet_pick_amd.models.networks.unet_small import head_z_slabs
+    assert head_z_slabs(1, 29, 4 * 32 * 32 * 32) is None
+    assert head_z_slabs(1, 29, 4 * 32 * 32 * 32, slab=8) == [(0, 0, 8, 0, 11), (0, 8, 8, 5, 19), (0, 16, 8, 13, 27),
+                                                            (0, 24, 5, 21, 29)]
+    assert [t[:3] for t in head_z_slabs(2, 10, 4 * 32 * 32 * 32, slab=8)] == [(0, 0, 8), (0, 8, 2), (1, 0, 8), (1, 8, 2)]
