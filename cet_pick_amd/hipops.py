@@ -156,6 +156,14 @@ class ParamArena:
             for p, o in zip(params, offs):
                 p._mi_grad_view2 = torch.as_strided(self.flat_grad2, p.shape, p.stride(), o)
                 p._mi_grad2_used = False
+        else:
+            self.drop_second_grads()               # views an earlier two-arena owner left behind would take every second contribution
+
+    def drop_second_grads(self):
+        """Remove the second-gradient views from the parameters: _grad_target accumulates a second contribution into .grad again."""
+        for p in self.params:
+            p.__dict__.pop("_mi_grad_view2", None)
+            p.__dict__.pop("_mi_grad2_used", None)
 
     def attach_grads(self):
         for p in self.params:
@@ -251,19 +259,35 @@ def _out_dims(shape5, k3, stride, p3):
     return tuple((v + 2 * p - k) // stride + 1 for v, k, p in zip((d, h, w), k3, p3))
 
 
-# Pre-cut weight images of the layer1-shaped convolutions (conv_direct3.hip).  Without a cache the C side rebuilds the image
-# of a weight on every convolution call (one extra launch); an owner that knows when the weights change - MocoStepEngine:
-# after the EMA kernel and after the SGD kernel - keeps them here and re-cuts a whole group in ONE launch.  The cache is
-# only consulted while ACTIVE_IMAGES is set (the engine sets it around its step), so a stale image can never reach a
-# convolution issued from anywhere else.
+# Pre-cut weight images of the conv_direct3.hip / conv_s2.hip / conv_p2d.hip convolutions.  Outside a step engine an image is cut in
+# front of its convolution (by the C side, or on the parameter: _kept_image); a step engine (trains/step_graph.py) knows when its weights
+# change, keeps them here and re-cuts a whole group in ONE launch per family.  The cache is only consulted while ACTIVE_IMAGES is set
+# (the engine sets it around its step), so a stale image can never reach a convolution issued from anywhere else.
 ACTIVE_IMAGES = None
+
+
+def _prep_images(fn, items):
+    """items: [(weight, None, dgrad flag, image tensor)] - all cut by `fn` (mi_conv3d_direct_prep / mi_conv2d_p2d_prep: one launch per 16)
+    on the current stream."""
+    import ctypes
+    n = len(items)
+    if not n:
+        return
+    ws = (ctypes.c_void_p * n)(*[it[0].data_ptr() for it in items])
+    imgs = (ctypes.c_void_p * n)(*[it[3].data_ptr() for it in items])
+    dg = (ctypes.c_int * n)(*[it[2] for it in items])
+    ch = (ctypes.c_int * n)(*[int(it[0].shape[0]) for it in items])
+    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    L.check(getattr(L.lib(), fn)(cast(ws), cast(imgs), cast(dg), cast(ch), n, L.stream()), fn)
 
 
 class WeightImages:
     def __init__(self):
-        self._groups = {}            # group -> list of (weight, dgrad flag, image tensor)
-        self._s2_groups = {}         # group -> list of (weight, shortcut weight, dgrad flag, image tensor)
-        self._by_weight = {}         # (weight storage address, dgrad [+ 2: stride-2 front]) -> image tensor
+        self._groups = {}            # group -> {family: [(weight, shortcut weight of an "s2" front or None, dgrad flag, image)]}
+        self._by_weight = {}         # (weight storage address, dgrad [+ 2: stride-2 front, + 4: p2d]) -> image tensor
+
+    def _family(self, group, fam):
+        return self._groups.setdefault(group, {"s2": [], "direct": [], "p2d": []})[fam]
 
     @staticmethod
     def eligible(w, k, stride, pad):
@@ -273,7 +297,7 @@ class WeightImages:
     def add(self, group, w, dgrad):
         nb = L.lib().mi_conv3d_direct_wimg_bytes(int(w.shape[0]))
         img = torch.empty(nb, dtype=torch.uint8, device=w.device)
-        self._groups.setdefault(group, []).append((w, int(bool(dgrad)), img))
+        self._family(group, "direct").append((w, None, int(bool(dgrad)), img))
         self._by_weight[(w.data_ptr(), int(bool(dgrad)))] = img
 
     def get(self, w, dgrad, n, d, h, wd):
@@ -289,14 +313,23 @@ class WeightImages:
         co, ci = int(w.shape[0]), int(w.shape[1])
         nb = lib.mi_conv3d_s2_dgrad_workspace_bytes(ci, co) if dgrad else lib.mi_conv3d_s2_fwd_workspace_bytes(ci, co)
         img = torch.empty(int(nb), dtype=torch.uint8, device=w.device)
-        self._s2_groups.setdefault(group, []).append((w, w_ds, int(bool(dgrad)), img))
+        self._family(group, "s2").append((w, w_ds, int(bool(dgrad)), img))
         self._by_weight[(w.data_ptr(), 2 + int(bool(dgrad)))] = img
 
     def get_s2(self, w, dgrad):
         return self._by_weight.get((w.data_ptr(), 2 + int(bool(dgrad))))
 
-    def _refresh_s2(self, group):
-        items = self._s2_groups.get(group)
+    # ---- the 2-D 3 x 3 / stride-1 C -> C layers (csrc/conv_p2d.hip): forward or data-gradient image ----
+    def add_p2d(self, group, w, dgrad):
+        img = torch.empty(int(L.lib().mi_conv2d_p2d_wimg_bytes(int(w.shape[0]))), dtype=torch.uint8, device=w.device)
+        self._family(group, "p2d").append((w, None, int(bool(dgrad)), img))
+        self._by_weight[(w.data_ptr(), 4 + int(bool(dgrad)))] = img
+
+    def get_p2d(self, w, dgrad):
+        return self._by_weight.get((w.data_ptr(), 4 + int(bool(dgrad))))
+
+    @staticmethod
+    def _refresh_s2(items):
         if not items:
             return
         import ctypes
@@ -312,27 +345,24 @@ class WeightImages:
                 "mi_conv3d_s2_prep")
 
     def refresh(self, group):
-        """Re-cut every image of `group` from the current weights: one launch (per 16 images) on the current stream, and one
-        for the group's stride-2 fronts."""
-        self._refresh_s2(group)
-        items = self._groups.get(group)
-        if not items:
+        """Re-cut every image of `group` from the current weights on the current stream: one launch for the group's stride-2
+        fronts, one (per 16 images) for its direct-kernel images, one for its p2d images."""
+        g = self._groups.get(group)
+        if g is None:
             return
-        import ctypes
-        n = len(items)
-        ws = (ctypes.c_void_p * n)(*[it[0].data_ptr() for it in items])
-        imgs = (ctypes.c_void_p * n)(*[it[2].data_ptr() for it in items])
-        dg = (ctypes.c_int * n)(*[it[1] for it in items])
-        ch = (ctypes.c_int * n)(*[int(it[0].shape[0]) for it in items])
-        L.check(L.lib().mi_conv3d_direct_prep(ctypes.cast(ws, ctypes.c_void_p), ctypes.cast(imgs, ctypes.c_void_p),
-                                              ctypes.cast(dg, ctypes.c_void_p), ctypes.cast(ch, ctypes.c_void_p), n,
-                                              L.stream()), "mi_conv3d_direct_prep")
+        self._refresh_s2(g["s2"])
+        _prep_images("mi_conv3d_direct_prep", g["direct"])
+        _prep_images("mi_conv2d_p2d_prep", g["p2d"])
+
+    def refresh_all(self):
+        for group in self._groups:              # (in registration order)
+            self.refresh(group)
 
     def versions(self):
         """Sum of the torch version counters of the cached weights: changes when anything but the engine's own kernels
         (which refresh by themselves) wrote a weight."""
-        return (sum(it[0]._version for items in self._groups.values() for it in items) +
-                sum(it[0]._version + (it[1]._version if it[1] is not None else 0) for items in self._s2_groups.values() for it in items))
+        return sum(it[0]._version + (it[1]._version if it[1] is not None else 0)
+                   for g in self._groups.values() for items in g.values() for it in items)
 
 
 def _arith_bf16x3():
@@ -359,6 +389,20 @@ WEIGHT_EPOCH = 0
 def _bump_weight_epoch():
     global WEIGHT_EPOCH
     WEIGHT_EPOCH += 1
+
+
+def _kept_image(holder, slot, w, geom, cut):
+    """`cut(previous image or None)`'s image of the weights `w`, kept as `holder.<slot>` and cut again when the storage, holder's version
+    (torch ops), WEIGHT_EPOCH (raw-pointer writes) or the geometry `geom` moved: the staleness rule of every lazily cut weight image."""
+    key = (w.data_ptr(), holder._version, WEIGHT_EPOCH) + geom
+    ent = getattr(holder, slot, None)
+    if ent is None or ent[0] != key:
+        ent = (key, cut(ent[1] if ent is not None else None))
+        try:
+            setattr(holder, slot, ent)
+        except AttributeError:
+            pass
+    return ent[1]
 
 
 def inference_mode():
@@ -390,18 +434,11 @@ def _smallk_image(w, owner, K, co):
     """The weight image of conv_smallk.hip for the kernel-layout weights `w` (a (K, co) matrix in memory), kept on `owner` (the
     parameter or folded-weight tensor that outlives the call) and rebuilt when the storage or its version changes."""
     lib = L.lib()
-    holder = owner if owner is not None else w
-    key = (w.data_ptr(), holder._version, WEIGHT_EPOCH, K, co)
-    cache = getattr(holder, "_mi_smallk", None)
-    if cache is None or cache[0] != key:
+    def cut(_):
         img = torch.empty(int(lib.mi_smallk_image_bytes(K, co)), dtype=torch.uint8, device=w.device)
         L.check(lib.mi_smallk_prep(L.ptr(w), L.ptr(img), K, co, L.stream()), "mi_smallk_prep")
-        cache = (key, img)
-        try:
-            holder._mi_smallk = cache
-        except AttributeError:
-            pass
-    return cache[1]
+        return img
+    return _kept_image(owner if owner is not None else w, "_mi_smallk", w, (K, co), cut)
 
 
 def _d32_kind(x5shape, ci, co, k3, stride, p3, d3, inference):
@@ -429,21 +466,15 @@ def _d32_call(x, w, bias, relu, kind, owner=None, out=None, pool=False):
     n, d, h, wd, ci = x5.shape
     ntap = 27 if kind == 2 else 1 if kind == 4 else 9
     co = int(w.shape[0]) if kind in (3, 4) else 32
-    holder = owner if owner is not None else w
-    key = (w.data_ptr(), holder._version, WEIGHT_EPOCH, ci, ntap, co)
-    cache = getattr(holder, "_mi_d32", None)
-    if cache is None or cache[0] != key:
+    def cut(_):
         if kind == 3 or (kind == 4 and co >= 64):
             img = torch.empty((co // 64) * int(lib.mi_conv_d64_image_bytes(ci, ntap)), dtype=torch.uint8, device=w.device)
             L.check(lib.mi_conv_d64_prep_co(L.ptr(w), L.ptr(img), ci, co, ntap, L.stream()), "mi_conv_d64_prep_co")
         else:
             img = torch.empty(int(lib.mi_conv_d32_image_bytes(ci, ntap)), dtype=torch.uint8, device=w.device)
             L.check(lib.mi_conv_d32_prep(L.ptr(w), L.ptr(img), ci, ntap, L.stream()), "mi_conv_d32_prep")
-        cache = (key, img)
-        try:
-            holder._mi_d32 = cache
-        except AttributeError:
-            pass
+        return img
+    wimg = _kept_image(owner if owner is not None else w, "_mi_d32", w, (ci, ntap, co), cut)
     shape = tuple(x.shape[:-1]) + (co,)
     if pool:                                          # kinds 1 / 3: the 2 x 2 max-pool of the result as a second output
         cstride = co
@@ -458,7 +489,7 @@ def _d32_call(x, w, bias, relu, kind, owner=None, out=None, pool=False):
                     or cstride < co or cstride % 4 or out.data_ptr() % 16):
                 raise L.HipExtensionError("`out` must be an fp32 %s tensor or a channel slice of a wider contiguous one" % (shape,))
         pooled = torch.empty(tuple(x.shape[:-3]) + (h // 2, wd // 2, co), dtype=torch.float32, device=x.device)
-        L.check(lib.mi_conv_d32_fwd_pool_strided_f32(L.ptr(x), L.ptr(cache[1]), L.ptr(bias), L.ptr(out), cstride, L.ptr(pooled),
+        L.check(lib.mi_conv_d32_fwd_pool_strided_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), cstride, L.ptr(pooled),
                                                      int(relu), n, d, h, wd, ci, co, L.stream()), "mi_conv_d32_fwd_pool_strided_f32")
         return out, pooled
     if out is None:
@@ -468,12 +499,12 @@ def _d32_call(x, w, bias, relu, kind, owner=None, out=None, pool=False):
 
     def call():
         if kind == 4:
-            return L.check(lib.mi_conv_d32_1x1_fwd_f32(L.ptr(x), L.ptr(cache[1]), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, co,
+            return L.check(lib.mi_conv_d32_1x1_fwd_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, co,
                                                        L.stream()), "mi_conv_d32_1x1_fwd_f32")
         if kind == 3:
-            return L.check(lib.mi_conv_d64_fwd_f32(L.ptr(x), L.ptr(cache[1]), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, co,
+            return L.check(lib.mi_conv_d64_fwd_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, co,
                                                    L.stream()), "mi_conv_d64_fwd_f32")
-        return L.check(lib.mi_conv_d32_fwd_f32(L.ptr(x), L.ptr(cache[1]), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, kind,
+        return L.check(lib.mi_conv_d32_fwd_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, kind,
                                                L.stream()), "mi_conv_d32_fwd_f32")
     _prof_run("fwd", 2.0 * n * d * h * wd * co * ci * ntap, call)
     return out
@@ -526,13 +557,6 @@ def _smallk_call(x, w, bias, relu, ntaps, out=None, owner=None):
     return out
 
 
-# Pre-cut weight images of the SimSiam 2-D encoder's 3 x 3 / stride-1 layers (conv_p2d.hip).  An engine that knows when the weights
-# change (SimSiamStepEngine: behind its SGD kernel) keeps them in ACTIVE_P2D = {(weight address, dgrad): image} for the duration of its
-# step and re-cuts them all in one or two launches; everywhere else the image lives on the parameter and is rebuilt when the
-# parameter's version (torch ops) or the weight epoch (raw-pointer writes) moved.
-ACTIVE_P2D = None
-
-
 def p2d_usable(x_shape, ci, co, k3, stride, p3, dil=None):
     """True when conv_p2d.hip takes this 2-D convolution (forward of x / data gradient onto x): (N, H, W, C) -> C channels, 3 x 3,
     stride 1, padding 1, (W, C) one of the SimSiam 2-D encoder's three at --bbox 36."""
@@ -549,44 +573,20 @@ def _stem3_ok(co):
     return 4 <= co <= 64 and co % 4 == 0 and 256 % (co // 4) == 0 and not os.environ.get("MI_NO_P2D")
 
 
-def p2d_prep(items):
-    """items: [(weight, dgrad flag, image tensor)] - all cut in one launch per 16 (mi_conv2d_p2d_prep) on the current stream."""
-    import ctypes
-    n = len(items)
-    if not n:
-        return
-    ws = (ctypes.c_void_p * n)(*[it[0].data_ptr() for it in items])
-    imgs = (ctypes.c_void_p * n)(*[it[2].data_ptr() for it in items])
-    dg = (ctypes.c_int * n)(*[int(bool(it[1])) for it in items])
-    ch = (ctypes.c_int * n)(*[int(it[0].shape[0]) for it in items])
-    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    L.check(L.lib().mi_conv2d_p2d_prep(cast(ws), cast(imgs), cast(dg), cast(ch), n, L.stream()), "mi_conv2d_p2d_prep")
-
-
 def _p2d_image(w, dgrad):
     dgrad = int(bool(dgrad))
-    if ACTIVE_P2D is not None and PROFILE is None:
-        img = ACTIVE_P2D.get((w.data_ptr(), dgrad))
+    if ACTIVE_IMAGES is not None and PROFILE is None:
+        img = ACTIVE_IMAGES.get_p2d(w, dgrad)
         if img is not None:
             return img
     if not _phys_ok(w):
         raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
-    key = (w.data_ptr(), w._version, WEIGHT_EPOCH)
-    cache = getattr(w, "_mi_p2d", None)
-    if cache is None:
-        cache = {}
-        try:
-            w._mi_p2d = cache
-        except AttributeError:
-            pass
-    ent = cache.get(dgrad)
-    if ent is None or ent[0] != key:
-        img = ent[1] if (ent is not None and ent[1].device == w.device) else torch.empty(int(L.lib().mi_conv2d_p2d_wimg_bytes(int(w.shape[0]))), dtype=torch.uint8,
-                                                         device=w.device)
-        p2d_prep([(w, dgrad, img)])
-        ent = (key, img)
-        cache[dgrad] = ent
-    return ent[1]
+    def cut(old):
+        img = old if (old is not None and old.device == w.device) else torch.empty(
+            int(L.lib().mi_conv2d_p2d_wimg_bytes(int(w.shape[0]))), dtype=torch.uint8, device=w.device)
+        _prep_images("mi_conv2d_p2d_prep", [(w, None, dgrad, img)])
+        return img
+    return _kept_image(w, ("_mi_p2d", "_mi_p2d_dgrad")[dgrad], w, (), cut)
 
 
 def _p2d_call(a, w, dgrad, res, mask, relu, tag):
@@ -1050,8 +1050,8 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
             slab = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)     # lives with the parameter
             if not getattr(param, "_mi_slabs_pinned", False):
                 param._mi_slabs = slab
-            # (pinned: a captured hipGraph writes and reads the old buffer on every replay - MocoStepEngine pins the slabs
-            # when it captures; an eager call that needs more space gets a buffer of its own and the graph's stays alive)
+            # (pinned: a captured hipGraph writes and reads the old buffer on every replay - the step engines pin the slabs
+            # when they capture; an eager call that needs more space gets a buffer of its own and the graph's stays alive)
         _f32c(x, "x"), _f32c(dy, "dy")
         job = _WgradJob(x, dy, tgt, slab, (n, d, h, wd, ci, co) + tuple(k3) + (stride,) + tuple(p3), param, flops)
         if DEFERRED_WGRADS is not None:
@@ -1294,6 +1294,17 @@ def conv_bn(conv, bn, x, relu=False, pool=False, out=None):
     return conv_bias_fwd(x, cache[1], cache[2], conv.k, conv.stride, conv.pad, relu)
 
 
+def _d32_up_image(up, ci, co):
+    """conv_d32.hip's image of the up-convolution's 1 x 1 product (4 co columns), kept on up.weight."""
+    wv = up.gemm_view()
+    lib = L.lib()
+    def cut(_):
+        img = torch.empty((4 * co // 64) * int(lib.mi_conv_d64_image_bytes(ci, 1)), dtype=torch.uint8, device=wv.device)
+        L.check(lib.mi_conv_d64_prep_co(L.ptr(wv), L.ptr(img), ci, 4 * co, 1, L.stream()), "mi_conv_d64_prep_co")
+        return img
+    return _kept_image(up.weight, "_mi_d32_up", wv, (ci, co, "up"), cut)
+
+
 def upconv_bn_relu_concat(up, bn, dec, enc, cat=None):
     """cat(relu(bn(up(dec))), enc) over the channel axis (unet.py:319-399).  At inference one 1 x 1 product + ONE pass that shuffles,
     applies the folded BatchNorm (the transposed convolution's bias included), the ReLU and writes the concatenation
@@ -1329,15 +1340,8 @@ def upconv_bn_relu_concat(up, bn, dec, enc, cat=None):
         # `enc` IS cat[..., co:] (the down-convolution block wrote it there: skip_into_concat_ok): only the first co channels are missing
         if (tuple(cat.shape) != (n, ho, wo, co + ce) or not cat.is_contiguous() or enc.data_ptr() != cat.data_ptr() + 4 * co):
             raise L.HipExtensionError("upconv_bn_relu_concat: `cat` is not the buffer `enc` is a channel slice of")
-        wv = up.gemm_view()
-        key = (wv.data_ptr(), up.weight._version, WEIGHT_EPOCH, ci, co, "up")
-        wc = getattr(up.weight, "_mi_d32_up", None)
-        if wc is None or wc[0] != key:
-            img = torch.empty((4 * co // 64) * int(lib.mi_conv_d64_image_bytes(ci, 1)), dtype=torch.uint8, device=dec.device)
-            L.check(lib.mi_conv_d64_prep_co(L.ptr(wv), L.ptr(img), ci, 4 * co, 1, L.stream()), "mi_conv_d64_prep_co")
-            wc = (key, img)
-            up.weight._mi_d32_up = wc
-        L.check(lib.mi_conv_d32_upconv_fwd_f32(L.ptr(dec), L.ptr(wc[1]), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(cat), n, h, w, ci, co,
+        wimg = _d32_up_image(up, ci, co)
+        L.check(lib.mi_conv_d32_upconv_fwd_f32(L.ptr(dec), L.ptr(wimg), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(cat), n, h, w, ci, co,
                                                ho, wo, co + ce, L.stream()), "mi_conv_d32_upconv_fwd_f32")
         return cat
     out = torch.empty((n, ho, wo, co + ce), dtype=torch.float32, device=dec.device)
@@ -1345,15 +1349,8 @@ def upconv_bn_relu_concat(up, bn, dec, enc, cat=None):
             and h % 8 == 0 and w % 16 == 0 and _phys_ok(up.gemm_view())):
         # the product, the pixel shuffle, the folded BatchNorm and the ReLU in ONE launch (conv_d32.hip, 1 x 1 form with the
         # up-convolution epilogue) straight into the concatenation; the encoder feature goes into the other channels
-        wv = up.gemm_view()
-        key = (wv.data_ptr(), up.weight._version, WEIGHT_EPOCH, ci, co, "up")
-        wc = getattr(up.weight, "_mi_d32_up", None)
-        if wc is None or wc[0] != key:
-            img = torch.empty((4 * co // 64) * int(lib.mi_conv_d64_image_bytes(ci, 1)), dtype=torch.uint8, device=dec.device)
-            L.check(lib.mi_conv_d64_prep_co(L.ptr(wv), L.ptr(img), ci, 4 * co, 1, L.stream()), "mi_conv_d64_prep_co")
-            wc = (key, img)
-            up.weight._mi_d32_up = wc
-        rc = lib.mi_conv_d32_upconv_fwd_f32(L.ptr(dec), L.ptr(wc[1]), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(out), n, h, w, ci, co,
+        wimg = _d32_up_image(up, ci, co)
+        rc = lib.mi_conv_d32_upconv_fwd_f32(L.ptr(dec), L.ptr(wimg), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(out), n, h, w, ci, co,
                                             ho, wo, co + ce, L.stream())
         if rc == 0:
             L.check(lib.mi_copy_channels_into(L.ptr(enc), ce, L.ptr(out), co + ce, co, n * ho * wo, L.stream()), "mi_copy_channels_into")

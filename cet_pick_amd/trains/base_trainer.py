@@ -162,9 +162,7 @@ class BaseTrainer(object):
         """One training step on a resident pair of view batches, as run_epoch's loop body performs it (the bench's step loop and
         the engine-equals-plain-sequence tests).  `eager`: keep a step engine out of its hipGraph for this call.  -> loss (device)."""
         if self.engine is not None:
-            if eager and hasattr(self.engine, "step_eager"):
-                return self.engine.step_eager(x1, x2)
-            return self.engine.step(x1, x2)
+            return self.engine.step_eager(x1, x2) if eager else self.engine.step(x1, x2)
         self.model_with_loss.train()
         _, loss, _ = self.model_with_loss({"input": x1, "input_aug": x2}, 0, "train")
         self.optimizer.zero_grad()

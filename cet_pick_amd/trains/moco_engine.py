@@ -1,33 +1,25 @@
 """One MoCo training step as the reference's hot loop performs it
 (trains/base_trainer.py:486-508 -> models/moco.py:101-146 -> trains/tomo_moco_trainer.py:73 ->
-optimizer.step), driven without per-iteration host syncs and replayed from a hipGraph - on one GPU and, with the RCCL
-backend, on N GPUs too (the collectives are captured with the kernels; CETPICK_DIST_GRAPH=0 keeps the N>1 step eager,
-and a capture that fails falls back to the eager step by itself).
+optimizer.step), driven without per-iteration host syncs and replayed from a hipGraph (trains/step_graph.py) - on one GPU and,
+with the RCCL backend, on N GPUs too.
 
 Data-parallel ranks (one process per GPU, torch.distributed backend "nccl" = RCCL) exchange per step:
 gradient arena all-reduce (40.4 MB fp32), MoCo key all-gather (B x 128), SyncBN per-channel sums.
 """
 import os
-import warnings
 
 import torch
 
 from .. import hipops as H
+from .step_graph import StepGraph
 
 
-def _dist():
-    import torch.distributed as dist
-    return dist if (dist.is_available() and dist.is_initialized()) else None
-
-
-class MocoStepEngine:
+class MocoStepEngine(StepGraph):
     def __init__(self, moco, lr, weight_decay=0.0, use_graph=False):
         self.moco = moco
-        self.lr = float(lr)
-        self.weight_decay = float(weight_decay)
         self.arena_q, self.arena_k = moco.flatten_parameters()
+        super().__init__(moco, [self.arena_q, self.arena_k], lr, weight_decay, use_graph)
         dev = self.arena_q.flat.device
-        self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
         self.logits = None
         self._one = torch.ones((), dtype=torch.float32, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
@@ -35,15 +27,6 @@ class MocoStepEngine:
         # running sum of the steps' losses since take_loss_sum(): accumulated by one launch INSIDE the step (a graph node) - run_epoch's
         # meters read it at print time instead of launching a mean and an add behind every step
         self.loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
-        d = _dist()
-        self.world = d.get_world_size() if d else 1
-        self.dist_on = H._distributed()
-        # an eager N>1 step is launch-bound on the host (3.5 ms against 2.4 ms on one GPU, before any collective); RCCL
-        # collectives can be captured into the graph, gloo's (host-side) cannot
-        graph_ok = (not self.dist_on) or (d.get_backend() == "nccl" and os.environ.get("CETPICK_DIST_GRAPH", "1") != "0")
-        self.use_graph = bool(use_graph) and graph_ok
-        self._graph = None
-        self._static_q = self._static_k = None
         self._xchg = None                # side stream of the gradient exchange (overlaps the backward pass)
         self.buckets_sent = []           # tags of the last step's exchanges, in issue order (tests / diagnostics)
         if self.dist_on:
@@ -56,7 +39,6 @@ class MocoStepEngine:
         if self.side_wgrads:
             moco.encoder_q.grad_marker = self._on_marker
         self._images = self._build_weight_images()
-        self._img_versions = None
 
     # ---- pre-cut weight images of the layer1 convolutions (conv_direct3.hip) ---------------------------------
     def _build_weight_images(self):
@@ -86,19 +68,6 @@ class MocoStepEngine:
                     imgs.add_s2(group, w, wds, True)
         self.moco.weight_images = imgs                 # MoCo re-cuts group "k" right behind its momentum update
         return imgs
-
-    def refresh_weight_images(self):
-        """Call after writing the encoders' weights from outside the step (checkpoint load, broadcast): the step itself
-        keeps the images current, and notices writes made through torch ops by their version counters."""
-        if self._images is not None:
-            self._images.refresh("q")
-            self._images.refresh("k")
-            self._img_versions = self._weight_versions()
-
-    def _weight_versions(self):
-        """Changes whenever a torch op wrote a cached weight OR either flat arena (dist.broadcast, arena.flat.copy_, a
-        checkpoint load): the engine's own SGD / EMA kernels go through the C-ABI, bump nothing, and refresh by themselves."""
-        return self._images.versions() + self.arena_q.flat._version + self.arena_k.flat._version
 
     # ---- data parallel: bucketed gradient all-reduce overlapped with the backward pass ---------------------
     def _setup_buckets(self):
@@ -137,20 +106,10 @@ class MocoStepEngine:
                 H.dist_all_reduce(self.arena_q.flat_grad[a:b])
             self.buckets_sent.append(tag)
 
-    # CETPICK_L2_WGRAD_LATE=1 (measured, not faster: r05_experiments.txt item 9): layer2's weight gradients wait for layer1's marker and
-    # run next to the stem chain instead of next to layer1's data-gradient chain; the layer2 bucket of the gradient exchange then goes
-    # out with layer1's.
-    l2_late = os.environ.get("CETPICK_L2_WGRAD_LATE", "0") != "0"
-
     def _on_marker(self, tag):
-        late = self.l2_late and self.side_wgrads
-        if self.side_wgrads and tag in ("layer3", "layer2", "layer1") and not (late and tag == "layer2"):
+        if self.side_wgrads and tag in ("layer3", "layer2", "layer1"):
             self._issue_side_wgrads(enqueue=(tag == "layer3"))
         if self.dist_on:
-            if late and tag == "layer2":
-                return
-            if late and tag == "layer1":
-                self._reduce_bucket("layer2")
             self._reduce_bucket(tag)
 
     def _issue_side_wgrads(self, enqueue=False):
@@ -183,26 +142,16 @@ class MocoStepEngine:
         del items[:]
         self._wside_used = True
 
-    def broadcast_state(self, src=0):
-        """Identical replicas before the first step (what DistributedDataParallel does at construction): the two flat
-        parameter arenas (the parameters themselves are kernel-layout views, which RCCL refuses as non-contiguous), the
-        buffers and the queue."""
-        d = _dist()
-        if d is None:
-            return
-        d.broadcast(self.arena_q.flat, src)
-        d.broadcast(self.arena_k.flat, src)
-        for b in self.moco.buffers():
-            d.broadcast(b, src)
-        self.refresh_weight_images()
+    # ---- the step ------------------------------------------------------------------------------------------------
+    def step(self, im_q, im_k):
+        """Returns the loss as a 0-d device tensor (no host sync); graph mode: StepGraph._run."""
+        return self._run({"q": im_q, "k": im_k})
 
-    def set_lr(self, lr):
-        """utils/utils.py:58-70 `adjust_learning_rate` target: the schedule reaches a captured graph
-        through a device scalar."""
-        self.lr = float(lr)
-        self.lr_dev.fill_(self.lr)
+    def step_eager(self, im_q, im_k):
+        return self._run({"q": im_q, "k": im_k}, eager=True)
 
-    def _step_eager(self, im_q, im_k):
+    def _step_eager(self, inputs):
+        im_q, im_k = inputs["q"], inputs["k"]
         moco = self.moco
         self.buckets_sent = []
         self.arena_q.zero_grad()
@@ -253,133 +202,3 @@ class MocoStepEngine:
         v = float(self.loss_sum.item())
         self.loss_sum.zero_()
         return v
-
-    @staticmethod
-    def _drain_watchdog():
-        """Data parallel, before a capture: wait until the process group's watchdog thread holds no Work of the eager steps.
-        The watchdog polls its list every 100 ms (hipEventQuery on each Work's end event) and drops the Works it finds
-        complete.  A Work of the eager warm-up steps that is still on that list when the capture starts gets polled DURING
-        the capture - and ProcessGroupNCCL's internal communication stream, on which that end event was recorded, is by then
-        part of the capture: ROCm answers hipErrorCapturedEvent ("operation not permitted on an event last recorded in a
-        capturing stream") for an event whose stream is capturing NOW, the watchdog rethrows and the process aborts
-        (profiles/r04_watchdog_abort.txt: 1 run in ~10; `thread_local` capture mode cured the other form of this race, the
-        query of an unrelated event under `global` mode).
-        The drain is a synchronisation, not a timer: the caller has synchronised the device (every Work is complete), and
-        `ProcessGroup._wait_for_pending_works()` (c10d: ProcessGroupNCCL::waitForPendingWorks) returns once it has seen, under
-        the watchdog's own two mutexes, BOTH the watchdog's work list and its completed-work list empty - it re-checks every
-        watchdog poll period until then.  Nothing is issued between that return and the capture, so the list is still empty
-        when the capture begins, and every collective of the captured step is synchronous (no Work is registered under
-        capture).  Paid once per capture, never per step.  Only a torch build without the binding falls back to waiting
-        three poll periods (CETPICK_WATCHDOG_DRAIN_S, default 0.3 s) - and says so."""
-        d = _dist()
-        pg = d.distributed_c10d._get_default_group()
-        wait = getattr(pg, "_wait_for_pending_works", None)
-        if wait is not None:
-            wait()
-            return
-        import os
-        import time
-        warnings.warn("this torch has no ProcessGroup._wait_for_pending_works: draining the watchdog by a timed wait")
-        time.sleep(float(os.environ.get("CETPICK_WATCHDOG_DRAIN_S", "0.3")))
-
-    def _capture(self, im_q, im_k):
-        """Record one step into a hipGraph.  Returns the graph, or None when the data-parallel ranks agreed to stay
-        eager.  With collectives in the step every rank must take the same decision: a rank that replays a graph
-        and a rank that launches eagerly no longer issue their collectives in one order."""
-        self._static_q = im_q.clone()
-        self._static_k = im_k.clone()
-        torch.cuda.synchronize()
-        if self.dist_on:
-            self._drain_watchdog()
-        graph = torch.cuda.CUDAGraph(keep_graph=True)      # the hipGraph_t stays queryable (node_counts)
-        err = None
-        try:
-            # Data parallel: the process group's watchdog THREAD polls (hipEventQuery) Works at its own pace.  Two races, two
-            # cures: (1) under the default "global" capture mode ANY such call from another thread while this one is
-            # capturing terminates the process (hipErrorStreamCaptureUnsupported) - "thread_local" restricts only the capturing
-            # thread; (2) a query of an event whose own stream has joined the capture fails in either mode
-            # (hipErrorCapturedEvent) - _drain_watchdog() above emptied the watchdog's list, and nothing captured adds to it.
-            mode = "thread_local" if self.dist_on else "global"
-            # (the capture runs on a stream of its own: the kept-clean workspaces the eager steps made for THEIR stream get a twin for it
-            # now, or their zero-fill would be recorded and replay with every step)
-            cap = torch.cuda.Stream(device=self.lr_dev.device)
-            if os.environ.get("CETPICK_PRIME_WS", "1") != "0":            # (A/B: 0 leaves the fill in the graph)
-                H.L.prime_workspaces_for_stream(torch.cuda.current_stream(), cap)
-            with torch.cuda.graph(graph, stream=cap, capture_error_mode=mode):       # records, does not execute
-                self._step_eager(self._static_q, self._static_k)
-        except Exception as e:                        # e.g. a collective that cannot be captured
-            if not self.dist_on:
-                raise
-            err = e
-        # the graph bakes in the addresses of the weight-gradient slab buffers: they must never be reallocated from now on
-        for prm in self.arena_q.params:
-            if getattr(prm, "_mi_slabs", None) is not None:
-                prm._mi_slabs_pinned = True
-        if self.dist_on:
-            # the outcome is agreed on eagerly (outside any capture); a stream or communicator left in an error
-            # state by the aborted capture surfaces here instead of being swallowed
-            torch.cuda.synchronize()
-            ok = torch.tensor([0 if err is not None else 1], dtype=torch.int32, device=self.lr_dev.device)
-            _dist().all_reduce(ok, op=_dist().ReduceOp.MIN)
-            if int(ok.item()) == 0:
-                warnings.warn("hipGraph capture of the data-parallel step failed on %s (%s); every rank runs it eagerly"
-                              % ("this rank" if err is not None else "another rank", err))
-                del graph
-                self.use_graph = False
-                self._static_q = self._static_k = None
-                return None
-        return graph
-
-    def step(self, im_q, im_k):
-        """Returns the loss as a 0-d device tensor (no host sync).
-
-        Graph mode: the first two calls run eagerly (they size every workspace), the third call
-        captures the step into a hipGraph and from then on each call is one graph replay.  A batch whose
-        shape differs from the captured one (a short last batch) runs eagerly."""
-        if self._images is not None and self._weight_versions() != self._img_versions:
-            self.refresh_weight_images()               # first step, or the weights / arenas were written through torch ops
-        if not self.use_graph:
-            return self._step_eager(im_q, im_k)
-        if self._graph is None:
-            self._calls = getattr(self, "_calls", 0) + 1
-            if self._calls <= 2:
-                return self._step_eager(im_q, im_k)
-            self._graph = self._capture(im_q, im_k)
-            if self._graph is None:
-                return self._step_eager(im_q, im_k)
-        if im_q.shape != self._static_q.shape or im_k.shape != self._static_k.shape:
-            if self.dist_on:
-                raise ValueError("data-parallel graph step: batch %s differs from the captured %s (use drop_last)"
-                                 % (tuple(im_q.shape), tuple(self._static_q.shape)))
-            return self._step_eager(im_q, im_k)
-        if os.environ.get("CETPICK_COPY_PAIR", "1") != "0":
-            H.copy_pair_(self._static_q, im_q, self._static_k, im_k)      # (one launch for both views)
-        else:
-            self._static_q.copy_(im_q)
-            self._static_k.copy_(im_k)
-        H._bump_weight_epoch()                          # the replayed SGD / momentum kernels write the arenas (no Python runs)
-        self._graph.replay()
-        return self.loss
-
-    def node_counts(self):
-        """{'kernel', 'memcpy', 'memset', 'other'} nodes of the captured step (None while the step runs eagerly)."""
-        if self._graph is None:
-            return None
-        import ctypes
-        from .. import _lib as L
-        counts = (ctypes.c_int * 4)()
-        L.check(L.lib().mi_graph_node_counts(ctypes.c_void_p(self._graph.raw_cuda_graph()), ctypes.cast(counts, ctypes.c_void_p)),
-                "mi_graph_node_counts")
-        return dict(zip(("kernel", "memcpy", "memset", "other"), [int(c) for c in counts]))
-
-    def close(self):
-        """Release everything that refers to the process group's communicator BEFORE the group is destroyed: the
-        captured hipGraph holds the RCCL kernels of its collectives, so it has to go first; then the device is drained.
-        Call before dist.destroy_process_group()."""
-        if self._graph is not None:
-            torch.cuda.synchronize()
-            self._graph.reset()
-            self._graph = None
-        self._static_q = self._static_k = None
-        self._calls = 0
-        torch.cuda.synchronize()

@@ -116,3 +116,22 @@ def test_head_z_slabs_forced_slab():
     assert head_z_slabs(1, 29, 4 * 32 * 32 * 32, slab=8) == [(0, 0, 8, 0, 11), (0, 8, 8, 5, 19), (0, 16, 8, 13, 27),
                                                             (0, 24, 5, 21, 29)]
     assert [t[:3] for t in head_z_slabs(2, 10, 4 * 32 * 32 * 32, slab=8)] == [(0, 0, 8), (0, 8, 2), (1, 0, 8), (1, 8, 2)]
+
+
+def test_plain_arena_drops_second_gradient_views():
+    """A plain ParamArena on a module that a two-arena owner (the SimSiam step engine) flattened before: the second gradient of a
+    parameter accumulates into .grad, where the stock optimizer reads it - not into the orphaned second arena."""
+    from cet_pick_amd import hipops as H
+    m = torch.nn.Linear(4, 3)
+    H.ParamArena(m, second_grad_arena=True)
+    arena = H.ParamArena(m)
+    p = m.weight
+    arena.zero_grad()
+    for contribution in (1.0, 2.0):
+        tgt, acc = H._grad_target(p)
+        if acc:
+            tgt.add_(torch.full_like(p, contribution))
+        else:
+            tgt.copy_(torch.full_like(p, contribution))
+    assert torch.equal(p.grad, torch.full_like(p, 3.0))
+    assert p.grad.data_ptr() == p._mi_grad_view.data_ptr()
