@@ -38,6 +38,8 @@ SIGNATURES = {
     "mi_crop_normalize": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mi_crop_normalize_table": (_I, [_P, _P, _P, _P, _P, _c.c_int64, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mi_u8_roundtrip_normalize": (_I, [_P, _P, _Z, _F, _F, _P]),
+    "mi_aug2d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _I] + [_F] * 7 + [_P, _P]),
+    "mi_aug2d_apply": (_I, [_P, _c.c_int64, _I, _P, _P, _c.c_int64, _I, _F, _F, _P, _P]),
     "mi_tilt_patches": (_I, [_P, _I, _P, _P, _c.c_int64, _I, _I, _D, _D, _P, _P, _P]),
     "mi_semi_labels": (_I, [_P, _I, _I, _I, _P, _c.c_int64, _P, _I, _I, _P]),
     "mi_semi_pairs": (_I, [_P, _P, _I, _P, _P, _c.c_int64, _I, _I, _P, _P, _P, _P]),

@@ -19,8 +19,9 @@ from . import subvols as S
 class SyntheticSimSiamDataset:
     """One or more synthetic tomograms -> DoG picks (`get_potential_coords_pyramid`, sigma = --dog) -> (3, bbox, bbox)
     crops summed over z and min-max'ed (`extract_subvols`) -> dataset mean / std (:238-239).  Iterating yields
-    batches of two views: the normalised crop and its mirror image (the random torchvision augmentations of the
-    reference's sample class are out of scope)."""
+    batches of two views: the normalised crop and its mirror image, or - `--augment reference`, train split - the
+    reference's random views: the strong chain on the crop and the weak chain on the crop of one of four neighbouring
+    centres, drawn and applied on the device (datasets/augment.py)."""
     num_classes = 256
     default_resolution = [24, 24]
 
@@ -54,6 +55,37 @@ class SyntheticSimSiamDataset:
         self.mean_subvols3d, self.std_subvols3d = S.subvol_mean_std(self.sub_vols_3d)
         self.normed = (self.sub_vols_3d - self.mean_subvols3d) / self.std_subvols3d
         self.num_samples = self.sub_vols_3d.shape[0]
+        self._setup_views()
+
+    def _wants_reference_views(self):
+        return getattr(self.opt, "augment", "mirror") == "reference" and self.split == "train"
+
+    def _neighbour_crops(self, rec, c):
+        """The crops of the four neighbouring centres of every pick `c` (x, y, z) of tomogram `rec` (:211-215): (4, n, 1, bbox, bbox)."""
+        d, h, w = rec.shape
+        c = np.asarray(c, dtype=np.int64)
+        up, down = np.clip(c[:, 2] + 1, 1, d - 2), np.clip(c[:, 2] - 1, 1, d - 2)
+        cents = [np.stack([c[:, 0], c[:, 1], up], 1), np.stack([c[:, 0], c[:, 1], down], 1),
+                 np.stack([c[:, 0] - 1, c[:, 1], down], 1), np.stack([c[:, 0], c[:, 1] + 1, down], 1)]
+        hx, hy = self.size[2] // 2, self.size[1] // 2
+        # the picks' border rule leaves room for the shifted windows (the crop kernel would clamp, not fault; the reference would cut a short crop)
+        assert (c[:, 0] - 1 - hx).min() >= 0 and (c[:, 0] + hx).max() <= w and (c[:, 1] - hy).min() >= 0 and \
+            (c[:, 1] + 1 + hy).max() <= h, "--augment reference: a neighbouring crop leaves the tomogram (bbox %d)" % self.size[1]
+        return torch.stack([S.extract_subvols(rec, q, self.size) for q in cents], 0)
+
+    def _setup_views(self):
+        """--augment reference, train split: the four neighbour banks and the device-side augmenter (datasets/augment.py)."""
+        self.augmenter = None
+        if not self._wants_reference_views():
+            return
+        from .augment import ViewAugmenter
+        banks, first = [], 0
+        for name in self.names:
+            n = self.names_all.count(name)
+            if n:
+                banks.append(self._neighbour_crops(self.tomos[name], np.stack(self.coords[first:first + n])))
+                first += n
+        self.augmenter = ViewAugmenter(self.sub_vols_3d, torch.cat(banks, 1), self.mean_subvols3d, self.std_subvols3d, self.seed)
 
     def set_epoch(self, epoch):
         self.epoch = epoch
@@ -64,6 +96,14 @@ class SyntheticSimSiamDataset:
     def __iter__(self):
         order = np.random.default_rng(self.seed + 1000 * self.epoch).permutation(self.num_samples)
         order = order[self.rank::self.world]
+        if self.augmenter is not None:
+            # view 1 = strong(crop), view 2 = weak(crop of a random neighbouring centre) (particle_pre_3d_vol.py:70-85); one upload
+            # of the epoch's order, then four launches per batch that index it
+            ids = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int64)).to(self.normed.device)
+            for i in range(len(self)):
+                x, x_aug = self.augmenter.views(ids[i * self.batch_size:(i + 1) * self.batch_size], self.epoch)
+                yield {"input": x, "input_aug": x_aug}
+            return
         for i in range(len(self)):
             idx = torch.as_tensor(order[i * self.batch_size:(i + 1) * self.batch_size], device=self.normed.device)
             x = self.normed[idx]

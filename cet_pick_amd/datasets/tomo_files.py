@@ -8,8 +8,10 @@ datasets/particle_pre_3d_vol.py:70-85 for the batch dictionary) through the devi
 
 Semantics kept from the reference: the list format, `--order` / `--compress` / `--gauss`, the picker and its sigmas, the
 crop geometry and the border rule of `load_data` (:196), the dataset mean / std (:238-239), the attributes
-simsiam_test_hm_3d.py reads.  Out of scope: the random torchvision / torchio augmentations - the second
-view is the mirrored crop (2-D) / the crop shifted by <= 1 voxel and mirrored (3-D), as in the synthetic datasets.
+simsiam_test_hm_3d.py reads.  The second view is the mirrored crop (2-D) / the crop shifted by <= 1 voxel and mirrored (3-D), as
+in the synthetic datasets; with `--augment reference` the 2-D train split serves the reference's random views instead (the
+strong chain on the crop, the weak chain on a neighbouring centre's crop: datasets/augment.py, on the device).  The torchio
+augmentations of the 3-D loader stay out of scope.
 """
 import os
 
@@ -129,6 +131,7 @@ class TomoFileSimSiamDataset(SyntheticSimSiamDataset):
         self.mean_subvols3d, self.std_subvols3d = S.subvol_mean_std(self.sub_vols_3d)
         self.normed = (self.sub_vols_3d - self.mean_subvols3d) / self.std_subvols3d
         self.num_samples = self.sub_vols_3d.shape[0]
+        self._setup_views()
         print("Loaded {} {} samples".format(split, self.num_samples))
 
 

@@ -68,6 +68,9 @@ _FLAGS = [
     # MI355X build only (not a reference flag): replay the MoCo / SimSiam step from a hipGraph (default) or launch it eagerly
     ("--hipgraph", dict(dest="hipgraph", action="store_true", default=None)),
     ("--no_hipgraph", dict(dest="hipgraph", action="store_false")),
+    # MI355X build only: the two views of the simsiam3d train split - the crop and its mirror image (default), or the reference's
+    # random chains on the crop and on a neighbouring centre's crop, drawn and applied on the device (datasets/augment.py)
+    ("--augment", dict(default="mirror", choices=["mirror", "reference"])),
 ]
 
 # task -> heads (opts.py:285-304); lambdas see the parsed opt

@@ -165,6 +165,38 @@ int mi_crop_normalize_table(const mi_vol_desc* vols, const int32_t* owner, const
  * Normalize; mean / std = the dataset statistics of tomo_pre_proj_angle_select_new3d_vol.py:238-239).  y may alias x. */
 int mi_u8_roundtrip_normalize(const float* x, float* y, size_t n, float mean, float std, mi_stream_t stream);
 
+/* Random view augmentation of the `simsiam3d` dataset (datasets/tomo_pre_proj_angle_select_new3d_vol.py:49-89: ToPILImage,
+ * RandomHorizontalFlip, RandomVerticalFlip, ColorJitter, RandomResizedCrop(aspect 1), ToTensor, FixedRotation
+ * (utils/image.py:195-201), Normalize; datasets/particle_pre_3d_vol.py:70-85: the second view is the crop of one of four
+ * neighbouring centres).
+ *
+ * mi_aug2d_params draws table[t] = the parameter record of sample sample_ids[t] for `view` (0 strong, 1 weak; < 256):
+ * 8 x 32 bit
+ *     word 0  bit 0 hflip, bit 1 vflip, bit 2 bright_first (brightness acts before contrast); other bits reserved, 0
+ *     word 1  brightness factor (float32 bits) ~ U(bright_lo, bright_hi)
+ *     word 2  contrast factor   (float32 bits) ~ U(contrast_lo, contrast_hi)
+ *     word 3  s = round(bbox * sqrt(u)), u ~ U(area_lo, area_hi): side of the square crop window
+ *     word 4, 5  i, j: top row and left column of the window, uniform integers in [0, bbox - s]
+ *     word 6  k in 0..3: quarter turns, orientation of torch.rot90(img, k, dims=[1, 2])
+ *     word 7  neighbour in 0..3: which neighbouring centre's crop the view is made of
+ * hflip, vflip ~ Bernoulli(flip_p); bright_first ~ Bernoulli(0.5); k, neighbour uniform.  The generator is Philox-4x32-10
+ * with counter (sample id, epoch, view) and key seed: a record is a pure function of (seed, epoch, sample id, view) and of
+ * the ranges - no state, no dependence on the position in sample_ids or on n.
+ *
+ * mi_aug2d_apply: out[t] (bbox x bbox; out is (n, 1, bbox, bbox)) = the chain on crop sample_ids[t] of `bank`
+ * ((n_banks, n_samples, bbox, bbox) fp32 in [0, 1]; n_banks > 1: bank table[t].neighbour, clamped) with table[t]:
+ *     g = floor(255 x); flips; brightness / contrast in the drawn order, each the 8-bit blend (uint8)(d + f (g - d)) in
+ *     single precision, clipped to [0, 255] (brightness: d = 0; contrast: d = int(mean grey level of the current image +
+ *     0.5)); window [i : i + s, j : j + s] resized to bbox x bbox, bilinear with half-pixel centres and taps clamped to
+ *     the window, rounded to a grey level; / 255; rot90(k); (x - mean) / std.
+ * A record's s, i, j are clamped into the crop; a sample id outside [0, n_samples) gives a NaN image.  Both entries take
+ * bbox in 8..128 (MI_E_UNSUPPORTED outside); apply runs one workgroup per sample and needs the table 16-byte aligned. */
+int mi_aug2d_params(const int64_t* sample_ids, int64_t n, uint64_t seed, int epoch, int view, int bbox, float flip_p,
+                    float bright_lo, float bright_hi, float contrast_lo, float contrast_hi, float area_lo, float area_hi,
+                    int32_t* table, mi_stream_t stream);
+int mi_aug2d_apply(const float* bank, int64_t n_samples, int n_banks, const int64_t* sample_ids, const int32_t* table,
+                   int64_t n, int bbox, float mean, float std, float* out, mi_stream_t stream);
+
 /* Tilt-series patches of the 2d3d exploration mode (datasets/tomo_pre_proj_angle_select_new2d3d.py:91-133
  * `convert_tomo_to_tilt` + `extract_patches`), one per centre.  Centre i = (x, y, z_full) of stack owner[i]
  * (owner == NULL: stack 0).  For every tilt t of that stack, in order:
