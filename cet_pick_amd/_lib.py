@@ -170,6 +170,13 @@ SIGNATURES = {
     "mi_sgd_step2": (_I, [_P, _P, _P, _P, _F, _F, _F, _L, _P]),
     "mi_scalar_accumulate": (_I, [_P, _P, _P, _P, _P, _P]),
     "mi_queue_enqueue": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    # k-means over the exploration embeddings (csrc/kmeans.hip)
+    "mi_kmeans_image_bytes": (_Z, [_I, _I]),
+    "mi_kmeans_workspace_bytes": (_Z, [_L, _I, _I]),
+    "mi_kmeans_prep": (_I, [_P, _I, _I, _P, _P]),
+    "mi_kmeans_xnorm": (_I, [_P, _L, _I, _P, _P]),
+    "mi_kmeans_assign": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _Z, _P]),
+    "mi_kmeans_update": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

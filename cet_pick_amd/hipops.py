@@ -2574,3 +2574,77 @@ class HipZHead(nn.Module):
     def forward(self, x):
         return _ZHeadFn.apply(_f32c(x, "x"), self.weight, self)
 
+
+
+# ---- k-means over the exploration embeddings (csrc/kmeans.hip) -----------------------------------------------------------
+
+def _km_x(x, name="x"):
+    x = L.require_cuda(x, name)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise L.HipExtensionError("%s must be a contiguous (N, d) tensor, got %s" % (name, tuple(x.shape)))
+    return x
+
+
+def kmeans_workspace(n, d, k, device):
+    nbytes = L.lib().mi_kmeans_workspace_bytes(n, d, k)
+    if nbytes == 0:
+        L.check(-3, "mi_kmeans_workspace_bytes(n=%d, d=%d, k=%d)" % (n, d, k))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def kmeans_prep(centroids, image=None):
+    """The centroids' operand image for kmeans_assign (once per iteration)."""
+    c = _km_x(centroids, "centroids")
+    k, d = c.shape
+    nbytes = L.lib().mi_kmeans_image_bytes(d, k)
+    if nbytes == 0:
+        L.check(-3, "mi_kmeans_image_bytes(d=%d, k=%d)" % (d, k))
+    if image is None:
+        image = torch.empty(nbytes, dtype=torch.uint8, device=c.device)
+    L.check(L.lib().mi_kmeans_prep(L.ptr(c), d, k, L.ptr(image), L.stream()), "mi_kmeans_prep")
+    return image
+
+
+def kmeans_xnorm(x, out=None):
+    x = _km_x(x)
+    if out is None:
+        out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    L.check(L.lib().mi_kmeans_xnorm(L.ptr(x), x.shape[0], x.shape[1], L.ptr(out), L.stream()), "mi_kmeans_xnorm")
+    return out
+
+
+def kmeans_assign(x, xnorm, image, k, labels=None, dist=None, ws=None):
+    """labels (N,) int32 = nearest centroid (lowest index on ties), dist (N,) fp32 = squared distance to it."""
+    x = _km_x(x)
+    n, d = x.shape
+    L.require_cuda(xnorm, "xnorm")
+    L.require_cuda(image, "image", torch.uint8)
+    if ws is None:
+        ws = kmeans_workspace(n, d, k, x.device)
+    if labels is None:
+        labels = torch.empty(n, dtype=torch.int32, device=x.device)
+    if dist is None:
+        dist = torch.empty(n, dtype=torch.float32, device=x.device)
+    L.check(L.lib().mi_kmeans_assign(L.ptr(x), L.ptr(xnorm), L.ptr(image), n, d, k, L.ptr(labels), L.ptr(dist), L.ptr(ws),
+                                     ws.numel(), L.stream()), "mi_kmeans_assign")
+    return labels, dist
+
+
+def kmeans_update(x, labels, centroids, counts=None, obj=None, nsplit=None, ws=None):
+    """centroids (k, d), in place: the mean of the rows of each label, then the empty-cluster rule; counts (k,) int32.
+    obj (1,) fp32 / nsplit (1,) int32: device slots for the objective of the preceding kmeans_assign on `ws` and the running
+    number of empty clusters served."""
+    x = _km_x(x)
+    c = _km_x(centroids, "centroids")
+    n, d = x.shape
+    k = c.shape[0]
+    if c.shape[1] != d:
+        raise L.HipExtensionError("centroids are %s, x is %s" % (tuple(c.shape), tuple(x.shape)))
+    L.require_cuda(labels, "labels", torch.int32)
+    if ws is None:
+        ws = kmeans_workspace(n, d, k, x.device)
+    if counts is None:
+        counts = torch.empty(k, dtype=torch.int32, device=x.device)
+    L.check(L.lib().mi_kmeans_update(L.ptr(x), L.ptr(labels), n, d, k, L.ptr(c), L.ptr(counts), L.ptr(obj), L.ptr(nsplit),
+                                     L.ptr(ws), ws.numel(), L.stream()), "mi_kmeans_update")
+    return counts

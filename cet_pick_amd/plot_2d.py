@@ -1,0 +1,104 @@
+"""Cluster the exploration embeddings and write the per-pick class table (the reference's plot_2d.py without its plots):
+
+    python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
+                                   [--seed 1234] [--gpus 0] [--host 7000]
+
+`pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
+reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
+reference's arguments; --n_cluster 0 keeps the k-means assignment as the class), and every pick gets the class of its centroid.
+
+    OUT/kmeans_labels.npz                 centroids (k, d) f32, assign (N,) i32, dist (N,) f32, label (N,) i32, obj (niter,) f32,
+                                          name, coords: numpy only, always written
+    OUT/interactive_info_parquet.gzip     the reference's table (name, coord, embeddings, label, image) where pandas with a
+                                          parquet engine imports
+
+The UMAP / t-SNE plots, the PNG thumbnails and all_colors.npy are not made here.
+"""
+import argparse
+import os
+
+import numpy as np
+
+
+def add_arguments(parser):
+    parser.add_argument("--input", required=True, help="all_output_info.npz of the exploration inference (pred, name, coords)")
+    parser.add_argument("--path", required=True, help="output directory")
+    parser.add_argument("--n_cluster", type=int, default=0, help="classes after merging the centroids; 0 (or >= k): no merge")
+    parser.add_argument("--k", type=int, default=256, help="k-means centroids (the reference: 256)")
+    parser.add_argument("--niter", type=int, default=300, help="k-means iterations (the reference: 300)")
+    parser.add_argument("--seed", type=int, default=1234, help="seed of the initial centroids (the reference passes 1234 to faiss)")
+    parser.add_argument("--host", type=int, default=7000, help="port in the image URLs of the parquet table")
+    parser.add_argument("--gpus", default="0", help="GPU index; -1 (CPU) is refused")
+    # accepted for the reference's command lines; they only steer its plots
+    parser.add_argument("--num_neighbor", type=int, default=None)
+    parser.add_argument("--mode", default="umap")
+    parser.add_argument("--min_dist_umap", type=float, default=0.5)
+    parser.add_argument("--min_dist_vis", type=float, default=None)
+    parser.add_argument("--save_out_img", type=int, default=1)
+    return parser
+
+
+def merge_centroids(centroids, n_cluster):
+    """The reference's host step on the k centroids: class of every centroid, (k,) int."""
+    try:
+        from sklearn.cluster import SpectralClustering
+    except ImportError as e:
+        raise RuntimeError("--n_cluster %d merges the centroids with sklearn.cluster.SpectralClustering, and sklearn does not "
+                           "import (%s); use --n_cluster 0 to keep the k-means assignment as the class" % (n_cluster, e)) from None
+    sc = SpectralClustering(n_clusters=n_cluster, assign_labels="discretize", random_state=0)
+    sc.fit(centroids)
+    return np.asarray(sc.labels_)
+
+
+def write_parquet(path, names, coords, projs, labels, host):
+    """The reference's table; False (one log line) where pandas or a parquet engine does not import."""
+    try:
+        import pandas as pd
+        try:
+            import pyarrow  # noqa: F401
+        except ImportError:
+            import fastparquet  # noqa: F401
+    except ImportError as e:
+        print("[cet_pick_amd] %s left out: pandas with a parquet engine does not import (%s)" % (path, e))
+        return False
+    rela = "http://localhost:{}/imgs/".format(host)
+    table = {"name": list(names), "coord": [[str(j) for j in list(c)] for c in coords], "embeddings": [list(p) for p in projs],
+             "label": list(labels), "image": [os.path.join(rela, str(i) + ".png") for i in range(len(names))]}
+    pd.DataFrame.from_dict(table).to_parquet(path, compression="gzip")
+    return True
+
+
+def main(args):
+    gpu = int(str(args.gpus).split(",")[0])
+    if gpu < 0:
+        raise RuntimeError("the MI355X path has no CPU mode (--gpus -1)")
+    import torch
+    from .utils.kmeans import Kmeans
+    data = np.load(args.input)
+    projs = np.ascontiguousarray(data["pred"], dtype=np.float32)
+    projs = projs.reshape(projs.shape[0], -1)
+    names, coords = data["name"], data["coords"]
+    print("[cet_pick_amd] plot_2d: the 2-D plots, thumbnails and colour map are not made here (--num_neighbor, --mode, "
+          "--min_dist_umap, --min_dist_vis, --save_out_img are ignored)")
+    os.makedirs(args.path, exist_ok=True)
+    km = Kmeans(projs.shape[1], args.k, niter=args.niter, seed=args.seed, device=torch.device("cuda", gpu))
+    with torch.cuda.device(gpu):
+        km.train(projs)
+        D, I = km.assign(projs)
+    assign = I[:, 0].astype(np.int32)
+    centroids = km.centroids
+    if 0 < args.n_cluster < args.k:
+        y = merge_centroids(centroids, args.n_cluster)
+        print("Actual number of clusters is:", len(set(y.tolist())))
+        label = y[assign].astype(np.int32)
+    else:
+        label = assign.copy()
+    np.savez(os.path.join(args.path, "kmeans_labels.npz"), centroids=centroids, assign=assign, dist=D[:, 0].astype(np.float32),
+             label=label, obj=km.obj.astype(np.float32), name=names, coords=coords)
+    write_parquet(os.path.join(args.path, "interactive_info_parquet.gzip"), names, coords, projs, label, args.host)
+    print("[cet_pick_amd] plot_2d: %d picks, %d centroids, %d classes, objective %.6g -> %s"
+          % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
+
+
+if __name__ == "__main__":
+    main(add_arguments(argparse.ArgumentParser("cluster exploration embeddings into classes")).parse_args())

@@ -741,6 +741,32 @@ int mi_ucl_rowsums_bwd_ranged(const float* feat, const uint8_t* cls, int n2, int
                               const float* g_all, const float* g_pos, const float* g_other, const float* g_pair, float* dfeat,
                               float* range, mi_stream_t stream);
 
+/* k-means over embeddings (reference plot_2d.py: faiss.Kmeans(d, 256, niter=300)), DESIGN.md 4.9.  x (n, d) fp32 rows,
+ * centroids (k, d) fp32, 1 <= d <= 512, 2 <= k <= 1024, k <= n < 2^31 (MI_E_UNSUPPORTED outside; the size entries return 0).
+ * Rows are addressed with 64-bit offsets: n x d may exceed 2 GiB.  One arithmetic: bf16x3 on the matrix cores
+ * (MI_CONV_ARITH is not consulted).
+ *   mi_kmeans_prep    image (mi_kmeans_image_bytes, 16-byte aligned) = the centroids' bf16x3 cut in MFMA operand order + |c_j|^2
+ *   mi_kmeans_xnorm   xnorm[i] = |x_i|^2
+ *   mi_kmeans_assign  labels[i] = argmin_j |x_i|^2 + (|c_j|^2 - 2 x_i.c_j), the LOWEST j on ties; dist[i] = that minimum,
+ *                     clamped at 0.  Leaves per-workgroup sums of dist in ws for the mi_kmeans_update that follows.
+ *   mi_kmeans_update  counts[j] and centroids[j] = mean of the rows with labels[i] == j (labels outside [0, k) are left out),
+ *                     deterministic: stable counting sort of the indices, sums of 64 sorted positions in position order, those
+ *                     in segment order in fp64.  Then, on the device, empty clusters in ascending index: the donor is the
+ *                     cluster with the most points at that moment (lowest index on ties); the empty cluster takes the donor's
+ *                     centroid with component m times 1 + 1/1024 (m even) or 1 - 1/1024 (m odd), the donor the opposite; of the
+ *                     donor's count n the empty cluster takes n / 2, the donor keeps n - n / 2 (counts[] holds the split
+ *                     values).  obj (may be NULL): obj[0] = sum of dist of the mi_kmeans_assign that last wrote ws (same n, d,
+ *                     k).  nsplit (may be NULL): nsplit[0] += number of empty clusters served.
+ * ws: mi_kmeans_workspace_bytes(n, d, k), 16-byte aligned, shared by assign and update. */
+size_t mi_kmeans_image_bytes(int d, int k);
+size_t mi_kmeans_workspace_bytes(long n, int d, int k);
+int mi_kmeans_prep(const float* centroids, int d, int k, void* image, mi_stream_t stream);
+int mi_kmeans_xnorm(const float* x, long n, int d, float* xnorm, mi_stream_t stream);
+int mi_kmeans_assign(const float* x, const float* xnorm, const void* image, long n, int d, int k, int32_t* labels,
+                     float* dist, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_kmeans_update(const float* x, const int32_t* labels, long n, int d, int k, float* centroids, int32_t* counts,
+                     float* obj, int32_t* nsplit, void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
