@@ -14,6 +14,14 @@ LIB_PATH = os.environ.get("CETPICK_HIP_LIB") or os.path.join(_HERE, "libcetpick_
 _c = ctypes
 _P, _I, _F, _Z, _D, _L = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_double, _c.c_long
 
+
+class ConvGeom(ctypes.Structure):
+    """mi_conv_geom of include/cetpick_hip.h, fields in header order (tests/test_abi.py checks)"""
+    _fields_ = [(f, _I) for f in "N Di Hi Wi Ci Co kd kh kw stride pd ph pw dd dh dw".split()]
+
+
+_G = _c.POINTER(ConvGeom)
+
 # name -> (restype, argtypes); kept in step with include/cetpick_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "mi_abi_version": (_I, []),
@@ -50,23 +58,17 @@ SIGNATURES = {
     "mi_vol_stats": (_I, [_P, _L, _L, _P, _P, _Z, _P]),
     "mi_zscore": (_I, [_P, _P, _L, _L, _P, _P]),
     "mi_zscore_quantize_minmax": (_I, [_P, _P, _L, _L, _P, _D, _D, _I, _P]),
-    "mi_conv3d_workspace_bytes": (_Z, [_I] * 9),
-    "mi_conv3d_fwd_f32": (_I, [_P, _P, _P, _P, _I] + [_I] * 9 + [_P, _Z, _P]),
-    "mi_conv3d_dgrad_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 9 + [_P, _Z, _P]),
-    "mi_conv3d_wgrad_f32": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _Z, _P]),
-    "mi_convnd_workspace_bytes": (_Z, [_I] * 13),
-    "mi_convnd_fwd_f32": (_I, [_P, _P, _P, _P, _I] + [_I] * 13 + [_P, _Z, _P]),
-    "mi_convnd_dgrad_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 13 + [_P, _Z, _P]),
-    "mi_convnd_wgrad_f32": (_I, [_P, _P, _P] + [_I] * 13 + [_P, _Z, _P]),
-    "mi_convnd_fwd_bias_f32": (_I, [_P, _P, _P, _P] + [_I] * 14 + [_P, _Z, _P]),
+    "mi_conv_workspace_bytes": (_Z, [_G]),
+    "mi_conv_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _G, _P, _Z, _P]),
+    "mi_conv_dgrad_f32": (_I, [_P, _P, _P, _P, _P, _G, _P, _Z, _P]),
+    "mi_conv_wgrad_f32": (_I, [_P, _P, _P, _G, _P, _Z, _P, _P]),
+    "mi_conv_wgrad_batch_f32": (_I, [_P, _P, _P, _P, _I, _G, _Z, _P, _P]),
     "mi_stem2d_fwd_bias_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "mi_upconv_tail_fwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7 + [_P]),
     "mi_smallk_image_bytes": (_Z, [_I, _I]),
     "mi_smallk_prep": (_I, [_P, _P, _I, _I, _P]),
     "mi_smallk_fwd_f32": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _I, _P]),
     "mi_smallk_heads_fwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _L, _I, _P]),
-    "mi_convnd_wgrad_slabs_batch_f32": (_I, [_P, _P, _P, _P] + [_I] * 14 + [_Z, _P, _P]),
-    "mi_convnd_wgrad_slabs_f32": (_I, [_P, _P, _P] + [_I] * 13 + [_P, _Z, _P, _P]),
     "mi_splitk_reduce_batch": (_I, [_P, _P, _P, _P, _I, _P]),
     "mi_linear_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "mi_conv3d_direct_wimg_bytes": (_Z, [_I]),
@@ -86,12 +88,10 @@ SIGNATURES = {
     "mi_conv3d_cube2_workspace_bytes": (_Z, [_I, _I]),
     "mi_conv3d_cube2_usable": (_I, [_I] * 9),
     "mi_conv3d_cube2_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
-    "mi_convnd_dil_workspace_bytes": (_Z, [_I] * 15),
     "mi_conv_d32_kind": (_I, [_I] * 12),
     "mi_conv_d32_image_bytes": (_Z, [_I, _I]),
     "mi_conv_d64_image_bytes": (_Z, [_I, _I]),
     "mi_conv_d32_prep": (_I, [_P, _P, _I, _I, _P]),
-    "mi_conv_d64_prep": (_I, [_P, _P, _I, _I, _P]),
     "mi_conv_d64_prep_co": (_I, [_P, _P, _I, _I, _I, _P]),
     "mi_conv_d32_1x1_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mi_conv_d32_fwd_pool_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 7 + [_P]),
@@ -100,9 +100,6 @@ SIGNATURES = {
     "mi_conv_d32_upconv_fwd_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
     "mi_conv_d64_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mi_conv_d32_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "mi_convnd_dil_fwd_f32": (_I, [_P, _P, _P, _P, _I] + [_I] * 15 + [_P, _Z, _P]),
-    "mi_convnd_dil_dgrad_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 15 + [_P, _Z, _P]),
-    "mi_convnd_dil_wgrad_f32": (_I, [_P, _P, _P] + [_I] * 15 + [_P, _Z, _P]),
     "mi_maxpool2d_ceil_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mi_maxpool2d_ceil_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mi_shuffle2x2_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -120,7 +117,6 @@ SIGNATURES = {
     "mi_mse_loss_fwd": (_I, [_P, _P, _L, _P, _P, _P, _Z, _P]),
     "mi_mse_loss_bwd": (_I, [_P, _P, _L, _P, _P, _P, _P, _P]),
     "mi_ucl_rowsums_fwd": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
-    "mi_ucl_rowsums_bwd": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
     "mi_ucl_rowsums_bwd_ranged": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mi_colreduce_workspace_bytes": (_Z, [_L, _I]),
     "mi_bn_stats": (_I, [_P, _L, _I, _P, _P, _Z, _P]),
@@ -153,7 +149,6 @@ SIGNATURES = {
     "mi_rowdot_mean_fwd": (_I, [_P, _P, _P, _I, _I, _P]),
     "mi_rowdot_mean_bwd": (_I, [_P, _P, _P, _I, _I, _P]),
     "mi_column_std_mean": (_I, [_P, _P, _I, _I, _P]),
-    "mi_ce_label0": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "mi_ce_label0_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "mi_ce_label0_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "mi_conv3d_s2_dgrad_usable": (_I, [_I, _I, _I, _I]),
@@ -210,6 +205,11 @@ def check(rc, what):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def host_array(vals, ctype=ctypes.c_void_p):
+    """A host array of device pointers / ints as the void* the C-ABI's array arguments take (the cast keeps the array alive)."""
+    return ctypes.cast((ctype * len(vals))(*vals), ctypes.c_void_p)
 
 
 def stream():

@@ -374,13 +374,6 @@ extern "C" int mi_conv_d64_prep_co(const float* w, void* img, int Ci, int Co, in
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
-extern "C" int mi_conv_d64_prep(const float* w, void* img, int Ci, int ntap, mi_stream_t stream) {
-    if (!w || !img || (Ci != 32 && Ci != 64 && Ci != 128) || ntap != 9) return MI_E_ARG;
-    const int n = (Ci / 16) * ntap * 2 * 64;
-    hipLaunchKernelGGL(conv_d32_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (unsigned char*)img, Ci, ntap, 64);
-    MI_RETURN_IF_LAUNCH_FAILED();
-    return MI_OK;
-}
 
 extern "C" int mi_conv_d64_fwd_f32(const float* x, const void* wimg, const float* bias, float* y, int relu, int N, int D, int H, int W,
                                    int Ci, int Co, mi_stream_t stream);

@@ -1168,7 +1168,7 @@ __device__ void direct3s256_prep_body(const float* w, unsigned char* img, int dg
 // ---- host side (internal: conv_igemm.hip's run_conv dispatches here; extern "C" wrappers at the end) ----
 // 0: not a direct shape; 1: 64 -> 64 channels on 8 x 8 planes (direct3_kernel); 2: 128 -> 128 on 4 x 4 x 4 (direct3s_kernel);
 // 3 (round 4): 128 -> 128 on 8 x 8 planes (direct3_kernel<., 128>: layer2 of a 64^3 crop) - reached through mi_conv3d_* /
-// mi_convnd_* only (image cut per call), not through the caller-kept images of mi_conv3d_direct_*
+// mi_conv_fwd_f32 / mi_conv_dgrad_f32 only (image cut per call), not through the caller-kept images of mi_conv3d_direct_*
 int mi_direct3_kind(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride, int pd, int ph,
                     int pw, int dd, int dh, int dw) {
     const char* off = getenv("MI_CONV_NO_DIRECT");      // A/B switch: keep the implicit GEMM
@@ -1384,7 +1384,7 @@ extern "C" size_t mi_conv3d_direct_workspace_bytes(int N, int channels) { return
 
 extern "C" int mi_conv3d_direct_usable(int N, int Di, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad) {
     const int kind = mi_direct3_kind(N, Di, Hi, Wi, Ci, Co, k, k, k, stride, pad, pad, pad, 1, 1, 1);
-    return kind <= 2 ? kind : 0;           // (kinds 3 and 5 cut their image per call inside mi_conv3d_* / mi_convnd_*)
+    return kind <= 2 ? kind : 0;           // (kinds 3 and 5 cut their image per call inside mi_conv_fwd_f32 / mi_conv_dgrad_f32)
 }
 
 extern "C" int mi_conv3d_direct_prep(const void* const* w, void* const* img, const int* dgrad, const int* channels, int n,

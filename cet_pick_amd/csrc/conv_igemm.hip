@@ -1006,16 +1006,24 @@ bool geom_ok(const Geom& g) {
     if ((g.dd > 1 || g.dh > 1 || g.dw > 1) && (g.stride != 1 || g.Ci == 1)) return false;   // dilation: stride 1, no stem
     return true;
 }
-Geom make_geom_nd(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride,
-                  int pd, int ph, int pw, int dd = 1, int dh = 1, int dw = 1) {
-    Geom g{N, Di, Hi, Wi, Ci, 0, 0, 0, Co, kd, kh, kw, stride, pd, ph, pw, dd, dh, dw};
-    g.Do = (Di + 2 * pd - dd * (kd - 1) - 1) / stride + 1;
-    g.Ho = (Hi + 2 * ph - dh * (kh - 1) - 1) / stride + 1;
-    g.Wo = (Wi + 2 * pw - dw * (kw - 1) - 1) / stride + 1;
+// the public description (include/cetpick_hip.h) with its output extent
+Geom from_public(const mi_conv_geom& p) {
+    Geom g{p.N, p.Di, p.Hi, p.Wi, p.Ci, 0, 0, 0, p.Co, p.kd, p.kh, p.kw, p.stride, p.pd, p.ph, p.pw, p.dd, p.dh, p.dw};
+    const int s = p.stride > 0 ? p.stride : 1;                         // (geom_ok refuses the geometry; no division by zero here)
+    g.Do = (p.Di + 2 * p.pd - p.dd * (p.kd - 1) - 1) / s + 1;
+    g.Ho = (p.Hi + 2 * p.ph - p.dh * (p.kh - 1) - 1) / s + 1;
+    g.Wo = (p.Wi + 2 * p.pw - p.dw * (p.kw - 1) - 1) / s + 1;
     return g;
 }
+// cubic window, no dilation (the stem and linear entries below)
 Geom make_geom(int N, int Di, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad) {
-    return make_geom_nd(N, Di, Hi, Wi, Ci, Co, k, k, k, stride, pad, pad, pad);
+    return from_public(mi_conv_geom{N, Di, Hi, Wi, Ci, Co, k, k, k, stride, pad, pad, pad, 1, 1, 1});
+}
+// a caller's geometry as the public entries see it: false = MI_E_ARG
+bool public_geom(const mi_conv_geom* pg, Geom* g) {
+    if (!pg) return false;
+    *g = from_public(*pg);
+    return geom_ok(*g) && g->Do > 0 && g->Ho > 0 && g->Wo > 0;
 }
 
 // rows of DGRAD parity class c and its reduction length in taps
@@ -1207,6 +1215,20 @@ size_t direct3_ws_bytes(const Geom& g) {
     return b;
 }
 
+// a workspace that serves forward, data gradient and weight gradient of this geometry, whichever kernel family takes them
+size_t conv_ws_bytes(const Geom& g) {
+    size_t best = is_stem7(g) ? std::max(mi_stem7_wgrad_workspace_bytes(g.N, g.Di, g.Hi, g.Wi, g.Co), mi_stem7_fwd_workspace_bytes()) : 0;
+    best = std::max(best, direct3_ws_bytes(g));
+    if (mi_pair_wgrad_usable(g.N, g.Di, g.Hi, g.Wi, g.Ci, g.Co, g.kd, g.kh, g.kw, g.stride, g.pd, g.ph, g.pw, g.dd, g.dh, g.dw))
+        best = std::max(best, mi_pair_wgrad_slab_bytes(g.N, g.Di, g.Ci, g.Co, g.kd, g.stride));
+    for (int mode = 0; mode < 3; ++mode) {
+        Setup st;
+        if (setup_conv(mode, g, &st)) continue;
+        if (st.pl.splits > 1) best = std::max(best, sizeof(float) * (size_t)st.p.M * st.p.Ncols * st.pl.splits);
+    }
+    return best + 256;
+}
+
 // defer_splits != null (weight gradients only): a split launch leaves its slabs in `ws` un-reduced and reports the split
 // count - the caller sums many layers' slabs in one mi_splitk_reduce_batch launch; an unsplit launch (or the stem,
 // which reduces by itself) reports 1 and `out` is final.
@@ -1383,28 +1405,32 @@ int mi_direct3_finish_slabs(const float* slabs, int n_slabs, long out_elems, flo
     return MI_OK;
 }
 
-extern "C" size_t mi_conv3d_workspace_bytes(int N, int Di, int Hi, int Wi, int Ci, int Co, int k,
-                                            int stride, int pad) {
-    Geom g = make_geom(N, Di, Hi, Wi, Ci, Co, k, stride, pad);
-    if (!geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return 0;
-    size_t best = is_stem7(g) ? std::max(mi_stem7_wgrad_workspace_bytes(g.N, g.Di, g.Hi, g.Wi, g.Co), mi_stem7_fwd_workspace_bytes()) : 0;
-    best = std::max(best, direct3_ws_bytes(g));
-    if (mi_pair_wgrad_usable(g.N, g.Di, g.Hi, g.Wi, g.Ci, g.Co, g.kd, g.kh, g.kw, g.stride, g.pd, g.ph, g.pw, g.dd, g.dh, g.dw))
-        best = std::max(best, mi_pair_wgrad_slab_bytes(g.N, g.Di, g.Ci, g.Co, g.kd, g.stride));
-    for (int mode = 0; mode < 3; ++mode) {
-        Setup st;
-        if (setup_conv(mode, g, &st)) continue;
-        if (st.pl.splits > 1) best = std::max(best, sizeof(float) * (size_t)st.p.M * st.p.Ncols * st.pl.splits);
-    }
-    return best + 256;
+/* ---- the public convolution family (include/cetpick_hip.h): one geometry struct, the parameters of run_conv ---- */
+extern "C" size_t mi_conv_workspace_bytes(const mi_conv_geom* pg) {
+    Geom g;
+    return public_geom(pg, &g) ? conv_ws_bytes(g) : 0;
 }
 
-extern "C" int mi_conv3d_fwd_f32(const float* x, const float* w, float* y, const float* res,
-                                 int relu, int N, int Di, int Hi, int Wi, int Ci, int Co, int k,
-                                 int stride, int pad, void* ws, size_t ws_bytes, mi_stream_t stream) {
-    Geom g = make_geom(N, Di, Hi, Wi, Ci, Co, k, stride, pad);
-    if (!x || !w || !y || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_FWD, g, x, w, y, res, nullptr, relu, ws, ws_bytes, (hipStream_t)stream);
+extern "C" int mi_conv_fwd_f32(const float* x, const float* w, float* y, const float* res, int res_is_bias, int relu,
+                               const mi_conv_geom* pg, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    Geom g;
+    if (!x || !w || !y || (res_is_bias && !res) || !public_geom(pg, &g)) return MI_E_ARG;
+    return run_conv(MODE_FWD, g, x, w, y, res, nullptr, relu, ws, ws_bytes, (hipStream_t)stream, nullptr, res_is_bias ? 1 : 0);
+}
+
+extern "C" int mi_conv_dgrad_f32(const float* dy, const float* w, float* dx, const float* res, const float* mask,
+                                 const mi_conv_geom* pg, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    Geom g;
+    if (!dy || !w || !dx || !public_geom(pg, &g)) return MI_E_ARG;
+    return run_conv(MODE_DGRAD, g, dy, w, dx, res, mask, 0, ws, ws_bytes, (hipStream_t)stream);
+}
+
+/* splits_out == NULL: dw is final.  Otherwise the split-K reduction is left to the caller (run_conv's defer_splits). */
+extern "C" int mi_conv_wgrad_f32(const float* x, const float* dy, float* dw, const mi_conv_geom* pg, void* ws, size_t ws_bytes,
+                                 int* splits_out, mi_stream_t stream) {
+    Geom g;
+    if (!x || !dy || !dw || !public_geom(pg, &g)) return MI_E_ARG;
+    return run_conv(MODE_WGRAD, g, x, dy, dw, nullptr, nullptr, 0, ws, ws_bytes, (hipStream_t)stream, splits_out);
 }
 
 /* measurement aid: the kernel family the last mi_conv* call of the calling thread ran ("direct3", "cube2 + reduce", ...) */
@@ -1445,7 +1471,7 @@ extern "C" int mi_linear_stats_fwd_f32(const float* x, const float* w, const flo
  * the batch statistics its BatchNorm3d needs (`bn1`, :326-328): sums[0..Co) = column sums of y, sums[Co..2Co) = column sums
  * of y^2 (doubles, what mi_bn_stats would produce from y), taken from the output tiles while they are still in registers.
  * MI_E_UNSUPPORTED where the stem kernel does not apply (shape, Co != 64, MI_CONV_ARITH=f32): the caller then runs
- * mi_conv3d_fwd_f32 + mi_bn_stats. */
+ * mi_conv_fwd_f32 + mi_bn_stats. */
 extern "C" size_t mi_conv3d_stem_stats_workspace_bytes(int N, int Di, int Hi, int Wi, int Co) {
     Geom g = make_geom(N, Di, Hi, Wi, 1, Co, 7, 2, 3);
     if (!geom_ok(g) || !is_stem7(g) || Co != 64) return 0;
@@ -1469,96 +1495,14 @@ extern "C" int mi_linear_fwd_f32(const float* x, const float* w, const float* bi
     return run_conv(MODE_FWD, g, x, w, y, bias, nullptr, 0, ws, ws_bytes, (hipStream_t)stream, nullptr, bias ? 1 : 0);
 }
 
-extern "C" int mi_conv3d_dgrad_f32(const float* dy, const float* w, float* dx, const float* res,
-                                   const float* mask, int N, int Di, int Hi, int Wi, int Ci, int Co,
-                                   int k, int stride, int pad, void* ws, size_t ws_bytes,
-                                   mi_stream_t stream) {
-    Geom g = make_geom(N, Di, Hi, Wi, Ci, Co, k, stride, pad);
-    if (!dy || !w || !dx || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_DGRAD, g, dy, w, dx, res, mask, 0, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int mi_conv3d_wgrad_f32(const float* x, const float* dy, float* dw, int N, int Di,
-                                   int Hi, int Wi, int Ci, int Co, int k, int stride, int pad,
-                                   void* ws, size_t ws_bytes, mi_stream_t stream) {
-    Geom g = make_geom(N, Di, Hi, Wi, Ci, Co, k, stride, pad);
-    if (!x || !dy || !dw || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_WGRAD, g, x, dy, dw, nullptr, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
-}
-
-// ---- per-axis window / padding (2-D convolutions of the SimSiam 2-D encoder: kd = 1, pd = 0, D = 1)
-extern "C" size_t mi_convnd_workspace_bytes(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh,
-                                            int kw, int stride, int pd, int ph, int pw) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return 0;
-    size_t best = is_stem7(g) ? std::max(mi_stem7_wgrad_workspace_bytes(g.N, g.Di, g.Hi, g.Wi, g.Co), mi_stem7_fwd_workspace_bytes()) : 0;
-    best = std::max(best, direct3_ws_bytes(g));
-    if (mi_pair_wgrad_usable(g.N, g.Di, g.Hi, g.Wi, g.Ci, g.Co, g.kd, g.kh, g.kw, g.stride, g.pd, g.ph, g.pw, g.dd, g.dh, g.dw))
-        best = std::max(best, mi_pair_wgrad_slab_bytes(g.N, g.Di, g.Ci, g.Co, g.kd, g.stride));
-    for (int mode = 0; mode < 3; ++mode) {
-        Setup st;
-        if (setup_conv(mode, g, &st)) continue;
-        if (st.pl.splits > 1) best = std::max(best, sizeof(float) * (size_t)st.p.M * st.p.Ncols * st.pl.splits);
-    }
-    return best + 256;
-}
-
-extern "C" int mi_convnd_fwd_f32(const float* x, const float* w, float* y, const float* res, int relu,
-                                 int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw,
-                                 int stride, int pd, int ph, int pw, void* ws, size_t ws_bytes,
-                                 mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!x || !w || !y || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_FWD, g, x, w, y, res, nullptr, relu, ws, ws_bytes, (hipStream_t)stream);
-}
-
-/* y = act(conv(x, w) + bias[co]) - the same launch with the residual read as ONE row of Co values.  Evaluation-mode BatchNorm
- * folds into it (w' = w * gamma / sqrt(var + eps) per output channel, bias = beta - mean * gamma / sqrt(var + eps)): the detector's
- * U-Net at inference (models/networks/unet_small.py:30-97, unet.py:198-399: conv -> BatchNorm -> ReLU) drops its BatchNorm passes. */
-extern "C" int mi_convnd_fwd_bias_f32(const float* x, const float* w, float* y, const float* bias, int relu,
-                                      int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw,
-                                      int stride, int pd, int ph, int pw, void* ws, size_t ws_bytes,
-                                      mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!x || !w || !y || !bias || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_FWD, g, x, w, y, bias, nullptr, relu, ws, ws_bytes, (hipStream_t)stream, nullptr, 1);
-}
-
-extern "C" int mi_convnd_dgrad_f32(const float* dy, const float* w, float* dx, const float* res,
-                                   const float* mask, int N, int Di, int Hi, int Wi, int Ci, int Co,
-                                   int kd, int kh, int kw, int stride, int pd, int ph, int pw, void* ws,
-                                   size_t ws_bytes, mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!dy || !w || !dx || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_DGRAD, g, dy, w, dx, res, mask, 0, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int mi_convnd_wgrad_f32(const float* x, const float* dy, float* dw, int N, int Di, int Hi,
-                                   int Wi, int Ci, int Co, int kd, int kh, int kw, int stride, int pd,
-                                   int ph, int pw, void* ws, size_t ws_bytes, mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!x || !dy || !dw || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_WGRAD, g, x, dy, dw, nullptr, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int mi_convnd_wgrad_slabs_f32(const float* x, const float* dy, float* dw, int N, int Di, int Hi, int Wi, int Ci,
-                                         int Co, int kd, int kh, int kw, int stride, int pd, int ph, int pw, void* ws,
-                                         size_t ws_bytes, int* splits_out, mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!x || !dy || !dw || !splits_out || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_WGRAD, g, x, dy, dw, nullptr, nullptr, 0, ws, ws_bytes, (hipStream_t)stream, splits_out);
-}
-
 /* nb weight gradients of ONE geometry in one launch (the engine issues a stage's weight gradients together, behind the stage's
  * data-gradient chain): problem i reads xs[i] / dys[i] and leaves *splits_out slabs in wss[i] (> 1: the caller's
  * mi_splitk_reduce_batch sums them into dws[i]) or, *splits_out == 1, the final gradient in dws[i].  MI_E_UNSUPPORTED: this
  * geometry has no batched kernel - the caller issues nb single calls.  ws_bytes: size of EACH workspace. */
-extern "C" int mi_convnd_wgrad_slabs_batch_f32(const float* const* xs, const float* const* dys, float* const* dws, void* const* wss,
-                                               int nb, int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw,
-                                               int stride, int pd, int ph, int pw, size_t ws_bytes, int* splits_out,
-                                               mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw);
-    if (!xs || !dys || !dws || !wss || !splits_out || nb < 1 || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
+extern "C" int mi_conv_wgrad_batch_f32(const float* const* xs, const float* const* dys, float* const* dws, void* const* wss, int nb,
+                                       const mi_conv_geom* pg, size_t ws_bytes, int* splits_out, mi_stream_t stream) {
+    Geom g;
+    if (!xs || !dys || !dws || !wss || !splits_out || nb < 1 || !public_geom(pg, &g)) return MI_E_ARG;
     for (int i = 0; i < nb; ++i) if (!xs[i] || !dys[i] || !dws[i]) return MI_E_ARG;
     if (nb < 2 || !conv_arith_bf16x3() || env_int("MI_NO_WGRAD_BATCH")) return MI_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
@@ -1648,49 +1592,4 @@ extern "C" int mi_splitk_reduce_batch(const void* const* slabs, void* const* out
         MI_RETURN_IF_LAUNCH_FAILED();
     }
     return MI_OK;
-}
-
-// ---- dilated windows (stride 1): the 3-D head of the detector, unet_small.py:38-41 (kernel 3x3x3,
-// dilation (1,4,4), padding (1,4,4))
-extern "C" size_t mi_convnd_dil_workspace_bytes(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh,
-                                                int kw, int pd, int ph, int pw, int dd, int dh, int dw) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, 1, pd, ph, pw, dd, dh, dw);
-    if (!geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return 0;
-    size_t best = is_stem7(g) ? std::max(mi_stem7_wgrad_workspace_bytes(g.N, g.Di, g.Hi, g.Wi, g.Co), mi_stem7_fwd_workspace_bytes()) : 0;
-    best = std::max(best, direct3_ws_bytes(g));
-    if (mi_pair_wgrad_usable(g.N, g.Di, g.Hi, g.Wi, g.Ci, g.Co, g.kd, g.kh, g.kw, g.stride, g.pd, g.ph, g.pw, g.dd, g.dh, g.dw))
-        best = std::max(best, mi_pair_wgrad_slab_bytes(g.N, g.Di, g.Ci, g.Co, g.kd, g.stride));
-    for (int mode = 0; mode < 3; ++mode) {
-        Setup st;
-        if (setup_conv(mode, g, &st)) continue;
-        if (st.pl.splits > 1) best = std::max(best, sizeof(float) * (size_t)st.p.M * st.p.Ncols * st.pl.splits);
-    }
-    return best + 256;
-}
-
-extern "C" int mi_convnd_dil_fwd_f32(const float* x, const float* w, float* y, const float* res, int relu,
-                                     int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw,
-                                     int pd, int ph, int pw, int dd, int dh, int dw, void* ws,
-                                     size_t ws_bytes, mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, 1, pd, ph, pw, dd, dh, dw);
-    if (!x || !w || !y || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_FWD, g, x, w, y, res, nullptr, relu, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int mi_convnd_dil_dgrad_f32(const float* dy, const float* w, float* dx, const float* res,
-                                       const float* mask, int N, int Di, int Hi, int Wi, int Ci, int Co,
-                                       int kd, int kh, int kw, int pd, int ph, int pw, int dd, int dh,
-                                       int dw, void* ws, size_t ws_bytes, mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, 1, pd, ph, pw, dd, dh, dw);
-    if (!dy || !w || !dx || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_DGRAD, g, dy, w, dx, res, mask, 0, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int mi_convnd_dil_wgrad_f32(const float* x, const float* dy, float* dwt, int N, int Di, int Hi,
-                                       int Wi, int Ci, int Co, int kd, int kh, int kw, int pd, int ph,
-                                       int pw, int dd, int dh, int dw, void* ws, size_t ws_bytes,
-                                       mi_stream_t stream) {
-    Geom g = make_geom_nd(N, Di, Hi, Wi, Ci, Co, kd, kh, kw, 1, pd, ph, pw, dd, dh, dw);
-    if (!x || !dy || !dwt || !geom_ok(g) || g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return MI_E_ARG;
-    return run_conv(MODE_WGRAD, g, x, dy, dwt, nullptr, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
 }

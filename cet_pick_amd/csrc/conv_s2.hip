@@ -641,7 +641,7 @@ extern "C" int mi_conv3d_s2_prep(const float* const* w, const float* const* w_ds
 
 /* Forward of a stride-2 block front of the MoCo-3D encoder (models/networks/moco_encoder_3d.py:55-84, 257-272): hmid = relu(conv3d(x;
  * w [27][Ci][Co], k 3, stride 2, pad 1)) and the shortcut r = conv3d(x; w_ds [Ci][Co], k 1, stride 2) in one launch.  Shapes: the
- * encoder's two at 32^3 crops (Gi 8, 64 -> 128 and Gi 4, 128 -> 256) and layer3.0 of the 64^3 crops (Gi 8, 128 -> 256), bf16x3 arithmetic; otherwise MI_E_UNSUPPORTED (run mi_conv3d_fwd_f32
+ * encoder's two at 32^3 crops (Gi 8, 64 -> 128 and Gi 4, 128 -> 256) and layer3.0 of the 64^3 crops (Gi 8, 128 -> 256), bf16x3 arithmetic; otherwise MI_E_UNSUPPORTED (run mi_conv_fwd_f32
  * twice).  The weight image is cut into `ws` (mi_conv3d_s2_fwd_workspace_bytes) by this call. */
 extern "C" int mi_conv3d_s2_fwd_usable(int N, int Gi, int Ci, int Co) {
     const char* no = getenv("MI_CONV_NO_S2FWD");       // A/B switch: the generic launches

@@ -770,9 +770,10 @@ __global__ __launch_bounds__(1024) void ucl_rowmax_range_kernel(const float* row
     }
 }
 
-extern "C" int mi_ucl_rowsums_bwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T,
-                                  const float* rowmax, const float* g_all, const float* g_pos, const float* g_other,
-                                  const float* g_pair, float* dfeat, mi_stream_t stream) {
+// both terms of a similarity tile in one launch (dim 32) or two (dim 64, MI_UCL_BWD_SPLIT=1); the public entry is the ranged form below
+static int ucl_rowsums_bwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const float* rowmax,
+                           const float* g_all, const float* g_pos, const float* g_other, const float* g_pair, float* dfeat,
+                           mi_stream_t stream) {
     if (!feat || !cls || !rowmax || !g_all || !g_pos || !g_other || !g_pair || !dfeat || n2 <= 0 || (n2 & 1)) return MI_E_ARG;
     const dim3 grid((n2 + UB - 1) / UB), block(256);
     hipStream_t s = (hipStream_t)stream;
@@ -801,7 +802,7 @@ extern "C" int mi_ucl_rowsums_bwd_ranged(const float* feat, const uint8_t* cls, 
                                          const float* g_all, const float* g_pos, const float* g_other, const float* g_pair, float* dfeat,
                                          float* range, mi_stream_t stream) {
     if (!range || dim != 32 || getenv("MI_UCL_BWD_SPLIT") || getenv("MI_UCL_BWD_TWO_EXP"))
-        return mi_ucl_rowsums_bwd(feat, cls, n2, dim, inv_T, rowmax, g_all, g_pos, g_other, g_pair, dfeat, stream);
+        return ucl_rowsums_bwd(feat, cls, n2, dim, inv_T, rowmax, g_all, g_pos, g_other, g_pair, dfeat, stream);
     if (!feat || !cls || !rowmax || !g_all || !g_pos || !g_other || !g_pair || !dfeat || n2 <= 0 || (n2 & 1)) return MI_E_ARG;
     const dim3 grid((n2 + UB - 1) / UB), block(256);
     hipStream_t s = (hipStream_t)stream;

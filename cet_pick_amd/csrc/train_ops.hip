@@ -909,37 +909,8 @@ __global__ __launch_bounds__(256) void moco_logits_bwd_kernel(const float* dlogi
     if (lane == 0) dq[(long)b * C + c] = (s + dl[0] * k[(long)b * C + c]) * invT;
 }
 
-// mean cross-entropy against label 0 and its gradient: dlogits = scale * (softmax - onehot0) / B
-// one workgroup per row; row_loss[b] written, loss reduced by a second tiny kernel (fixed order)
-__global__ __launch_bounds__(256) void ce0_kernel(const float* logits, float* row_loss,
-                                                 float* dlogits, int B, int n, float scale) {
-    __shared__ float red[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* l = logits + (long)b * n;
-    float m = -INFINITY;
-    for (int j = tid; j < n; j += 256) m = fmaxf(m, l[j]);
-    m = wave_max(m);
-    if ((tid & 63) == 0) red[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float s = 0.f;
-    for (int j = tid; j < n; j += 256) s += expf(l[j] - m);
-    s = wave_sum(s);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    s = red[0] + red[1] + red[2] + red[3];
-    const float lse = m + logf(s);
-    if (tid == 0) row_loss[b] = lse - l[0];
-    if (dlogits) {
-        const float g = scale / (float)B;
-        for (int j = tid; j < n; j += 256) {
-            float pj = expf(l[j] - lse);
-            dlogits[(long)b * n + j] = g * (pj - (j == 0 ? 1.f : 0.f));
-        }
-    }
-}
-// One workgroup per row (as ce0_kernel); the workgroup that finishes LAST sums the row losses in row order and writes the
+// mean cross-entropy against label 0: loss = mean_b(logsumexp(l_b) - l_b[0])
+// One workgroup per row; the workgroup that finishes LAST sums the row losses in row order and writes the
 // mean - one launch, deterministic.  (A single 16-wave workgroup for all rows was measured at 29 us on the step's critical
 // path against 5 us here.)  The arrival counter is the caller's (one word per stream, zero before the first call): it resets
 // itself, so launches on different streams - the key branch's side stream, a second model, an eager step beside a graph
@@ -988,13 +959,6 @@ __global__ __launch_bounds__(256) void ce0_bwd_kernel(const float* logits, const
     const float g = (*g_dev) / (float)B, lse = row_lse[b];
     const float* l = logits + (long)b * n;
     for (int j = threadIdx.x; j < n; j += 256) dlogits[(long)b * n + j] = g * (expf(l[j] - lse) - (j == 0 ? 1.f : 0.f));
-}
-__global__ void mean_kernel(const float* v, int n, float* out) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < n; ++i) s += v[i];
-        *out = s / (float)n;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1480,17 +1444,6 @@ extern "C" int mi_moco_logits_bwd(const float* dlogits, const float* k, const fl
     if (!dlogits || !k || !queue || !dq || B <= 0 || C <= 0 || R <= 0 || !(T > 0.f)) return MI_E_ARG;
     hipLaunchKernelGGL(moco_logits_bwd_kernel, dim3(B, (C + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                        dlogits, k, queue, dq, C, R, 1.0f / T);
-    MI_RETURN_IF_LAUNCH_FAILED();
-    return MI_OK;
-}
-
-extern "C" int mi_ce_label0(const float* logits, float* loss, float* row_loss, float* dlogits, int B,
-                            int n, float grad_scale, mi_stream_t stream) {
-    if (!logits || !loss || !row_loss || B <= 0 || n <= 0) return MI_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce0_kernel, dim3(B), dim3(256), 0, s, logits, row_loss, dlogits, B, n, grad_scale);
-    MI_RETURN_IF_LAUNCH_FAILED();
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, s, (const float*)row_loss, B, loss);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }

@@ -9,6 +9,7 @@ the model was flattened by :class:`ParamArena`): a parameter whose ``.grad`` is 
 gradient assigned, otherwise it is accumulated - the same contract as torch's AccumulateGrad.
 PyTorch is the allocator / stream owner; all arithmetic happens in the HIP kernels.
 """
+import ctypes
 import os
 import torch
 import torch.nn as nn
@@ -254,9 +255,27 @@ def _as5d(x):
     return x if x.dim() == 5 else x.unsqueeze(1)
 
 
-def _out_dims(shape5, k3, stride, p3):
-    n, d, h, w, _ = shape5
-    return tuple((v + 2 * p - k) // stride + 1 for v, k, p in zip((d, h, w), k3, p3))
+class _Geom:
+    """One convolution problem - (N, D, H, W, Ci) -> co channels, window k3, stride, padding p3, dilation d3 (None: none) - as the
+    C-ABI takes it: the mi_conv_geom struct built once (`ref` is what the mi_conv_* entries get), the output extent, the tap count of
+    the FLOP tags and a hashable key."""
+    __slots__ = ("key", "c", "ref", "out", "taps")
+
+    def __init__(self, shape5, co, k3, stride, p3, d3=None):
+        d3 = (1, 1, 1) if d3 is None else tuple(d3)
+        self.key = tuple(int(v) for v in shape5) + (int(co),) + tuple(k3) + (int(stride),) + tuple(p3) + d3
+        self.c = L.ConvGeom(*self.key)
+        self.ref = ctypes.byref(self.c)
+        self.out = tuple((v + 2 * p - dl * (k - 1) - 1) // stride + 1 for v, k, p, dl in zip(shape5[1:4], k3, p3, d3))
+        self.taps = k3[0] * k3[1] * k3[2]
+
+    def workspace(self, device):
+        return _ws(L.lib().mi_conv_workspace_bytes(self.ref), device, "conv")
+
+
+def _linear_geom(m, ci, co):
+    """nn.Linear on m rows: the 1 x 1 x 1 convolution of m one-voxel volumes."""
+    return _Geom((m, 1, 1, 1, ci), co, (1, 1, 1), 1, (0, 0, 0))
 
 
 # Pre-cut weight images of the conv_direct3.hip / conv_s2.hip / conv_p2d.hip convolutions.  Outside a step engine an image is cut in
@@ -269,16 +288,11 @@ ACTIVE_IMAGES = None
 def _prep_images(fn, items):
     """items: [(weight, None, dgrad flag, image tensor)] - all cut by `fn` (mi_conv3d_direct_prep / mi_conv2d_p2d_prep: one launch per 16)
     on the current stream."""
-    import ctypes
-    n = len(items)
-    if not n:
+    if not items:
         return
-    ws = (ctypes.c_void_p * n)(*[it[0].data_ptr() for it in items])
-    imgs = (ctypes.c_void_p * n)(*[it[3].data_ptr() for it in items])
-    dg = (ctypes.c_int * n)(*[it[2] for it in items])
-    ch = (ctypes.c_int * n)(*[int(it[0].shape[0]) for it in items])
-    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    L.check(getattr(L.lib(), fn)(cast(ws), cast(imgs), cast(dg), cast(ch), n, L.stream()), fn)
+    L.check(getattr(L.lib(), fn)(L.host_array([it[0].data_ptr() for it in items]), L.host_array([it[3].data_ptr() for it in items]),
+                                 L.host_array([it[2] for it in items], ctypes.c_int),
+                                 L.host_array([int(it[0].shape[0]) for it in items], ctypes.c_int), len(items), L.stream()), fn)
 
 
 class WeightImages:
@@ -332,17 +346,12 @@ class WeightImages:
     def _refresh_s2(items):
         if not items:
             return
-        import ctypes
-        n = len(items)
-        ws = (ctypes.c_void_p * n)(*[it[0].data_ptr() for it in items])
-        wd = (ctypes.c_void_p * n)(*[(it[1].data_ptr() if it[1] is not None else None) for it in items])
-        imgs = (ctypes.c_void_p * n)(*[it[3].data_ptr() for it in items])
-        ci = (ctypes.c_int * n)(*[int(it[0].shape[1]) for it in items])
-        co = (ctypes.c_int * n)(*[int(it[0].shape[0]) for it in items])
-        dg = (ctypes.c_int * n)(*[it[2] for it in items])
-        cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-        L.check(L.lib().mi_conv3d_s2_prep(cast(ws), cast(wd), cast(imgs), cast(ci), cast(co), cast(dg), n, L.stream()),
-                "mi_conv3d_s2_prep")
+        arr = L.host_array
+        L.check(L.lib().mi_conv3d_s2_prep(arr([it[0].data_ptr() for it in items]),
+                                          arr([(it[1].data_ptr() if it[1] is not None else None) for it in items]),
+                                          arr([it[3].data_ptr() for it in items]), arr([int(it[0].shape[1]) for it in items], ctypes.c_int),
+                                          arr([int(it[0].shape[0]) for it in items], ctypes.c_int),
+                                          arr([it[2] for it in items], ctypes.c_int), len(items), L.stream()), "mi_conv3d_s2_prep")
 
     def refresh(self, group):
         """Re-cut every image of `group` from the current weights on the current stream: one launch for the group's stride-2
@@ -634,47 +643,38 @@ def conv_fwd(x, w, k, stride, pad, res=None, relu=False, dil=None, owner=None, i
         if res is not None:
             _f32c(res, "res")
         return _p2d_call(x, owner if owner is not None else w, False, res, None, relu, "fwd")
-    x5 = _as5d(x)
-    n, d, h, wd, ci = x5.shape
+    n, d, h, wd, ci = _as5d(x).shape
     co = w.shape[0]
     lib = L.lib()
-    if dil is not None and tuple(dil) != (1, 1, 1):
-        d3 = _k3(dil, nd5)
-        if stride != 1:
-            raise L.HipExtensionError("dilated convolution needs stride 1")
-        do, ho, wo = (v + 2 * p - dl * (kk - 1) for v, kk, p, dl in zip((d, h, wd), k3, p3, d3))
-        y = torch.empty((n, do, ho, wo, co) if nd5 else (n, ho, wo, co), dtype=torch.float32, device=x.device)
-        ws = _ws(lib.mi_convnd_dil_workspace_bytes(n, d, h, wd, ci, co, *k3, *p3, *d3), x.device, "conv")
-        def call():
-            return L.check(lib.mi_convnd_dil_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(res), int(relu), n, d, h,
-                wd, ci, co, *k3, *p3, *d3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_dil_fwd_f32")
-        _prof_run("fwd", 2.0 * n * do * ho * wo * co * ci * k3[0] * k3[1] * k3[2], call)
-        return y
-    do, ho, wo = _out_dims(x5.shape, k3, stride, p3)
-    y = torch.empty((n, do, ho, wo, co) if nd5 else (n, ho, wo, co), dtype=torch.float32, device=x.device)
-    img = _cached_image(w, False, n, d, h, wd, k3, stride, p3) if nd5 else None
+    dilated = dil is not None and tuple(dil) != (1, 1, 1)
+    if dilated and stride != 1:
+        raise L.HipExtensionError("dilated convolution needs stride 1")
+    g = _Geom((n, d, h, wd, ci), co, k3, stride, p3, _k3(dil, nd5) if dilated else None)
+    y = torch.empty((n,) + (g.out if nd5 else g.out[1:]) + (co,), dtype=torch.float32, device=x.device)
+    flops = 2.0 * y.numel() * ci * g.taps
+    img = _cached_image(w, False, n, d, h, wd, k3, stride, p3) if (nd5 and not dilated) else None
     if img is not None:
         ws = _ws(lib.mi_conv3d_direct_workspace_bytes(n, ci), x.device, "conv")
         L.check(lib.mi_conv3d_direct_f32(L.ptr(x), L.ptr(img), L.ptr(y), L.ptr(res), None, int(relu), n, d, h, wd, ci,
                                          L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_direct_f32")
         return y
-    if nd5 and _cube2_final(lib, n, d, h, wd, ci, co, k3, stride, p3):
+    if nd5 and not dilated and _cube2_final(lib, n, d, h, wd, ci, co, k3, stride, p3):
         ws = _cube2_ws(lib, n, ci, x.device)
         def call():
             return _cube2_call(lib, x, w, y, res, None, int(relu), 0, n, ci, ws)
-        _prof_run("fwd", 2.0 * n * do * ho * wo * co * ci * 27, call)
+        _prof_run("fwd", flops, call)
         return y
-    ws = _ws(lib.mi_convnd_workspace_bytes(n, d, h, wd, ci, co, *k3, stride, *p3), x.device, "conv")
+    ws = g.workspace(x.device)
     def call():
-        return L.check(lib.mi_convnd_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(res), int(relu), n, d, h, wd, ci,
-            co, *k3, stride, *p3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_fwd_f32")
-    _prof_run("fwd", 2.0 * n * do * ho * wo * co * ci * k3[0] * k3[1] * k3[2], call)
+        return L.check(lib.mi_conv_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(res), 0, int(relu), g.ref, L.ptr(ws), ws.numel(),
+                                           L.stream()), "mi_conv_fwd_f32")
+    _prof_run("fwd", flops, call)
     return y
 
 
 def _cube2_final(lib, n, d, h, wd, ci, co, k3, stride, p3):
     """3^3 / stride 1 / padding 1 on a 2 x 2 x 2 volume (layer3, feature_3d): conv_cube2.hip, final in one launch
-    (mi_conv3d_cube2_f32; MI_CUBE2_REDUCE=1 keeps the partial sums + reduce launch of mi_convnd_*)."""
+    (mi_conv3d_cube2_f32; MI_CUBE2_REDUCE=1 keeps the partial sums + reduce launch of mi_conv_fwd_f32 / mi_conv_dgrad_f32)."""
     if os.environ.get("MI_CUBE2_REDUCE") or os.environ.get("MI_CONV_ARITH", "")[:1] == "f":
         return False
     return (tuple(k3) == (3, 3, 3) and tuple(p3) == (1, 1, 1) and
@@ -709,15 +709,9 @@ def conv_dgrad(dy, w, in_shape, k, stride, pad, res=None, mask=None, dil=None):
         return _p2d_call(dy, w, True, res, mask, False, "dgrad")
     dx = torch.empty(tuple(in_shape), dtype=torch.float32, device=dy.device)
     lib = L.lib()
-    flops = 2.0 * dy.numel() * ci * k3[0] * k3[1] * k3[2]
-    if dil is not None and tuple(_k3(dil, nd5)) != (1, 1, 1):
-        d3 = _k3(dil, nd5)
-        ws = _ws(lib.mi_convnd_dil_workspace_bytes(n, d, h, wd, ci, co, *k3, *p3, *d3), dy.device, "conv")
-        def call():
-            return L.check(lib.mi_convnd_dil_dgrad_f32(L.ptr(dy), L.ptr(w), L.ptr(dx), L.ptr(res), L.ptr(mask), n, d,
-                h, wd, ci, co, *k3, *p3, *d3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_dil_dgrad_f32")
-        _prof_run("dgrad", flops, call)
-        return dx
+    d3 = _k3(dil, nd5) if dil is not None else (1, 1, 1)
+    g = _Geom(shape5, co, k3, stride, p3, d3)
+    flops = 2.0 * dy.numel() * ci * g.taps
     img = _cached_image(w, True, n, d, h, wd, k3, stride, p3) if (nd5 and dil is None) else None
     if img is not None:
         ws = _ws(lib.mi_conv3d_direct_workspace_bytes(n, ci), dy.device, "conv")
@@ -730,10 +724,10 @@ def conv_dgrad(dy, w, in_shape, k, stride, pad, res=None, mask=None, dil=None):
             return _cube2_call(lib, dy, w, dx, res, mask, 0, 1, n, ci, ws)
         _prof_run("dgrad", flops, call)
         return dx
-    ws = _ws(lib.mi_convnd_workspace_bytes(n, d, h, wd, ci, co, *k3, stride, *p3), dy.device, "conv")
+    ws = g.workspace(dy.device)
     def call():
-        return L.check(lib.mi_convnd_dgrad_f32(L.ptr(dy), L.ptr(w), L.ptr(dx), L.ptr(res), L.ptr(mask), n, d, h, wd,
-            ci, co, *k3, stride, *p3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_dgrad_f32")
+        return L.check(lib.mi_conv_dgrad_f32(L.ptr(dy), L.ptr(w), L.ptr(dx), L.ptr(res), L.ptr(mask), g.ref, L.ptr(ws), ws.numel(),
+                                             L.stream()), "mi_conv_dgrad_f32")
     _prof_run("dgrad", flops, call)
     return dx
 
@@ -806,15 +800,10 @@ def flush_wgrad_reduces():
     items = DEFERRED_WGRADS
     if not items:
         return
-    import ctypes
-    n = len(items)
-    slabs = (ctypes.c_void_p * n)(*[it[0].data_ptr() for it in items])
-    outs = (ctypes.c_void_p * n)(*[it[1].data_ptr() for it in items])
-    cnt = (ctypes.c_int * n)(*[it[2] for it in items])
-    elems = (ctypes.c_long * n)(*[it[3] for it in items])
-    L.check(L.lib().mi_splitk_reduce_batch(ctypes.cast(slabs, ctypes.c_void_p), ctypes.cast(outs, ctypes.c_void_p),
-                                           ctypes.cast(cnt, ctypes.c_void_p), ctypes.cast(elems, ctypes.c_void_p), n,
-                                           L.stream()), "mi_splitk_reduce_batch")
+    L.check(L.lib().mi_splitk_reduce_batch(L.host_array([it[0].data_ptr() for it in items]), L.host_array([it[1].data_ptr() for it in items]),
+                                           L.host_array([it[2] for it in items], ctypes.c_int),
+                                           L.host_array([it[3] for it in items], ctypes.c_long), len(items), L.stream()),
+            "mi_splitk_reduce_batch")
     del items[:]
 
 
@@ -841,18 +830,16 @@ def _side_or_now(fn, rows):
 
 class _WgradJob:
     """One deferred convolution weight gradient (slab form): callable like the closures next to it in SIDE_WGRADS; jobs of one
-    geometry that are issued together go out as ONE launch (run_wgrad_jobs -> mi_convnd_wgrad_slabs_batch_f32)."""
+    geometry (`geom`: a _Geom) that are issued together go out as ONE launch (run_wgrad_jobs -> mi_conv_wgrad_batch_f32)."""
     __slots__ = ("x", "dy", "tgt", "slab", "geom", "param", "flops")
 
     def __init__(self, x, dy, tgt, slab, geom, param=None, flops=0.0):
         self.x, self.dy, self.tgt, self.slab, self.geom, self.param, self.flops = x, dy, tgt, slab, geom, param, flops
 
     def __call__(self):
-        import ctypes
         splits = ctypes.c_int(0)
-        L.check(L.lib().mi_convnd_wgrad_slabs_f32(L.ptr(self.x), L.ptr(self.dy), L.ptr(self.tgt), *self.geom, L.ptr(self.slab),
-                                                  self.slab.numel(), ctypes.addressof(splits), L.stream()),
-                "mi_convnd_wgrad_slabs_f32")
+        L.check(L.lib().mi_conv_wgrad_f32(L.ptr(self.x), L.ptr(self.dy), L.ptr(self.tgt), self.geom.ref, L.ptr(self.slab),
+                                          self.slab.numel(), ctypes.addressof(splits), L.stream()), "mi_conv_wgrad_f32")
         if splits.value > 1:
             DEFERRED_WGRADS.append((self.slab, self.tgt, int(splits.value), self.tgt.numel()))
 
@@ -906,23 +893,40 @@ def _flush_backward_end():
         DEFERRED_WGRADS = saved
 
 
+def _launch_wgrad_group(jobs):
+    """Up to WGRAD_BATCH_MAX jobs of one geometry and slab size: ONE batched launch or - a single job, or a geometry the library has no
+    batched kernel for - one launch each; split launches leave their slabs registered in DEFERRED_WGRADS."""
+    rc = -3
+    if len(jobs) > 1:
+        splits = ctypes.c_int(0)
+        rc = L.lib().mi_conv_wgrad_batch_f32(L.host_array([j.x.data_ptr() for j in jobs]), L.host_array([j.dy.data_ptr() for j in jobs]),
+                                             L.host_array([j.tgt.data_ptr() for j in jobs]), L.host_array([j.slab.data_ptr() for j in jobs]),
+                                             len(jobs), jobs[0].geom.ref, jobs[0].slab.numel(), ctypes.addressof(splits), L.stream())
+        if rc == 0 and splits.value > 1:
+            for j in jobs:
+                DEFERRED_WGRADS.append((j.slab, j.tgt, int(splits.value), j.tgt.numel()))
+    if rc == -3:                                           # MI_E_UNSUPPORTED (or a single job): one launch each
+        for j in jobs:
+            j()
+    else:
+        L.check(rc, "mi_conv_wgrad_batch_f32")
+
+
 def run_wgrad_jobs(items):
     """Issue the collected weight-gradient launches of a stage on the current stream: convolution jobs of one geometry in
     groups of up to four per launch, everything else (and what the library declines) one by one, in collection order."""
-    import ctypes
     groups, order = {}, []
     for it in items:
         if isinstance(it, _WgradJob) and it.param is not None:
             it.param._mi_wgrad_pending = False
         if isinstance(it, _WgradJob) and WGRAD_BATCH and DEFERRED_WGRADS is not None:
-            key = it.geom + (it.slab.numel(),)
+            key = it.geom.key + (it.slab.numel(),)
             if key not in groups:
                 groups[key] = []
                 order.append(groups[key])
             groups[key].append(it)
         else:
             order.append(it)
-    lib = L.lib()
     if PROFILE is not None:
         _run_wgrad_jobs_profiled(order)
         return
@@ -931,34 +935,12 @@ def run_wgrad_jobs(items):
             it()
             continue
         for i0 in range(0, len(it), WGRAD_BATCH_MAX):
-            jobs = it[i0:i0 + WGRAD_BATCH_MAX]
-            rc = -3
-            if len(jobs) > 1:
-                n = len(jobs)
-                xs = (ctypes.c_void_p * n)(*[j.x.data_ptr() for j in jobs])
-                dys = (ctypes.c_void_p * n)(*[j.dy.data_ptr() for j in jobs])
-                dws = (ctypes.c_void_p * n)(*[j.tgt.data_ptr() for j in jobs])
-                wss = (ctypes.c_void_p * n)(*[j.slab.data_ptr() for j in jobs])
-                splits = ctypes.c_int(0)
-                rc = lib.mi_convnd_wgrad_slabs_batch_f32(ctypes.cast(xs, ctypes.c_void_p), ctypes.cast(dys, ctypes.c_void_p),
-                                                         ctypes.cast(dws, ctypes.c_void_p), ctypes.cast(wss, ctypes.c_void_p), n,
-                                                         *jobs[0].geom, jobs[0].slab.numel(), ctypes.addressof(splits), L.stream())
-                if rc == 0 and splits.value > 1:
-                    for j in jobs:
-                        DEFERRED_WGRADS.append((j.slab, j.tgt, int(splits.value), j.tgt.numel()))
-            if rc == -3:                                   # MI_E_UNSUPPORTED (or a single job): one launch each
-                for j in jobs:
-                    j()
-            else:
-                L.check(rc, "mi_convnd_wgrad_slabs_batch_f32")
+            _launch_wgrad_group(it[i0:i0 + WGRAD_BATCH_MAX])
 
 
 def _run_wgrad_jobs_profiled(order):
     """bench.py's roofline pass: a group's launch + the reduce of its slabs is ONE timed call (what the step launches), with the
     group's algorithmic FLOPs; the slabs are reduced here instead of in the stage's deferred reduce."""
-    import ctypes
-    global DEFERRED_WGRADS
-    lib = L.lib()
     for it in order:
         if not isinstance(it, list):
             if isinstance(it, _WgradJob):
@@ -973,23 +955,7 @@ def _run_wgrad_jobs_profiled(order):
                 global DEFERRED_WGRADS
                 saved, DEFERRED_WGRADS = DEFERRED_WGRADS, []
                 try:
-                    rc = -3
-                    if len(jobs) > 1:
-                        n = len(jobs)
-                        arr = lambda vals: ctypes.cast((ctypes.c_void_p * n)(*vals), ctypes.c_void_p)
-                        keep = [arr([j.x.data_ptr() for j in jobs]), arr([j.dy.data_ptr() for j in jobs]),
-                                arr([j.tgt.data_ptr() for j in jobs]), arr([j.slab.data_ptr() for j in jobs])]
-                        splits = ctypes.c_int(0)
-                        rc = lib.mi_convnd_wgrad_slabs_batch_f32(*keep, n, *jobs[0].geom, jobs[0].slab.numel(), ctypes.addressof(splits),
-                                                                 L.stream())
-                        if rc == 0 and splits.value > 1:
-                            for j in jobs:
-                                DEFERRED_WGRADS.append((j.slab, j.tgt, int(splits.value), j.tgt.numel()))
-                    if rc == -3:
-                        for j in jobs:
-                            j()
-                    else:
-                        L.check(rc, "mi_convnd_wgrad_slabs_batch_f32")
+                    _launch_wgrad_group(jobs)
                     flush_wgrad_reduces()
                 finally:
                     DEFERRED_WGRADS = saved
@@ -1040,11 +1006,13 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
         if acc:
             g.add_(tgt)
         return
-    slab_form = (not acc and (dil is None or tuple(_k3(dil, nd5)) == (1, 1, 1)) and x.is_cuda and
+    d3 = _k3(dil, nd5) if dil is not None else (1, 1, 1)
+    geom = _Geom((n, d, h, wd, ci), co, k3, stride, p3, d3)
+    slab_form = (not acc and d3 == (1, 1, 1) and x.is_cuda and
                  (PROFILE is None or (DEFERRED_WGRADS is not None and SIDE_WGRADS is not None and dy.numel() // co <= SIDE_ROWS_MAX)))
     if slab_form and (DEFERRED_WGRADS is not None or (WGRAD_BATCH and lib.mi_conv3d_direct_usable(n, d, h, wd, ci, co, k3[0], stride, p3[0]) in (1, 2)
                                                       and k3[0] == k3[1] == k3[2] and p3[0] == p3[1] == p3[2])):
-        nbytes = lib.mi_convnd_workspace_bytes(n, d, h, wd, ci, co, *k3, stride, *p3)
+        nbytes = lib.mi_conv_workspace_bytes(geom.ref)
         slab = getattr(param, "_mi_slabs", None)
         if slab is None or slab.numel() < nbytes or slab.device != x.device:
             slab = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)     # lives with the parameter
@@ -1053,26 +1021,18 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
             # (pinned: a captured hipGraph writes and reads the old buffer on every replay - the step engines pin the slabs
             # when they capture; an eager call that needs more space gets a buffer of its own and the graph's stays alive)
         _f32c(x, "x"), _f32c(dy, "dy")
-        job = _WgradJob(x, dy, tgt, slab, (n, d, h, wd, ci, co) + tuple(k3) + (stride,) + tuple(p3), param, flops)
+        job = _WgradJob(x, dy, tgt, slab, geom, param, flops)
         if DEFERRED_WGRADS is not None:
             if _side_or_now(job, dy.numel() // co):
                 param._mi_wgrad_pending = True             # queued: cleared by run_wgrad_jobs (a second contribution before that raises)
             return
         if _defer_to_backward_end(job):                    # plain autograd: layer1's / layer2's weight gradients, batched at the end
             return
-    if dil is not None and tuple(_k3(dil, nd5)) != (1, 1, 1):
-        d3 = _k3(dil, nd5)
-        ws = _ws(lib.mi_convnd_dil_workspace_bytes(n, d, h, wd, ci, co, *k3, *p3, *d3), x.device, "conv")
-        def call():
-            return L.check(lib.mi_convnd_dil_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, d, h, wd, ci, co, *k3,
-                *p3, *d3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_dil_wgrad_f32")
-        _prof_run("wgrad", flops, call)
-    else:
-        ws = _ws(lib.mi_convnd_workspace_bytes(n, d, h, wd, ci, co, *k3, stride, *p3), x.device, "conv")
-        def call():
-            return L.check(lib.mi_convnd_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, d, h, wd, ci, co, *k3, stride,
-                *p3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_wgrad_f32")
-        _prof_run("wgrad", flops, call)
+    ws = geom.workspace(x.device)
+    def call():
+        return L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
+                       "mi_conv_wgrad_f32")
+    _prof_run("wgrad", flops, call)
     if acc:
         g.add_(tgt)
 
@@ -1174,8 +1134,8 @@ class _ConvFn(torch.autograd.Function):
 
 
 def conv_bias_fwd(x, w, bias, k, stride, pad, relu=False, out=None, pool=False):
-    """y = act(conv(x, w) + bias[co]) in one launch (mi_convnd_fwd_bias_f32), inference only: no autograd node.  `out`: a
-    contiguous (N, [D,] Ho, Wo, Co) tensor (or a leading-axis slice of one) that receives the result."""
+    """y = act(conv(x, w) + bias[co]) in one launch (mi_conv_fwd_f32 with the residual read as a bias row), inference only: no
+    autograd node.  `out`: a contiguous (N, [D,] Ho, Wo, Co) tensor (or a leading-axis slice of one) that receives the result."""
     _f32c(x, "x")
     if not _phys_ok(w):
         raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
@@ -1197,10 +1157,10 @@ def conv_bias_fwd(x, w, bias, k, stride, pad, relu=False, out=None, pool=False):
         return _smallk_call(x, w, _f32c(bias, "bias"), relu, taps, out=out)
     if kind:
         return _d32_call(x, w, _f32c(bias, "bias"), relu, kind, out=out)
-    x5 = _as5d(x)
-    n, d, h, wd, ci = x5.shape
+    n, d, h, wd, ci = _as5d(x).shape
     co = w.shape[0]
-    do, ho, wo = _out_dims(x5.shape, k3, stride, p3)
+    g = _Geom((n, d, h, wd, ci), co, k3, stride, p3)
+    do, ho, wo = g.out
     shape = (n, do, ho, wo, co) if nd5 else (n, ho, wo, co)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
@@ -1215,11 +1175,11 @@ def conv_bias_fwd(x, w, bias, k, stride, pad, relu=False, out=None, pool=False):
                                                       L.stream()), "mi_stem2d_fwd_bias_f32")
         _prof_run("fwd", 2.0 * n * do * ho * wo * co * 49, call)
         return out
-    ws = _ws(lib.mi_convnd_workspace_bytes(n, d, h, wd, ci, co, *k3, stride, *p3), x.device, "conv")
+    ws = g.workspace(x.device)
     def call():
-        return L.check(lib.mi_convnd_fwd_bias_f32(L.ptr(x), L.ptr(w), L.ptr(out), L.ptr(_f32c(bias, "bias")), int(relu), n, d, h,
-            wd, ci, co, *k3, stride, *p3, L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_fwd_bias_f32")
-    _prof_run("fwd", 2.0 * n * do * ho * wo * co * ci * k3[0] * k3[1] * k3[2], call)
+        return L.check(lib.mi_conv_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(out), L.ptr(_f32c(bias, "bias")), 1, int(relu), g.ref, L.ptr(ws),
+                                           ws.numel(), L.stream()), "mi_conv_fwd_f32")
+    _prof_run("fwd", 2.0 * n * do * ho * wo * co * ci * g.taps, call)
     return out
 
 
@@ -1471,7 +1431,7 @@ class _LinearFn(torch.autograd.Function):
             lib = L.lib()
             co = w5.shape[0]
             y = torch.empty((m, co), dtype=torch.float32, device=x.device)
-            ws = _ws(lib.mi_conv3d_workspace_bytes(m, 1, 1, 1, ci, co, 1, 1, 0), x.device, "conv")
+            ws = _linear_geom(m, ci, co).workspace(x.device)
             L.check(lib.mi_linear_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), m, ci, co, L.ptr(ws), ws.numel(),
                                           L.stream()), "mi_linear_fwd_f32")
         else:
@@ -1495,9 +1455,10 @@ class _LinearFn(torch.autograd.Function):
             g, acc = _grad_target(mod.weight)
             tgt = torch.empty_like(g) if acc else g
             def launch(g=g, acc=acc, tgt=tgt):          # (bound now: the names are reused for the bias below)
-                ws = _ws(lib.mi_conv3d_workspace_bytes(m, 1, 1, 1, ci, co, 1, 1, 0), x.device, "conv")
-                L.check(lib.mi_conv3d_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), m, 1, 1, 1, ci, co, 1, 1, 0,
-                                                L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_wgrad_f32")
+                geom = _linear_geom(m, ci, co)
+                ws = geom.workspace(x.device)
+                L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
+                        "mi_conv_wgrad_f32")
                 if acc:
                     g.add_(tgt)
             _side_or_now(launch, m)
@@ -2446,9 +2407,10 @@ class _ConvT2x2Fn(torch.autograd.Function):
             g, acc = _grad_target(mod.weight)
             tgt = torch.empty_like(g) if acc else g
             lib = L.lib()
-            ws = _ws(lib.mi_convnd_workspace_bytes(n, 1, h, wd, ci, 4 * co, 1, 1, 1, 1, 0, 0, 0), x.device, "conv")
-            L.check(lib.mi_convnd_wgrad_f32(L.ptr(x), L.ptr(dt), L.ptr(tgt), n, 1, h, wd, ci, 4 * co, 1, 1, 1, 1, 0, 0, 0,
-                                            L.ptr(ws), ws.numel(), L.stream()), "mi_convnd_wgrad_f32")
+            geom = _Geom((n, 1, h, wd, ci), 4 * co, (1, 1, 1), 1, (0, 0, 0))
+            ws = geom.workspace(x.device)
+            L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dt), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
+                    "mi_conv_wgrad_f32")
             if acc:
                 g.add_(tgt)
         dx = conv_dgrad(dt, mod.gemm_view(), x.shape, 1, 1, 0) if ctx.x_needs_grad else None

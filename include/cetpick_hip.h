@@ -241,30 +241,53 @@ int mi_semi_pairs(const mi_vol_desc* tomos, const mi_vol_desc* labels, int n_tom
  * weights [tap][Cin][Cout] with tap = (kd*k + kh)*k + kw.
  * ------------------------------------------------------------------------------------------ */
 
-/* nn.Conv3d (cubic kernel k, stride, pad, no bias) / nn.Linear (k=1, D=H=W=1) as implicit GEMM
- * on the matrix cores: f32 operands, f32 accumulation.  The environment variable MI_CONV_ARITH selects how the f32
+/* One convolution problem, passed by pointer: input (N, Di, Hi, Wi, Ci) -> Co channels, window (kd, kh, kw), one stride for
+ * the three axes, zero padding (pd, ph, pw), dilation (dd, dh, dw) (1 = none; a dilated window needs stride 1 and Ci != 1).
+ * Output extent per axis = (in + 2 * pad - dil * (k - 1) - 1) / stride + 1.  Window <= 7 per axis, stride 1 or 2,
+ * Ci % 16 == 0 (or Ci == 1), Co % 16 == 0. */
+typedef struct mi_conv_geom {
+    int N, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pd, ph, pw, dd, dh, dw;
+} mi_conv_geom;
+
+/* nn.Conv3d / nn.Conv2d (D = 1, kd = 1, pd = 0 on (N,1,H,W,C) activations) / nn.Linear (1x1x1 window, D = H = W = 1), no bias
+ * of their own, as implicit GEMM on the matrix cores: f32 operands, f32 accumulation; weights [kd][kh][kw][Cin][Cout].  The
+ * environment variable MI_CONV_ARITH selects how the f32
  * products are formed: "bf16x3" (default) - every operand element is cut exactly into three bf16 values and the six
  * products of weight <= 2 are accumulated by v_mfma_f32_32x32x16_bf16 (f32-equivalent: the dropped terms are below one
  * f32 rounding; non-finite inputs give NaN where an f32 multiply would give Inf) - or "f32" - v_mfma_f32_32x32x2_f32,
  * bit-for-bit an fmaf chain.  Replaces models/networks/moco_encoder_3d.py:40-84 (conv3x3x3,
- * BasicBlock), :163-169 (7x7x7 stem, Ci == 1), :183, :189, :198-205 (feature conv, fc, proj).
- * Ci % 16 == 0 (or Ci == 1), Co % 16 == 0.
- *   fwd:   y  = act(conv(x, w) + res)                 res may be NULL, relu 0/1
+ * BasicBlock), :163-169 (7x7x7 stem, Ci == 1), :183, :189, :198-205 (feature conv, fc, proj), the nn.Conv2d of the 2-D
+ * encoder (models/networks/simsiam_model_2d.py:25-28, 473-502, 617-661) and the dilated 3-D head of the detector
+ * (kernel (3,3,3), dilation (1,4,4), padding (1,4,4): models/networks/unet_small.py:38-41).
+ *   fwd:   y  = act(conv(x, w) + res)                 res may be NULL, relu 0/1.  res_is_bias != 0: res is ONE row of Co
+ *          values (a bias; NULL is MI_E_ARG) - the reference's conv -> BatchNorm(eval) -> ReLU triple at inference
+ *          (models/networks/unet.py:198-249,319-399) once the caller has folded the BatchNorm's scale into w and its shift into bias
  *   dgrad: dx = (conv_transpose(dy, w) + res) * (mask > 0)     res, mask may be NULL
- *   wgrad: dw = sum over output voxels
- * `ws` holds split-K slabs (mi_conv3d_workspace_bytes covers all three); a NULL / short ws
- * silently selects the unsplit schedule (same values up to fp32 summation order). */
-size_t mi_conv3d_workspace_bytes(int N, int Di, int Hi, int Wi, int Ci, int Co, int k, int stride,
-                                 int pad);
-int mi_conv3d_fwd_f32(const float* x, const float* w, float* y, const float* res, int relu, int N,
-                      int Di, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, void* ws,
-                      size_t ws_bytes, mi_stream_t stream);
-int mi_conv3d_dgrad_f32(const float* dy, const float* w, float* dx, const float* res,
-                        const float* mask, int N, int Di, int Hi, int Wi, int Ci, int Co, int k,
-                        int stride, int pad, void* ws, size_t ws_bytes, mi_stream_t stream);
-int mi_conv3d_wgrad_f32(const float* x, const float* dy, float* dw, int N, int Di, int Hi, int Wi,
-                        int Ci, int Co, int k, int stride, int pad, void* ws, size_t ws_bytes,
-                        mi_stream_t stream);
+ *   wgrad: dw = sum over output voxels.  splits_out == NULL: dw is final.  Otherwise the split-K reduction is left to the
+ *          caller: *splits_out = 1 -> dw is final; > 1 -> `ws` holds that many slabs of Co*Ci*kd*kh*kw floats (slab s at
+ *          ws + s * that many floats) and dw is untouched.  mi_splitk_reduce_batch sums the slabs of n such launches
+ *          (outs[i] <- sum of n_slabs[i] slabs at slabs[i], out_elems[i] floats each, a multiple of 4) in one launch per 24
+ *          of them: one reduce for the weight gradients of a whole backward pass.  Its pointer / count arrays are HOST
+ *          arrays (read during the call).
+ * `ws` holds split-K slabs and the weight images of the direct kernels (mi_conv_workspace_bytes covers all three passes; 0 = a
+ * geometry the entries refuse); a NULL / short ws silently selects the unsplit schedule (same values up to fp32 summation order). */
+size_t mi_conv_workspace_bytes(const mi_conv_geom* g);
+int mi_conv_fwd_f32(const float* x, const float* w, float* y, const float* res, int res_is_bias, int relu,
+                    const mi_conv_geom* g, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_conv_dgrad_f32(const float* dy, const float* w, float* dx, const float* res, const float* mask,
+                      const mi_conv_geom* g, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_conv_wgrad_f32(const float* x, const float* dy, float* dw, const mi_conv_geom* g, void* ws, size_t ws_bytes,
+                      int* splits_out, mi_stream_t stream);
+int mi_splitk_reduce_batch(const void* const* slabs, void* const* outs, const int* n_slabs, const long* out_elems, int n,
+                           mi_stream_t stream);
+/* Round 5: nb (2..4) weight gradients of ONE geometry in ONE launch - the weight gradients of a residual stage exist together
+ * once loss.backward() (trains/base_trainer.py:497) has left the stage (moco_encoder_3d.py:55-84: layer1's four, layer2's and
+ * layer3's three equal convolutions), and a launch's fixed costs are a third of each when they run one by one.  Problem i reads
+ * xs[i] / dys[i] and leaves *splits_out slabs in wss[i] (each workspace ws_bytes long; > 1: mi_splitk_reduce_batch sums them into
+ * dws[i]) or, *splits_out == 1, the final gradient in dws[i].  The pointer arrays are HOST arrays.  MI_E_UNSUPPORTED: no batched
+ * kernel for this geometry / nb (or MI_NO_WGRAD_BATCH=1) - issue nb single calls. */
+int mi_conv_wgrad_batch_f32(const float* const* xs, const float* const* dys, float* const* dws, void* const* wss, int nb,
+                            const mi_conv_geom* g, size_t ws_bytes, int* splits_out, mi_stream_t stream);
 
 /* nn.Linear (+ bias) followed by training-mode nn.BatchNorm1d (+ ReLU) in one launch (the projection MLP,
  * models/networks/moco_encoder_3d.py:238-255): xlin (M, Co) = x W + bias (kept for the backward), y = act(bn(xlin)),
@@ -284,7 +307,7 @@ int mi_linear_stats_fwd_f32(const float* x, const float* w, const float* bias, f
 /* conv1 + the batch statistics of bn1 in one pass (models/networks/moco_encoder_3d.py:170-176, 326-328): the 7^3
  * stride-2 single-channel stem convolution, with sums[0..Co) = column sums of y and sums[Co..2Co) = column sums of y^2
  * (device doubles; what mi_bn_stats(y) would produce) taken from the output tiles while they are in registers.
- * MI_E_UNSUPPORTED where the stem kernel does not apply (shape, Co != 64, MI_CONV_ARITH=f32): run mi_conv3d_fwd_f32 and
+ * MI_E_UNSUPPORTED where the stem kernel does not apply (shape, Co != 64, MI_CONV_ARITH=f32): run mi_conv_fwd_f32 and
  * mi_bn_stats instead.  Workspace: mi_conv3d_stem_stats_workspace_bytes (0 = unsupported shape). */
 size_t mi_conv3d_stem_stats_workspace_bytes(int N, int Di, int Hi, int Wi, int Co);
 int mi_conv3d_stem_stats_f32(const float* x, const float* w, float* y, int N, int Di, int Hi, int Wi, int Co,
@@ -292,30 +315,16 @@ int mi_conv3d_stem_stats_f32(const float* x, const float* w, float* y, int N, in
 
 /* nn.Linear (models/networks/moco_encoder_3d.py:183-236: fc and the projection head): y[M][Co] = x[M][Ci] . W + bias with
  * W in kernel layout [Ci][Co]; bias (Co values, may be NULL) is added in the epilogue of the 1x1x1 convolution launch.
- * Workspace as mi_conv3d_workspace_bytes(M, 1, 1, 1, Ci, Co, 1, 1, 0). */
+ * Workspace as mi_conv_workspace_bytes of the geometry {M, 1, 1, 1, Ci, Co, 1, 1, 1, 1, 0, 0, 0, 1, 1, 1}. */
 int mi_linear_fwd_f32(const float* x, const float* w, const float* bias, float* y, int M, int Ci, int Co, void* ws,
                       size_t ws_bytes, mi_stream_t stream);
 
-/* Same kernels with a per-axis window (kd,kh,kw) and zero padding (pd,ph,pw); weights
- * [kd][kh][kw][Cin][Cout].  nn.Conv2d of the 2-D encoder (models/networks/simsiam_model_2d.py:25-28,
- * 473-502, 617-661) is the D = 1, kd = 1, pd = 0 case on (N,1,H,W,C) activations. */
-size_t mi_convnd_workspace_bytes(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw,
-                                 int stride, int pd, int ph, int pw);
-int mi_convnd_fwd_f32(const float* x, const float* w, float* y, const float* res, int relu, int N,
-                      int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride, int pd,
-                      int ph, int pw, void* ws, size_t ws_bytes, mi_stream_t stream);
-/* y = act(conv(x, w) + bias[Co]): mi_convnd_fwd_f32 with the residual read as one row of Co values (a bias).  Replaces the
- * reference's conv -> BatchNorm(eval) -> ReLU triple at inference (models/networks/unet.py:198-249,319-399) once the caller has
- * folded the BatchNorm's scale into w and its shift into bias. */
-int mi_convnd_fwd_bias_f32(const float* x, const float* w, float* y, const float* bias, int relu, int N, int Di,
-                           int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride, int pd, int ph,
-                           int pw, void* ws, size_t ws_bytes, mi_stream_t stream);
 /* y = act(conv2d(x, w, 7 x 7, stride 2, padding 3) + bias): ONE input channel, 16 output channels, x (N, H, W), w in kernel layout
  * [7][7][1][16], bias[16] or NULL, y (N, Ho, Wo, 16) channels-last with Ho = (H - 1) / 2 + 1 (models/networks/unet_small.py:35: the
  * detector's first layer, with its evaluation-mode BatchNorm folded in by the caller). */
 int mi_stem2d_fwd_bias_f32(const float* x, const float* w, const float* bias, float* y, int relu, int N, int H, int W,
                            mi_stream_t stream);
-/* Forward convolutions with a short reduction, inference path (round 4; no gradient form - training keeps mi_convnd_*): 1 x 1
+/* Forward convolutions with a short reduction, inference path (round 4; no gradient form - training keeps mi_conv_*_f32): 1 x 1
  * (ntaps 1) or (3, 1, 1) with padding (1, 0, 0) (ntaps 3: `plane` = H * W rows per z-plane, `D` planes per sample) on channels-last rows
  * x (M, Ci) -> y (M, Co) = act(x . W + bias), bias may be NULL.  Ci a multiple of 16, Co of 32.  `img` (mi_smallk_image_bytes(ntaps * Ci, Co)
  * bytes) is written by mi_smallk_prep from the kernel-layout weights [tap][Ci][Co] once per set of weights.  Replaces the implicit GEMM
@@ -330,38 +339,11 @@ int mi_smallk_fwd_f32(const float* x, const void* img, const float* bias, float*
  * w_hm: [3][Ci][K] f32.  M = N D plane rows.  Inference only. */
 int mi_smallk_heads_fwd_f32(const float* x, const void* img, float* y_proj, const float* w_hm, float* y_hm, int k_hm, long M, int Ci,
                             long plane, int D, mi_stream_t stream);
-int mi_convnd_dgrad_f32(const float* dy, const float* w, float* dx, const float* res,
-                        const float* mask, int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh,
-                        int kw, int stride, int pd, int ph, int pw, void* ws, size_t ws_bytes,
-                        mi_stream_t stream);
-int mi_convnd_wgrad_f32(const float* x, const float* dy, float* dw, int N, int Di, int Hi, int Wi,
-                        int Ci, int Co, int kd, int kh, int kw, int stride, int pd, int ph, int pw,
-                        void* ws, size_t ws_bytes, mi_stream_t stream);
-/* The weight gradient with its split-K reduction left to the caller: *splits_out = 1 -> dw is final; > 1 -> `ws` holds
- * that many slabs of Co*Ci*kd*kh*kw floats (slab s at ws + s * that many floats) and dw is untouched.
- * mi_splitk_reduce_batch sums the slabs of n such launches (outs[i] <- sum of n_slabs[i] slabs at slabs[i], out_elems[i]
- * floats each, a multiple of 4) in one launch per 24 of them: one reduce for the weight gradients of a whole backward
- * pass.  The pointer / count arrays are HOST arrays (read during the call). */
-int mi_convnd_wgrad_slabs_f32(const float* x, const float* dy, float* dw, int N, int Di, int Hi, int Wi, int Ci, int Co,
-                              int kd, int kh, int kw, int stride, int pd, int ph, int pw, void* ws, size_t ws_bytes,
-                              int* splits_out, mi_stream_t stream);
-int mi_splitk_reduce_batch(const void* const* slabs, void* const* outs, const int* n_slabs, const long* out_elems, int n,
-                           mi_stream_t stream);
-/* Round 5: nb (2..4) weight gradients of ONE geometry in ONE launch - the weight gradients of a residual stage exist together
- * once loss.backward() (trains/base_trainer.py:497) has left the stage (moco_encoder_3d.py:55-84: layer1's four, layer2's and
- * layer3's three equal convolutions), and a launch's fixed costs are a third of each when they run one by one.  Problem i reads
- * xs[i] / dys[i] and leaves *splits_out slabs in wss[i] (each workspace ws_bytes long; > 1: mi_splitk_reduce_batch sums them into
- * dws[i]) or, *splits_out == 1, the final gradient in dws[i].  The pointer arrays are HOST arrays.  MI_E_UNSUPPORTED: no batched
- * kernel for this geometry / nb (or MI_NO_WGRAD_BATCH=1) - issue nb single calls. */
-int mi_convnd_wgrad_slabs_batch_f32(const float* const* xs, const float* const* dys, float* const* dws, void* const* wss, int nb,
-                                    int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride, int pd,
-                                    int ph, int pw, size_t ws_bytes, int* splits_out, mi_stream_t stream);
-
 /* Patch-resident direct kernels for the 3^3 / stride 1 / padding 1 convolutions of the MoCo-3D encoder's residual layers
  * (models/networks/moco_encoder_3d.py:55-84,170-171), forward and data gradient, bf16x3 arithmetic:
  *   channels 64 : nn.Conv3d(64, 64, 3, 1, 1) on (N, D, 8, 8, 64), D even                  (layer1)
  *   channels 128: nn.Conv3d(128, 128, 3, 1, 1) on (N, 4, 4, 4, 128)                        (layer2)
- * mi_conv3d_fwd_f32 / mi_conv3d_dgrad_f32 (and the mi_convnd_* forms) take them by themselves for such shapes and build
+ * mi_conv_fwd_f32 / mi_conv_dgrad_f32 take them by themselves for such shapes and build
  * the weight image in `ws` on every call (MI_CONV_NO_DIRECT=1 keeps the implicit GEMM).  A caller that knows when the
  * weights change keeps the images instead: mi_conv3d_direct_prep cuts n weight tensors ([tap][Cin][Cout] f32, channels[i]
  * = 64 or 128) into n images of mi_conv3d_direct_wimg_bytes(channels[i]) bytes in one launch per channel count (dgrad[i]
@@ -414,7 +396,7 @@ int mi_conv2d_stem3_wgrad_f32(const float* x, const float* dy, float* dw, int N,
  * the last of the four reduction quarters of an output tile to arrive sums them - in a fixed order - and applies the epilogue):
  *   dgrad = 0: out = act(conv(a, w) + res)                      a = x (N, 2, 2, 2, C),  w = [27][Cin][Cout] f32, mask NULL
  *   dgrad = 1: out = (conv_transpose(a, w) + res) * (mask > 0)  a = dy, relu 0
- * mi_conv3d_fwd_f32 / mi_conv3d_dgrad_f32 take such shapes too (same kernel, partial sums + a reduce launch: their `ws` has no
+ * mi_conv_fwd_f32 / mi_conv_dgrad_f32 take such shapes too (same kernel, partial sums + a reduce launch: their `ws` has no
  * state).  `ws` here: mi_conv3d_cube2_workspace_bytes(N, C) bytes OWNED BY ONE STREAM whose first 16 KiB (arrival counters) are
  * ZERO before the first call; every completed call leaves them zero.  MI_E_UNSUPPORTED for other shapes
  * (mi_conv3d_cube2_usable). */
@@ -422,15 +404,6 @@ size_t mi_conv3d_cube2_workspace_bytes(int N, int C);
 int mi_conv3d_cube2_usable(int N, int Di, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad);
 int mi_conv3d_cube2_f32(const float* a, const float* w, float* out, const float* res, const float* mask, int relu, int dgrad,
                         int N, int C, void* ws, size_t ws_bytes, mi_stream_t stream);
-
-/* Dilated windows, stride 1 (kernel (3,3,3), dilation (1,4,4), padding (1,4,4): the 3-D head of the detector
- * network, models/networks/unet_small.py:38-41).  Same contract as mi_convnd_*; output extent per axis
- * = in + 2*pad - dil*(k-1). */
-size_t mi_convnd_dil_workspace_bytes(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw,
-                                     int pd, int ph, int pw, int dd, int dh, int dw);
-int mi_convnd_dil_fwd_f32(const float* x, const float* w, float* y, const float* res, int relu, int N, int Di,
-                          int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int pd, int ph, int pw,
-                          int dd, int dh, int dw, void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* Patch-resident direct convolution to 32 output channels, forward / inference (conv_d32.hip): the detector's
  * Conv2d(32|64, 32, 3, padding=1) layers with their BatchNorm folded into weights + bias
@@ -447,7 +420,6 @@ int mi_conv_d32_prep(const float* w, void* img, int Ci, int ntap, mi_stream_t st
  * the 128 x 128 level of the U-Net, unet.py:198-249): image [chunk][tap][column half][plane][lane]; forward through
  * mi_conv_d32_fwd_f32(..., kind = 3) with y (N, D, H, W, 64).  MI_NO_D64=1 keeps the implicit GEMM. */
 size_t mi_conv_d64_image_bytes(int Ci, int ntap);
-int mi_conv_d64_prep(const float* w, void* img, int Ci, int ntap, mi_stream_t stream);
 /* Co = 64, 128 or 256 (kind 3 too): one image per 64-column block - img holds (Co / 64) x mi_conv_d64_image_bytes(Ci, 9) bytes -,
  * a workgroup per tile and block; y (N, D, H, W, Co).  MI_NO_D64_WIDE=1 keeps Co > 64 on the implicit GEMM. */
 int mi_conv_d64_prep_co(const float* w, void* img, int Ci, int Co, int ntap, mi_stream_t stream);
@@ -481,14 +453,6 @@ int mi_conv_d64_fwd_f32(const float* x, const void* wimg, const float* bias, flo
                         int Co, mi_stream_t stream);
 int mi_conv_d32_fwd_f32(const float* x, const void* wimg, const float* bias, float* y, int relu, int N, int D, int H, int W,
                         int Ci, int kind, mi_stream_t stream);
-int mi_convnd_dil_dgrad_f32(const float* dy, const float* w, float* dx, const float* res, const float* mask,
-                            int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int pd,
-                            int ph, int pw, int dd, int dh, int dw, void* ws, size_t ws_bytes,
-                            mi_stream_t stream);
-int mi_convnd_dil_wgrad_f32(const float* x, const float* dy, float* dw_out, int N, int Di, int Hi, int Wi,
-                            int Ci, int Co, int kd, int kh, int kw, int pd, int ph, int pw, int dd, int dh,
-                            int dw, void* ws, size_t ws_bytes, mi_stream_t stream);
-
 /* ------------------------------------------------------------------------------------------
  * Detector network glue (models/networks/unet.py, unet_small.py), channels-last.
  * ------------------------------------------------------------------------------------------ */
@@ -499,7 +463,7 @@ int mi_maxpool2d_ceil_fwd(const float* x, float* y, uint8_t* argmax, int N, int 
 int mi_maxpool2d_ceil_bwd(const float* dy, const uint8_t* argmax, float* dx, int N, int Hi, int Wi, int C,
                           int k, mi_stream_t stream);
 /* nn.ConvTranspose2d(Ci, Co, 2, stride=2) (unet.py:155-160) = 1x1 conv to 4*Co columns [(a*2+b)*Co + co]
- * (mi_convnd_fwd_f32) + this shuffle: y[n][2h+a][2w+b][co] = t[n][h][w][(a*2+b)*Co+co] + bias[co], cropped to
+ * (mi_conv_fwd_f32) + this shuffle: y[n][2h+a][2w+b][co] = t[n][h][w][(a*2+b)*Co+co] + bias[co], cropped to
  * (Ho, Wo) <= (2H, 2W) (`autocrop`, unet.py:253-266).  bwd: the inverse scatter (zeros in the cropped rim). */
 int mi_shuffle2x2_fwd(const float* t, const float* bias, float* y, int N, int H, int W, int Co, int Ho, int Wo,
                       mi_stream_t stream);
@@ -633,11 +597,8 @@ int mi_moco_logits_bwd(const float* dlogits, const float* k, const float* queue,
 int mi_rowdot_mean_fwd(const float* a, const float* b, float* out, int B, int C, mi_stream_t stream);
 int mi_rowdot_mean_bwd(const float* b, const float* grad_out, float* da, int B, int C, mi_stream_t stream);
 int mi_column_std_mean(const float* x, float* out, int B, int C, mi_stream_t stream);
-/* nn.CrossEntropyLoss against label 0 (trains/tomo_moco_trainer.py:52,73; models/moco.py:141):
- * loss = mean_b(logsumexp(l_b) - l_b[0]); dlogits = grad_scale*(softmax - onehot0)/B (may be NULL). */
-int mi_ce_label0(const float* logits, float* loss, float* row_loss, float* dlogits, int B, int n,
-                 float grad_scale, mi_stream_t stream);
-/* The same loss in ONE launch (a workgroup per row; the last one to finish takes the mean, in row order), row_loss[B] and
+/* nn.CrossEntropyLoss against label 0 (trains/tomo_moco_trainer.py:52,73; models/moco.py:141): loss = mean_b(logsumexp(l_b) - l_b[0])
+ * in ONE launch (a workgroup per row; the last one to finish takes the mean, in row order), row_loss[B] and
  * row_lse[B] scratch / kept for the backward pass; the backward reads the upstream gradient from the device (no host
  * value, no extra scaling launch): dlogits = grad_loss * (softmax - onehot0) / B.
  * counter: the arrival counter of the "last workgroup" - ONE 4-byte word owned by the caller, zero before the first call and
@@ -654,14 +615,14 @@ int mi_ce_label0_bwd(const float* logits, const float* row_lse, const float* gra
  * dh / dout: (N, Gi/2, Gi/2, Gi/2, Co); w: [27][Ci][Co], w_ds: [Ci][Co] (kernel layouts); dout and w_ds are given together or
  * both NULL; res / mask (shape of dx) may be NULL.  `ws`: mi_conv3d_s2_dgrad_workspace_bytes(Ci, Co) bytes - the call cuts the
  * weight images into it.  mi_conv3d_s2_dgrad_usable: 1 for the three shapes above (bf16x3 arithmetic), else 0 (the caller keeps
- * mi_convnd_dgrad_f32). */
+ * mi_conv_dgrad_f32). */
 int mi_conv3d_s2_dgrad_usable(int N, int Gi, int Ci, int Co);
 size_t mi_conv3d_s2_dgrad_workspace_bytes(int Ci, int Co);
 int mi_conv3d_s2_dgrad_f32(const float* dh, const float* dout, const float* w, const float* w_ds, float* dx, const float* res,
                            const float* mask, int N, int Gi, int Ci, int Co, void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* Forward of the same block front in one launch (csrc/conv_s2.hip): hmid (N, Gi/2.., Co) = relu(conv3d(x; w [27][Ci][Co], k 3,
- * stride 2, pad 1)) and the 1x1 stride-2 shortcut r (N, Gi/2.., Co) = conv3d(x; w_ds [Ci][Co]) - replaces two mi_conv3d_fwd_f32
+ * stride 2, pad 1)) and the 1x1 stride-2 shortcut r (N, Gi/2.., Co) = conv3d(x; w_ds [Ci][Co]) - replaces two mi_conv_fwd_f32
  * calls (models/networks/moco_encoder_3d.py:66-69,78-79: conv1 + relu, downsample).  `ws`: mi_conv3d_s2_fwd_workspace_bytes(Ci, Co)
  * bytes - the call cuts the weight image into it.  mi_conv3d_s2_fwd_usable: 1 for the two encoder shapes, else 0. */
 int mi_conv3d_s2_fwd_usable(int N, int Gi, int Ci, int Co);
@@ -731,12 +692,10 @@ int mi_mse_loss_bwd(const float* a, const float* b, long n, const double* sums, 
  * `logits_max_all.detach()`). */
 int mi_ucl_rowsums_fwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, float* rowmax,
                        float* s_all, float* s_pos, float* s_other, float* e_pair, mi_stream_t stream);
-int mi_ucl_rowsums_bwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const float* rowmax,
-                       const float* g_all, const float* g_pos, const float* g_other, const float* g_pair,
-                       float* dfeat, mi_stream_t stream);
-/* Round 6: the same gradient with both terms of a similarity tile formed at once (S is symmetric: one product, one contraction - what
- * mi_ucl_rowsums_bwd does too, MI_UCL_BWD_SPLIT=1 for the two launches of rounds 2-5) and, where the row maxima lie within 2^16 of each
- * other - always for L2-normalised features - ONE exponential per similarity; decided on the device from `range` (2 floats of scratch). */
+/* The gradient forms both terms of a similarity tile at once (S is symmetric: one product, one contraction; MI_UCL_BWD_SPLIT=1: the two
+ * launches of rounds 2-5) and, where the row maxima lie within 2^16 of each other - always for L2-normalised features - takes ONE
+ * exponential per similarity; decided on the device from `range` (2 floats of scratch; NULL, dim 64 or MI_UCL_BWD_TWO_EXP=1: the
+ * two-exponential form). */
 int mi_ucl_rowsums_bwd_ranged(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const float* rowmax,
                               const float* g_all, const float* g_pos, const float* g_other, const float* g_pair, float* dfeat,
                               float* range, mi_stream_t stream);

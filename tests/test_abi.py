@@ -14,6 +14,18 @@ def _header_symbols():
     return sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", txt)))
 
 
+def _header_geom_fields():
+    """field names of `mi_conv_geom`, in the header's order (every one an int)"""
+    txt = open(os.path.join(REPO, "include", "cetpick_hip.h")).read()
+    body = re.search(r"typedef struct mi_conv_geom \{(.*?)\} mi_conv_geom;", txt, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        assert decl.startswith("int "), decl
+        fields += [f.strip() for f in decl[4:].split(",")]
+    return fields
+
+
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as ge
     ge.build()
@@ -24,8 +36,31 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(L, s), "missing export " + s
     assert set(syms) == set(_lib.SIGNATURES), (set(syms) ^ set(_lib.SIGNATURES))
-    assert L.mi_abi_version() >= 1
+    assert L.mi_abi_version() == 4
     assert L.mi_build_arch() == b"gfx950"
+
+
+def test_conv_geom_struct_matches_header():
+    import ctypes
+    from cet_pick_amd import _lib
+    fields = _header_geom_fields()
+    assert len(fields) == 16
+    assert [f for f, _ in _lib.ConvGeom._fields_] == fields
+    assert all(t is ctypes.c_int for _, t in _lib.ConvGeom._fields_)
+    assert ctypes.sizeof(_lib.ConvGeom) == 16 * 4
+
+
+def test_conv_workspace_bytes_refuses_bad_geometries():
+    """mi_conv_workspace_bytes needs no device: 0 for a geometry the convolution entries refuse, a size otherwise."""
+    import __graft_entry__ as ge
+    ge.build()
+    from cet_pick_amd import _lib
+    size = _lib.lib().mi_conv_workspace_bytes
+    #                      N  D  H   W   Ci  Co  window   s  padding  dilation
+    assert size(_lib.ConvGeom(1, 6, 20, 24, 32, 32, 3, 3, 3, 2, 1, 4, 4, 1, 4, 4)) == 0        # dilated and stride 2
+    assert size(_lib.ConvGeom(1, 8, 8, 8, 8, 16, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1)) == 0           # Ci = 8
+    assert size(_lib.ConvGeom(1, 6, 20, 24, 32, 32, 3, 3, 3, 1, 1, 4, 4, 1, 4, 4)) > 0
+    assert size(_lib.ConvGeom(64, 8, 8, 8, 64, 64, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1)) > 0
 
 
 def test_product_path_has_no_cpu_fallback():

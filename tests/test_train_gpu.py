@@ -932,7 +932,7 @@ def test_pair_weight_gradient_forms_match_float64(case, monkeypatch):
                                             ((6, 16, 64, 64, 3, 1), 2, "single:direct3_wgrad (8 x 8 tiles)"), ((16, 8, 128, 128, 3, 1), 3, "single:direct3_wgrad (128 channels)")])
 def test_batched_weight_gradients_against_single_launches(case, nb, family, monkeypatch):
     """Round 5: the weight gradients of a stage's equal convolutions in ONE launch (hipops.run_wgrad_jobs ->
-    mi_convnd_wgrad_slabs_batch_f32; layer1's four on direct3_wgrad_kernel, layer2's three on the implicit GEMM, layer3's on
+    mi_conv_wgrad_batch_f32; layer1's four on direct3_wgrad_kernel, layer2's three on the implicit GEMM, layer3's on
     pair_wgrad_kernel) against one launch per convolution.  Implicit GEMM and pair_wgrad: same chains, same slabs, same reduce -
     EQUAL BIT FOR BIT.  direct3_wgrad cuts a batched problem into 7 chains per (dz, dy) pair instead of 28 (that is where the time
     goes): equal to float64 within the single launch's bound, and a problem's gradient does not depend on its neighbours in the

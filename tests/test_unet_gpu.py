@@ -39,14 +39,13 @@ def test_dilated_conv_fwd_dgrad_wgrad(shape, k, pad, dil):
     np.testing.assert_allclose(_cf(got).numpy(), y.detach().numpy(), rtol=1e-4, atol=1e-4)
     lib = L.lib()
     xc, dyc = _cl(x.detach()), _cl(dy)
-    ws = L.workspace(lib.mi_convnd_dil_workspace_bytes(n, d, h, w, ci, co, *k, *pad, *dil), xc.device, "conv")
+    geom = L.ConvGeom(n, d, h, w, ci, co, *k, 1, *pad, *dil)
+    ws = L.workspace(lib.mi_conv_workspace_bytes(geom), xc.device, "conv")
     dx = torch.empty_like(xc)
-    L.check(lib.mi_convnd_dil_dgrad_f32(L.ptr(dyc), L.ptr(wk), L.ptr(dx), None, None, n, d, h, w, ci, co, *k, *pad, *dil,
-                                        L.ptr(ws), ws.numel(), L.stream()), "dgrad")
+    L.check(lib.mi_conv_dgrad_f32(L.ptr(dyc), L.ptr(wk), L.ptr(dx), None, None, geom, L.ptr(ws), ws.numel(), L.stream()), "dgrad")
     np.testing.assert_allclose(_cf(dx).numpy(), x.grad.numpy(), rtol=1e-4, atol=2e-4)
     dw = torch.empty(k[0], k[1], k[2], ci, co, device="cuda")
-    L.check(lib.mi_convnd_dil_wgrad_f32(L.ptr(xc), L.ptr(dyc), L.ptr(dw), n, d, h, w, ci, co, *k, *pad, *dil,
-                                        L.ptr(ws), ws.numel(), L.stream()), "wgrad")
+    L.check(lib.mi_conv_wgrad_f32(L.ptr(xc), L.ptr(dyc), L.ptr(dw), geom, L.ptr(ws), ws.numel(), None, L.stream()), "wgrad")
     ref = wt.grad.permute(2, 3, 4, 1, 0).numpy()
     np.testing.assert_allclose(dw.cpu().numpy(), ref, rtol=1e-3, atol=1e-3 * np.abs(ref).max())
 
@@ -498,7 +497,7 @@ def test_unet_inference_in_slice_chunks_matches_whole_volume_and_oracle():
 
 def test_unet_inference_with_folded_batchnorm_equals_the_unfolded_passes(monkeypatch):
     """Round 4: at inference evaluation-mode BatchNorm is folded into the convolution in front of it (scaled weights + a bias and
-    ReLU epilogue: mi_convnd_fwd_bias_f32) and the last 1 x 1 convolution adds its bias and writes its chunk of the feature volume
+    ReLU epilogue: mi_conv_fwd_f32 with res_is_bias) and the last 1 x 1 convolution adds its bias and writes its chunk of the feature volume
     itself.  Against the unfolded sequence (conv, bn_apply, bias_add, chunk copy: hipops.FOLD_EVAL_BN off) on a network whose
     running statistics are not the identity, chunked and whole; and the folded weights follow an in-place change of the
     statistics (models/networks/unet.py:198-249,319-399, unet_small.py:30-97)."""
