@@ -124,6 +124,32 @@ def _grad_target(param):
     return g, True
 
 
+class _GradInto:
+    """Where the launch that computes `param`'s gradient writes: `with _GradInto(param) as tgt:` around the launch.  The target is
+    decided when the object is MADE (_grad_target: .grad itself, the second arena or, for a gradient that accumulates, a temporary) -
+    a launch deferred through _side_or_now makes the object where autograd reaches the layer and enters it inside the closure;
+    leaving the block adds the temporary onto .grad.  param None (a gradient nobody asked for): tgt is None, the kernels' null pointer."""
+    __slots__ = ("grad", "tgt")
+
+    def __init__(self, param):
+        self.grad = self.tgt = None
+        if param is not None:
+            self.grad, acc = _grad_target(param)
+            self.tgt = torch.empty_like(self.grad) if acc else self.grad
+
+    @property
+    def accumulates(self):
+        return self.tgt is not self.grad
+
+    def __enter__(self):
+        return self.tgt
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None and self.tgt is not self.grad:
+            self.grad.add_(self.tgt)
+        return False
+
+
 class ParamArena:
     """Flatten a module's parameters (and their gradients) into two contiguous fp32 arenas so the
     momentum update (models/moco.py:31-39), SGD (moco_main.py:79) and the gradient all-reduce are
@@ -976,8 +1002,8 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
             raise L.HipExtensionError("MocoStepEngine: a convolution applied twice in one backward pass (its first weight gradient is "
                                       "still queued for the side stream) - run this model without the step engine")
         _flush_backward_end()
-    g, acc = _grad_target(param)
-    tgt = torch.empty_like(g) if acc else g
+    dest = _GradInto(param)
+    tgt = dest.tgt
     flops = 2.0 * dy.numel() * ci * k3[0] * k3[1] * k3[2]
     if (not nd5 and x.is_cuda and ci == 1 and tuple(k3) == (1, 3, 3) and stride == 1 and tuple(p3) == (0, 1, 1) and dil is None
             and _stem3_ok(int(co)) and _phys_ok(param)):
@@ -986,9 +1012,8 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
         def call():
             return L.check(lib.mi_conv2d_stem3_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, int(co), L.ptr(ws), ws.numel(),
                                                          L.stream()), "mi_conv2d_stem3_wgrad_f32")
-        _prof_run("wgrad", flops, call)
-        if acc:
-            g.add_(tgt)
+        with dest:
+            _prof_run("wgrad", flops, call)
         return
     # (under bench.py's roofline pass only the jobs the engine will queue take the job form - run_wgrad_jobs times them group by group -,
     # everything else is timed right here, call by call)
@@ -1002,13 +1027,12 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
         def call():
             return L.check(lib.mi_conv2d_p2d_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, ci, L.ptr(ws), ws.numel(), L.stream()),
                            "mi_conv2d_p2d_wgrad_f32")
-        _prof_run("wgrad", flops, call)
-        if acc:
-            g.add_(tgt)
+        with dest:
+            _prof_run("wgrad", flops, call)
         return
     d3 = _k3(dil, nd5) if dil is not None else (1, 1, 1)
     geom = _Geom((n, d, h, wd, ci), co, k3, stride, p3, d3)
-    slab_form = (not acc and d3 == (1, 1, 1) and x.is_cuda and
+    slab_form = (not dest.accumulates and d3 == (1, 1, 1) and x.is_cuda and
                  (PROFILE is None or (DEFERRED_WGRADS is not None and SIDE_WGRADS is not None and dy.numel() // co <= SIDE_ROWS_MAX)))
     if slab_form and (DEFERRED_WGRADS is not None or (WGRAD_BATCH and lib.mi_conv3d_direct_usable(n, d, h, wd, ci, co, k3[0], stride, p3[0]) in (1, 2)
                                                       and k3[0] == k3[1] == k3[2] and p3[0] == p3[1] == p3[2])):
@@ -1021,7 +1045,7 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
             # (pinned: a captured hipGraph writes and reads the old buffer on every replay - the step engines pin the slabs
             # when they capture; an eager call that needs more space gets a buffer of its own and the graph's stays alive)
         _f32c(x, "x"), _f32c(dy, "dy")
-        job = _WgradJob(x, dy, tgt, slab, geom, param, flops)
+        job = _WgradJob(x, dy, tgt, slab, geom, param, flops)    # (writes the gradient itself: no temporary to add behind it)
         if DEFERRED_WGRADS is not None:
             if _side_or_now(job, dy.numel() // co):
                 param._mi_wgrad_pending = True             # queued: cleared by run_wgrad_jobs (a second contribution before that raises)
@@ -1032,9 +1056,8 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
     def call():
         return L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
                        "mi_conv_wgrad_f32")
-    _prof_run("wgrad", flops, call)
-    if acc:
-        g.add_(tgt)
+    with dest:
+        _prof_run("wgrad", flops, call)
 
 
 def relu_mask(dy, y, add=None):
@@ -1379,62 +1402,61 @@ class HipConv2d(nn.Module):
         return _ConvFn.apply(x, self.weight, self, relu, False, inference_mode(), grad_slot, dx_slot)
 
 
+class _BNFuse:
+    """One call's request to the Linear node (linear_bn, linear_with_local_sums -> HipLinear.forward(fuse=...)): let the product's
+    launch also do the work of the BatchNorm `bn` behind it - apply it (+ ReLU), or `stats_only`: leave this rank's column sums
+    (SyncBN: the all-reduce and the apply stay launches of their own).  _LinearFn.forward fills in what its launch produced:
+    `sums`, `applied` = (y_bn, save), or neither where the library declined.  Made per call and dropped with it."""
+    __slots__ = ("bn", "relu", "stats_only", "sums", "applied")
+
+    def __init__(self, bn, relu, stats_only):
+        self.bn, self.relu, self.stats_only = bn, relu, stats_only
+        self.sums = self.applied = None
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, mod, inference=False):
+    def forward(ctx, x, w, b, mod, inference=False, fuse=None):
         m, ci = x.shape
         w5 = w.view(w.shape[0], ci, 1, 1, 1) if w.dim() == 5 else _as5(w)
         y = None
-        fuse = getattr(mod, "_fuse_bn", None)
-        if fuse is not None:
-            mod._bn_pre = None
-        if fuse is not None and fuse[2] and PROFILE is None and _phys_ok(w5):
-            # SyncBN across ranks (linear_bn): this rank's column sums come out of the product's epilogue and wait in
-            # mod._bn_pre for the BatchNorm node, which all-reduces them and applies
+        if (fuse is not None or b is not None) and PROFILE is None and _phys_ok(w5):
+            # one launch with an epilogue: the fused entry `fuse` asks for, then - no request, or the entry declined (-3,
+            # MI_E_UNSUPPORTED: rows, arithmetic switch) - the product with the bias in it, then the generic path below
             _f32c(x, "x")
             lib = L.lib()
             co = w5.shape[0]
             y = torch.empty((m, co), dtype=torch.float32, device=x.device)
-            sums = torch.empty(2 * co, dtype=torch.float64, device=x.device)
-            rc = lib.mi_linear_stats_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), L.ptr(sums), m, ci, co, L.stream())
-            if rc == -3:
-                y = None
-            else:
-                L.check(rc, "mi_linear_stats_fwd_f32")
-                mod._bn_pre = ("sums", sums)
-        elif fuse is not None and PROFILE is None and _phys_ok(w5):
-            # Linear + BatchNorm1d (+ ReLU) in one launch (linear_bn): the BatchNorm's output and saved statistics wait in
-            # mod._bn_pre for the BatchNorm node; this node's own output is the Linear's, as always
-            bn, bn_relu, _ = fuse
-            _f32c(x, "x")
-            lib = L.lib()
-            co = w5.shape[0]
-            y = torch.empty((m, co), dtype=torch.float32, device=x.device)
-            yb = torch.empty((m, co), dtype=torch.float32, device=x.device)
-            save = torch.empty(2 * co, dtype=torch.float32, device=x.device)
-            track = bn.track_running_stats and bn.training
-            rc = lib.mi_linear_bn_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), L.ptr(yb), m, ci, co, L.ptr(bn.weight),
-                                          L.ptr(bn.bias), bn.eps, bn.momentum, L.ptr(bn.running_mean if track else None),
-                                          L.ptr(bn.running_var if track else None),
-                                          L.ptr(bn.num_batches_tracked if track else None), L.ptr(save), int(bn_relu),
-                                          L.stream())
-            if rc == -3:
-                y = None                                  # declined (rows, arithmetic switch): the two launches
-            else:
-                L.check(rc, "mi_linear_bn_fwd_f32")
-                mod._bn_pre = (yb, save)
-        if y is not None:
-            pass
-        elif b is not None and PROFILE is None and _phys_ok(w5):
-            # the bias rides in the epilogue of the GEMM launch (or of its split-K reduce)
-            _f32c(x, "x")
-            lib = L.lib()
-            co = w5.shape[0]
-            y = torch.empty((m, co), dtype=torch.float32, device=x.device)
-            ws = _linear_geom(m, ci, co).workspace(x.device)
-            L.check(lib.mi_linear_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), m, ci, co, L.ptr(ws), ws.numel(),
-                                          L.stream()), "mi_linear_fwd_f32")
-        else:
+            rc, what = -3, None
+            if fuse is not None and fuse.stats_only:
+                # this rank's column sums come out of the product's epilogue; the BatchNorm node all-reduces them and applies
+                what = "mi_linear_stats_fwd_f32"
+                sums = torch.empty(2 * co, dtype=torch.float64, device=x.device)
+                rc = lib.mi_linear_stats_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), L.ptr(sums), m, ci, co, L.stream())
+                if rc == 0:
+                    fuse.sums = sums
+            elif fuse is not None:
+                # Linear + BatchNorm1d (+ ReLU) in one launch: the BatchNorm's output and saved statistics go back to linear_bn
+                # for the BatchNorm node; this node's own output is the Linear's, as always
+                what = "mi_linear_bn_fwd_f32"
+                bn = fuse.bn
+                yb = torch.empty((m, co), dtype=torch.float32, device=x.device)
+                save = torch.empty(2 * co, dtype=torch.float32, device=x.device)
+                rc = lib.mi_linear_bn_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), L.ptr(yb), m, ci, co, L.ptr(bn.weight),
+                                              L.ptr(bn.bias), bn.eps, bn.momentum,
+                                              *_bn_running_ptrs(bn, bn.track_running_stats and bn.training),
+                                              L.ptr(save), int(fuse.relu), L.stream())
+                if rc == 0:
+                    fuse.applied = (yb, save)
+            if rc == -3 and b is not None:
+                # the bias rides in the epilogue of the GEMM launch (or of its split-K reduce)
+                what = "mi_linear_fwd_f32"
+                ws = _linear_geom(m, ci, co).workspace(x.device)
+                rc = lib.mi_linear_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), m, ci, co, L.ptr(ws), ws.numel(), L.stream())
+            elif rc == -3:
+                y, rc = None, 0
+            L.check(rc, what)
+        if y is None:
             y = conv_fwd(x.view(m, 1, 1, 1, ci), w5, 1, 1, 0, owner=w, inference=inference).view(m, -1)
             if b is not None:
                 L.check(L.lib().mi_bias_add(L.ptr(y), L.ptr(b), m, y.shape[1], L.stream()), "mi_bias_add")
@@ -1450,33 +1472,21 @@ class _LinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         m, ci = x.shape
         co = dy.shape[1]
-        lib = L.lib()
         if mod.weight.requires_grad:
-            g, acc = _grad_target(mod.weight)
-            tgt = torch.empty_like(g) if acc else g
-            def launch(g=g, acc=acc, tgt=tgt):          # (bound now: the names are reused for the bias below)
+            dest = _GradInto(mod.weight)               # (the target is bound now, the launch may wait for the side stream)
+            def launch():
                 geom = _linear_geom(m, ci, co)
                 ws = geom.workspace(x.device)
-                L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
-                        "mi_conv_wgrad_f32")
-                if acc:
-                    g.add_(tgt)
+                with dest as tgt:
+                    L.check(L.lib().mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None,
+                                                      L.stream()), "mi_conv_wgrad_f32")
             _side_or_now(launch, m)
         if mod.bias is not None and mod.bias.requires_grad:
-            g, acc = _grad_target(mod.bias)
-            tgt = torch.empty_like(g) if acc else g
-            def launch_b(g=g, acc=acc, tgt=tgt):       # the bias gradient is a parameter gradient too: same side-stream batch
-                ws = _ws(lib.mi_colreduce_workspace_bytes(m, co), x.device, "colreduce")
-                sums = torch.empty(2 * co, dtype=torch.float64, device=x.device)
-                L.check(lib.mi_colsum(L.ptr(dy), m, co, L.ptr(tgt), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()),
-                        "mi_colsum")
-                if acc:
-                    g.add_(tgt)
-            _side_or_now(launch_b, m)
+            _side_or_now(_colsum_job(dy, mod.bias), m)  # the bias gradient is a parameter gradient too: same side-stream batch
         dx = None
         if ctx.x_needs_grad:
             dx = conv_dgrad(dy.view(m, 1, 1, 1, co), _as5(mod.weight), (m, 1, 1, 1, ci), 1, 1, 0).view(m, ci)
-        return dx, None, None, None, None
+        return dx, None, None, None, None, None
 
 
 def _as5(w2):
@@ -1497,10 +1507,11 @@ class HipLinear(nn.Module):
             if bias:
                 self.bias.uniform_(-bound, bound)
 
-    def forward(self, x):
+    def forward(self, x, fuse=None):
+        """fuse: a _BNFuse request (linear_bn, linear_with_local_sums); the result is the Linear's output either way."""
         if not _phys_ok(self.weight):
             raise L.HipExtensionError("linear weight is not in kernel layout [in][out]")
-        return _LinearFn.apply(_f32c(x, "x"), self.weight, self.bias, self, inference_mode())
+        return _LinearFn.apply(_f32c(x, "x"), self.weight, self.bias, self, inference_mode(), fuse)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1544,17 +1555,21 @@ def dist_all_reduce_pair(a, b):
         dist.all_reduce(b)
 
 
-def bn_local_sums(x):
-    """This rank's column sums (sum x, sum x^2: 2C doubles) of a channels-last activation - the statistics pass of a SyncBN whose
-    all-reduce the caller issues itself (paired with another branch's: MoCo's layer-locked forward)."""
-    _f32c(x, "x")
-    c = x.shape[-1]
-    m = x.numel() // c
+def _bn_stats(x, m, c):
+    """Column sums (sum x, sum x^2: 2C doubles) of the (m, c) activation x: the statistics pass."""
     lib = L.lib()
     ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), x.device, "colreduce")
     sums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
     L.check(lib.mi_bn_stats(L.ptr(x), m, c, L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_bn_stats")
     return sums
+
+
+def bn_local_sums(x):
+    """This rank's column sums (sum x, sum x^2: 2C doubles) of a channels-last activation - the statistics pass of a SyncBN whose
+    all-reduce the caller issues itself (paired with another branch's: MoCo's layer-locked forward)."""
+    _f32c(x, "x")
+    c = x.shape[-1]
+    return _bn_stats(x, x.numel() // c, c)
 
 
 def dist_all_gather(tensor_list, tensor):
@@ -1579,74 +1594,83 @@ def _distributed():
 BN_SMALL_MAX_ROWS = 4096      # == MI_BN_SMALL_MAX_ROWS
 
 
+def _bn_batch_sums(x, m, c, mod, sums=None, reduced=False):
+    """(sums, count) of a training-mode BatchNorm over the (m, c) activation x: the column sums over the whole batch and its number
+    of rows.  sums: this rank's, where the producer of x already has them (the statistics pass is skipped); reduced: they are
+    the GLOBAL sums already - the caller has all-reduced them (paired with another branch's)."""
+    if sums is None:
+        sums = _bn_stats(x, m, c)
+    count = float(m)
+    if mod.sync and _distributed():
+        if not reduced:
+            dist_all_reduce(sums)                         # RCCL: 2*C doubles
+        count = float(m) * _dist_world()
+    return sums, count
+
+
+def _bn_running_ptrs(mod, track):
+    """The (running_mean, running_var, num_batches_tracked) arguments of a BatchNorm launch: null unless `track`."""
+    if not track:
+        return L.ptr(None), L.ptr(None), L.ptr(None)
+    return L.ptr(mod.running_mean), L.ptr(mod.running_var), L.ptr(mod.num_batches_tracked)
+
+
+def _bn_affine_grads(mod):
+    """The _GradInto pair (dgamma, dbeta) of a BatchNorm backward: null targets without affine parameters or with frozen ones."""
+    gamma = mod.weight
+    wanted = gamma is not None and gamma.requires_grad
+    return _GradInto(gamma if wanted else None), _GradInto(mod.bias if wanted else None)
+
+
+def _bn_sync_bwd_sums(sums, c, dg, db, distributed):
+    """Between the reduce and the apply launch of a BatchNorm backward: the (dgamma, dbeta) pointers the apply launch gets.
+    Single process: that launch writes them from the sums.  Distributed: they come from the LOCAL sums here (torch.nn.SyncBatchNorm
+    does the same; the data-parallel gradient averaging then treats them like every other parameter), the sums are all-reduced
+    for dx and the apply launch gets null pointers."""
+    if not distributed:
+        return L.ptr(dg), L.ptr(db)
+    if dg is not None:
+        L.check(L.lib().mi_bn_param_grads(L.ptr(sums), c, L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_param_grads")
+    dist_all_reduce(sums)
+    return L.ptr(None), L.ptr(None)
+
+
 class _BNFn(torch.autograd.Function):
     """y = act(bn(x) + res); res (optional) is a residual branch added before the activation."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, mod, relu, res=None, pre=None, res_slot=None):
+    def forward(ctx, x, gamma, beta, mod, relu, res=None, res_slot=None, sums=None, reduced=False, applied=None):
         ctx.res_slot = res_slot if res is not None else None
-        shape = x.shape
-        c = shape[-1]
+        c = x.shape[-1]
         m = x.numel() // c
         lib = L.lib()
-        dev = x.device
-        distributed = mod.sync and _distributed()
-        ctx.small = (mod.training or not mod.track_running_stats) and m <= BN_SMALL_MAX_ROWS and not distributed
-        given_sums = None
-        reduced = False
-        if pre is not None and isinstance(pre[0], str):
-            given_sums = pre[1]                           # this rank's column sums from the producing Linear's epilogue (SyncBN)
-            reduced = pre[0] == "reduced"                 # ... or the GLOBAL sums: the caller has all-reduced them (paired with another branch's)
-            pre = None
-        if pre is not None:
+        train = mod.training or not mod.track_running_stats
+        ctx.small = train and m <= BN_SMALL_MAX_ROWS and not (mod.sync and _distributed())
+        ctx.count = float(m)
+        ctx.train_stats = train
+        track = mod.track_running_stats and mod.training
+        if applied is not None:
             # (y, save) came out of the producing Linear's launch (linear_bn): nothing to run here
             if not ctx.small or res is not None:
                 raise L.HipExtensionError("fused Linear+BatchNorm output handed to a BatchNorm that would not take the small path")
-            y, save = pre
-            ctx.count = float(m)
-            ctx.train_stats = True
+            y, save = applied
         else:
             y = torch.empty_like(x)
-            save = torch.empty(2 * c, dtype=torch.float32, device=dev)
-        if pre is not None:
-            pass
-        elif ctx.small:
-            # one launch: statistics, running statistics, affine (+res, ReLU)
-            track = mod.track_running_stats and mod.training
-            L.check(lib.mi_bn_small_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(gamma), L.ptr(beta), mod.eps, mod.momentum,
-                                        L.ptr(mod.running_mean if track else None),
-                                        L.ptr(mod.running_var if track else None),
-                                        L.ptr(mod.num_batches_tracked if track else None),
-                                        L.ptr(save), L.ptr(res), int(relu), L.stream()), "mi_bn_small_fwd")
-            ctx.count = float(m)
-            ctx.train_stats = True
-        elif mod.training or not mod.track_running_stats:
-            if given_sums is not None:
-                sums = given_sums
+            save = torch.empty(2 * c, dtype=torch.float32, device=x.device)
+            if ctx.small:
+                # one launch: statistics, running statistics, affine (+res, ReLU)
+                L.check(lib.mi_bn_small_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(gamma), L.ptr(beta), mod.eps, mod.momentum,
+                                            *_bn_running_ptrs(mod, track), L.ptr(save), L.ptr(res), int(relu), L.stream()),
+                        "mi_bn_small_fwd")
+            elif train:
+                sums, ctx.count = _bn_batch_sums(x, m, c, mod, sums, reduced)
+                L.check(lib.mi_bn_apply_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(sums), ctx.count, L.ptr(gamma), L.ptr(beta),
+                                            mod.eps, mod.momentum, *_bn_running_ptrs(mod, track),
+                                            L.ptr(save), L.ptr(res), int(relu), L.stream()), "mi_bn_apply_fwd")
             else:
-                ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dev, "colreduce")
-                sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
-                L.check(lib.mi_bn_stats(L.ptr(x), m, c, L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_bn_stats")
-            count = float(m)
-            if mod.sync and _distributed():
-                import torch.distributed as dist
-                if not reduced:
-                    dist_all_reduce(sums)                 # RCCL: 2*C doubles
-                count = float(m) * _dist_world()
-            track = mod.track_running_stats and mod.training
-            L.check(lib.mi_bn_apply_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(sums), count, L.ptr(gamma), L.ptr(beta),
-                                        mod.eps, mod.momentum,
-                                        L.ptr(mod.running_mean if track else None),
-                                        L.ptr(mod.running_var if track else None),
-                                        L.ptr(mod.num_batches_tracked if track else None),
-                                        L.ptr(save), L.ptr(res), int(relu), L.stream()), "mi_bn_apply_fwd")
-            ctx.count = count
-            ctx.train_stats = True
-        else:
-            L.check(lib.mi_bn_eval_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(mod.running_mean), L.ptr(mod.running_var),
-                                       L.ptr(gamma), L.ptr(beta), mod.eps, L.ptr(save), L.ptr(res), int(relu),
-                                       L.stream()), "mi_bn_eval_fwd")
-            ctx.train_stats = False
+                L.check(lib.mi_bn_eval_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(mod.running_mean), L.ptr(mod.running_var),
+                                           L.ptr(gamma), L.ptr(beta), mod.eps, L.ptr(save), L.ptr(res), int(relu),
+                                           L.stream()), "mi_bn_eval_fwd")
         ctx.mod, ctx.relu, ctx.m, ctx.c = mod, relu, m, c
         ctx.has_res = res is not None
         ctx.save_for_backward(x, y if relu else None, save)
@@ -1658,7 +1682,6 @@ class _BNFn(torch.autograd.Function):
         mod, relu, m, c = ctx.mod, ctx.relu, ctx.m, ctx.c
         dy = dy.contiguous()
         lib = L.lib()
-        dev = x.device
         if not ctx.train_stats:
             raise L.HipExtensionError("BatchNorm backward in eval mode is not on the hot path")
         dres = None
@@ -1672,73 +1695,40 @@ class _BNFn(torch.autograd.Function):
                     dy = relu_mask(dy, y)
                     relu = False
                 dres = dy
-        def hand_over(dres):
-            # through the block's GradSlot when its first convolution adds the residual gradient in its own epilogue
-            if ctx.res_slot is not None and dres is not None:
-                ctx.res_slot.tensor = dres
-                return None
-            return dres
-        if ctx.small:
-            gamma = mod.weight
-            dg = db = None
-            acc_g = acc_b = False
-            if gamma is not None and gamma.requires_grad:
-                gt, acc_g = _grad_target(gamma)
-                dg = torch.empty_like(gt) if acc_g else gt
-                bt, acc_b = _grad_target(mod.bias)
-                db = torch.empty_like(bt) if acc_b else bt
-            dx = torch.empty_like(x)
-            L.check(lib.mi_bn_small_bwd(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma),
-                                        int(relu), L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_small_bwd")
-            if acc_g:
-                gamma.grad.add_(dg)
-            if acc_b:
-                mod.bias.grad.add_(db)
-            return dx, None, None, None, None, hand_over(dres), None, None
-        ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dev, "colreduce")
-        sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
-        L.check(lib.mi_bn_bwd_reduce(L.ptr(dy), L.ptr(x), L.ptr(y), m, c, L.ptr(save), int(relu), L.ptr(sums),
-                                     L.ptr(ws), ws.numel(), L.stream()), "mi_bn_bwd_reduce")
         gamma = mod.weight
-        dg = db = None
-        acc_g = acc_b = False
-        if gamma is not None and gamma.requires_grad:
-            gt, acc_g = _grad_target(gamma)
-            dg = torch.empty_like(gt) if acc_g else gt
-            bt, acc_b = _grad_target(mod.bias)
-            db = torch.empty_like(bt) if acc_b else bt
-        distributed = mod.sync and _distributed()
-        if distributed:
-            if dg is not None:
-                # affine gradients come from the LOCAL sums (torch.nn.SyncBatchNorm does the same); the
-                # data-parallel gradient averaging then treats them like every other parameter
-                L.check(lib.mi_bn_param_grads(L.ptr(sums), c, L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_param_grads")
-            import torch.distributed as dist
-            dist_all_reduce(sums)                      # dx needs the global sums
         dx = torch.empty_like(x)
-        # single process: the same launch writes dgamma / dbeta from the sums
-        if want_dres:
-            dres = torch.empty_like(dy)
-            L.check(lib.mi_bn_bwd_apply_res(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), L.ptr(dres), m, c, L.ptr(save), L.ptr(gamma),
-                                            L.ptr(sums), ctx.count, L.ptr(None if distributed else dg),
-                                            L.ptr(None if distributed else db), L.stream()), "mi_bn_bwd_apply_res")
+        if ctx.small:
+            dgamma, dbeta = _bn_affine_grads(mod)
+            with dgamma as dg, dbeta as db:
+                L.check(lib.mi_bn_small_bwd(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma),
+                                            int(relu), L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_small_bwd")
         else:
-            L.check(lib.mi_bn_bwd_apply(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma),
-                                        L.ptr(sums), ctx.count, int(relu), L.ptr(None if distributed else dg),
-                                        L.ptr(None if distributed else db), L.stream()),
-                    "mi_bn_bwd_apply")
-        if acc_g:
-            gamma.grad.add_(dg)
-        if acc_b:
-            mod.bias.grad.add_(db)
-        return dx, None, None, None, None, hand_over(dres), None, None
+            ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), x.device, "colreduce")
+            sums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
+            L.check(lib.mi_bn_bwd_reduce(L.ptr(dy), L.ptr(x), L.ptr(y), m, c, L.ptr(save), int(relu), L.ptr(sums),
+                                         L.ptr(ws), ws.numel(), L.stream()), "mi_bn_bwd_reduce")
+            dgamma, dbeta = _bn_affine_grads(mod)
+            with dgamma as dg, dbeta as db:
+                pg, pb = _bn_sync_bwd_sums(sums, c, dg, db, mod.sync and _distributed())
+                if want_dres:
+                    dres = torch.empty_like(dy)
+                    L.check(lib.mi_bn_bwd_apply_res(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), L.ptr(dres), m, c, L.ptr(save),
+                                                    L.ptr(gamma), L.ptr(sums), ctx.count, pg, pb, L.stream()), "mi_bn_bwd_apply_res")
+                else:
+                    L.check(lib.mi_bn_bwd_apply(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma),
+                                                L.ptr(sums), ctx.count, int(relu), pg, pb, L.stream()), "mi_bn_bwd_apply")
+        if ctx.res_slot is not None and dres is not None:
+            # through the block's GradSlot when its first convolution adds the residual gradient in its own epilogue
+            ctx.res_slot.tensor = dres
+            dres = None
+        return dx, None, None, None, None, dres, None, None, None, None
 
 
 class _BNReluPoolFn(torch.autograd.Function):
     """MaxPool3d(k, s, p)(relu(bn(x))) without materialising relu(bn(x)): the stem of the 3-D encoder."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, mod, k, stride, pad, given_sums=None, reduced=False):
+    def forward(ctx, x, gamma, beta, mod, k, stride, pad, sums=None, reduced=False):
         n, d, h, w, c = x.shape
         lib = L.lib()
         dev = x.device
@@ -1748,27 +1738,13 @@ class _BNReluPoolFn(torch.autograd.Function):
         train = mod.training or not mod.track_running_stats
         arg = torch.empty((n, do, ho, wo, c), dtype=torch.uint8, device=dev) if (train and x.requires_grad) else None
         m = n * d * h * w
-        count = float(m)
-        sums = None
-        if train:
-            if given_sums is not None:
-                sums = given_sums
-            else:
-                ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dev, "colreduce")
-                sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
-                L.check(lib.mi_bn_stats(L.ptr(x), m, c, L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_bn_stats")
-            if mod.sync and _distributed():
-                import torch.distributed as dist
-                if not reduced:                           # (reduced: the caller has all-reduced `given_sums`, paired with another branch's)
-                    dist_all_reduce(sums)
-                count = float(m) * _dist_world()
+        sums, count = _bn_batch_sums(x, m, c, mod, sums, reduced) if train else (None, float(m))
         track = mod.track_running_stats and mod.training
-        use_running = not train
+        running_mean, running_var, _ = _bn_running_ptrs(mod, track or not train)     # (eval mode READS the running statistics)
         L.check(lib.mi_bn_relu_maxpool3d_fwd(
             L.ptr(x), L.ptr(y), L.ptr(arg), n, d, h, w, c, k, stride, pad, L.ptr(sums), count, L.ptr(gamma), L.ptr(beta),
-            mod.eps, mod.momentum, L.ptr(mod.running_mean if (track or use_running) else None),
-            L.ptr(mod.running_var if (track or use_running) else None),
-            L.ptr(mod.num_batches_tracked if track else None), L.ptr(save), L.stream()), "mi_bn_relu_maxpool3d_fwd")
+            mod.eps, mod.momentum, running_mean, running_var, L.ptr(mod.num_batches_tracked if track else None),
+            L.ptr(save), L.stream()), "mi_bn_relu_maxpool3d_fwd")
         ctx.mod, ctx.geom, ctx.count, ctx.train = mod, (n, d, h, w, c, k, stride, pad), count, train
         ctx.save_for_backward(x, save, arg)
         return y
@@ -1793,27 +1769,12 @@ class _BNReluPoolFn(torch.autograd.Function):
         ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dev, "colreduce")
         L.check(lib.mi_bn_relu_bwd_reduce_x(L.ptr(dy), L.ptr(x), m, c, L.ptr(save), L.ptr(gamma), L.ptr(beta), L.ptr(sums),
                                             L.ptr(ws), ws.numel(), L.stream()), "mi_bn_relu_bwd_reduce_x")
-        dg = db = None
-        acc_g = acc_b = False
-        if gamma is not None and gamma.requires_grad:
-            gt, acc_g = _grad_target(gamma)
-            dg = torch.empty_like(gt) if acc_g else gt
-            bt, acc_b = _grad_target(beta)
-            db = torch.empty_like(bt) if acc_b else bt
-        distributed = mod.sync and _distributed()
-        if distributed:
-            if dg is not None:           # affine gradients from the LOCAL sums, like torch.nn.SyncBatchNorm
-                L.check(lib.mi_bn_param_grads(L.ptr(sums), c, L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_param_grads")
-            import torch.distributed as dist
-            dist_all_reduce(sums)
         dx = dy                                            # in place: each element is read, then written, by one thread
-        L.check(lib.mi_bn_relu_bwd_apply_x(L.ptr(dy), L.ptr(x), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma), L.ptr(beta),
-                                           L.ptr(sums), ctx.count, L.ptr(None if distributed else dg),
-                                           L.ptr(None if distributed else db), L.stream()), "mi_bn_relu_bwd_apply_x")
-        if acc_g:
-            gamma.grad.add_(dg)
-        if acc_b:
-            beta.grad.add_(db)
+        dgamma, dbeta = _bn_affine_grads(mod)
+        with dgamma as dg, dbeta as db:
+            pg, pb = _bn_sync_bwd_sums(sums, c, dg, db, mod.sync and _distributed())
+            L.check(lib.mi_bn_relu_bwd_apply_x(L.ptr(dy), L.ptr(x), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma), L.ptr(beta),
+                                               L.ptr(sums), ctx.count, pg, pb, L.stream()), "mi_bn_relu_bwd_apply_x")
         return dx, None, None, None, None, None, None, None, None
 
 
@@ -1833,32 +1794,21 @@ def linear_bn(x, lin, bn, relu=False):
         return bn(lin(x), relu=relu)
     # SyncBN across ranks: only the statistics come out of the product's epilogue (this rank's column sums); the all-reduce and
     # the apply stay launches of their own
-    lin._fuse_bn = (bn, relu, bool(bn.sync and _distributed()))
-    try:
-        xl = lin(x)
-        pre = getattr(lin, "_bn_pre", None)
-    finally:
-        lin._fuse_bn = None
-        lin._bn_pre = None
-    return bn(xl, relu=relu, pre=pre)                 # (through the module: forward hooks keep firing)
+    req = _BNFuse(bn, relu, stats_only=bool(bn.sync and _distributed()))
+    xl = lin(x, fuse=req)
+    return bn(xl, relu=relu, sums=req.sums, applied=req.applied)     # (through the module: forward hooks keep firing)
 
 
 def linear_with_local_sums(x, lin, bn):
     """(lin(x), this rank's column sums of it) for a SyncBN whose all-reduce the CALLER issues (MoCo's layer-locked forward pairs it
     with the other encoder's): the sums come out of the product's epilogue where linear_bn's would, else from a statistics pass."""
     train = bn.training or not bn.track_running_stats
+    req = None
     if x.is_cuda and x.dim() == 2 and x.shape[0] <= 64 and train and PROFILE is None:
-        lin._fuse_bn = (bn, False, True)
-        try:
-            xl = lin(x)
-            pre = getattr(lin, "_bn_pre", None)
-        finally:
-            lin._fuse_bn = None
-            lin._bn_pre = None
-        if pre is not None and pre[0] == "sums":
-            return xl, pre[1]
-        return xl, bn_local_sums(xl)
-    xl = lin(x)
+        req = _BNFuse(bn, False, stats_only=True)
+    xl = lin(x, fuse=req)
+    if req is not None and req.sums is not None:
+        return xl, req.sums
     return xl, bn_local_sums(xl)
 
 
@@ -1880,8 +1830,9 @@ class HipBatchNorm(nn.Module):
         self.register_buffer("running_var", torch.ones(c))
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
-    def forward(self, x, relu=False, res=None, pre=None, res_slot=None):
-        return _BNFn.apply(_f32c(x, "x"), self.weight, self.bias, self, relu, res, pre, res_slot)
+    def forward(self, x, relu=False, res=None, res_slot=None, sums=None, reduced=False, applied=None):
+        """sums / reduced: as in bn_relu_maxpool3d.  applied: the (y, save) a fused Linear+BatchNorm launch produced (linear_bn)."""
+        return _BNFn.apply(_f32c(x, "x"), self.weight, self.bias, self, relu, res, res_slot, sums, reduced, applied)
 
 
 def convert_sync_batchnorm(module):
@@ -1963,12 +1914,9 @@ class _BNReluAvgPoolFn(torch.autograd.Function):
         y = torch.empty_like(x)
         pooled = torch.empty((x.shape[0], c), dtype=torch.float32, device=x.device)
         save = torch.empty(2 * c, dtype=torch.float32, device=x.device)
-        track = mod.track_running_stats and mod.training
         L.check(lib.mi_bn_small_pool_fwd(L.ptr(x), L.ptr(y), L.ptr(pooled), m, c, v, L.ptr(gamma), L.ptr(beta), mod.eps,
-                                         mod.momentum, L.ptr(mod.running_mean if track else None),
-                                         L.ptr(mod.running_var if track else None),
-                                         L.ptr(mod.num_batches_tracked if track else None), L.ptr(save), L.stream()),
-                "mi_bn_small_pool_fwd")
+                                         mod.momentum, *_bn_running_ptrs(mod, mod.track_running_stats and mod.training),
+                                         L.ptr(save), L.stream()), "mi_bn_small_pool_fwd")
         ctx.mod, ctx.m, ctx.c, ctx.v = mod, m, c, v
         ctx.save_for_backward(x, y, save)
         return pooled
@@ -1977,21 +1925,11 @@ class _BNReluAvgPoolFn(torch.autograd.Function):
     def backward(ctx, dp):
         x, y, save = ctx.saved_tensors
         mod, m, c, v = ctx.mod, ctx.m, ctx.c, ctx.v
-        gamma = mod.weight
-        dg = db = None
-        acc_g = acc_b = False
-        if gamma is not None and gamma.requires_grad:
-            gt, acc_g = _grad_target(gamma)
-            dg = torch.empty_like(gt) if acc_g else gt
-            bt, acc_b = _grad_target(mod.bias)
-            db = torch.empty_like(bt) if acc_b else bt
         dx = torch.empty_like(x)
-        L.check(L.lib().mi_bn_small_pool_bwd(L.ptr(dp.contiguous()), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, v, L.ptr(save),
-                                             L.ptr(gamma), L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_small_pool_bwd")
-        if acc_g:
-            gamma.grad.add_(dg)
-        if acc_b:
-            mod.bias.grad.add_(db)
+        dgamma, dbeta = _bn_affine_grads(mod)
+        with dgamma as dg, dbeta as db:
+            L.check(L.lib().mi_bn_small_pool_bwd(L.ptr(dp.contiguous()), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, v, L.ptr(save),
+                                                 L.ptr(mod.weight), L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_small_pool_bwd")
         return dx, None, None, None, None
 
 
@@ -2361,17 +2299,23 @@ def maxpool2d_ceil(x, k=2):
     return _MaxPool2dCeilFn.apply(_f32c(x, "x"), k)
 
 
+def _colsum_job(dy2d, param):
+    """The launch `param.grad (+)= column sums of dy2d (M, C)` as a closure: the gradient's target is bound here, the launch runs
+    when the closure is called (now, or from the side-stream batch: _side_or_now)."""
+    dest = _GradInto(param)
+    def launch():
+        m, c = dy2d.shape
+        lib = L.lib()
+        ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dy2d.device, "colreduce")
+        sums = torch.empty(2 * c, dtype=torch.float64, device=dy2d.device)
+        with dest as tgt:
+            L.check(lib.mi_colsum(L.ptr(dy2d), m, c, L.ptr(tgt), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_colsum")
+    return launch
+
+
 def _colsum_into(dy2d, param):
     """param.grad (+)= column sums of dy2d (M, C)."""
-    m, c = dy2d.shape
-    lib = L.lib()
-    g, acc = _grad_target(param)
-    tgt = torch.empty_like(g) if acc else g
-    ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dy2d.device, "colreduce")
-    sums = torch.empty(2 * c, dtype=torch.float64, device=dy2d.device)
-    L.check(lib.mi_colsum(L.ptr(dy2d), m, c, L.ptr(tgt), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_colsum")
-    if acc:
-        g.add_(tgt)
+    _colsum_job(dy2d, param)()
 
 
 class _ConvT2x2Fn(torch.autograd.Function):
@@ -2404,15 +2348,11 @@ class _ConvT2x2Fn(torch.autograd.Function):
             _colsum_into(dy.view(-1, co), mod.bias)
         if mod.weight.requires_grad:
             # the gradient tensor has the parameter's strides, i.e. the GEMM layout [ci][4*co]
-            g, acc = _grad_target(mod.weight)
-            tgt = torch.empty_like(g) if acc else g
-            lib = L.lib()
             geom = _Geom((n, 1, h, wd, ci), 4 * co, (1, 1, 1), 1, (0, 0, 0))
             ws = geom.workspace(x.device)
-            L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dt), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
-                    "mi_conv_wgrad_f32")
-            if acc:
-                g.add_(tgt)
+            with _GradInto(mod.weight) as tgt:
+                L.check(L.lib().mi_conv_wgrad_f32(L.ptr(x), L.ptr(dt), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
+                        "mi_conv_wgrad_f32")
         dx = conv_dgrad(dt, mod.gemm_view(), x.shape, 1, 1, 0) if ctx.x_needs_grad else None
         return dx, None, None, None, None, None, None
 
@@ -2511,15 +2451,10 @@ class _ZHeadFn(torch.autograd.Function):
         lib = L.lib()
         dy = dy.contiguous()
         dx = torch.empty_like(x) if ctx.x_needs_grad else None
-        tgt, g, acc = None, None, False
-        if mod.weight.requires_grad:
-            g, acc = _grad_target(mod.weight)
-            tgt = torch.empty_like(g) if acc else g
         ws = _ws(lib.mi_zhead_bwd_workspace_bytes(n, d, h * wd, c, k), x.device, "zhead")
-        L.check(lib.mi_zhead_bwd(L.ptr(x), L.ptr(mod.weight), L.ptr(dy), L.ptr(dx), L.ptr(tgt), n, d, h * wd, c, k,
-                                 L.ptr(ws), ws.numel(), L.stream()), "mi_zhead_bwd")
-        if acc:
-            g.add_(tgt)
+        with _GradInto(mod.weight if mod.weight.requires_grad else None) as tgt:
+            L.check(lib.mi_zhead_bwd(L.ptr(x), L.ptr(mod.weight), L.ptr(dy), L.ptr(dx), L.ptr(tgt), n, d, h * wd, c, k,
+                                     L.ptr(ws), ws.numel(), L.stream()), "mi_zhead_bwd")
         return dx, None, None
 
 

@@ -173,7 +173,7 @@ class TomoResClassifier3D(nn.Module):
         x = self.feature_3d[0](x, mask_dx=True)
         sums = H.bn_local_sums(x)
         yield sums
-        x = H.global_avgpool(self.feature_3d[1](x, relu=True, pre=("reduced", sums)))
+        x = H.global_avgpool(self.feature_3d[1](x, relu=True, sums=sums, reduced=True))
         x = self.fc(x)
         ret1 = {}
         for head in self.heads:
@@ -183,7 +183,7 @@ class TomoResClassifier3D(nn.Module):
                 for li, bi, relu in ((0, 1, True), (3, 4, True), (6, 7, False)):
                     yl, sums = H.linear_with_local_sums(y, seq[li], seq[bi])
                     yield sums
-                    y = seq[bi](yl, relu=relu, pre=("reduced", sums))
+                    y = seq[bi](yl, relu=relu, sums=sums, reduced=True)
                 ret1[head] = y
         return [ret1]
 

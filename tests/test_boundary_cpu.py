@@ -135,3 +135,29 @@ def test_plain_arena_drops_second_gradient_views():
             tgt.copy_(torch.full_like(p, contribution))
     assert torch.equal(p.grad, torch.full_like(p, 3.0))
     assert p.grad.data_ptr() == p._mi_grad_view.data_ptr()
+
+
+def test_grad_into_assigns_routes_and_accumulates():
+    """_GradInto over _grad_target, the one way a parameter gradient is written: the first contribution of a step lands in .grad (the
+    arena view), the second in the second arena, every further one in a temporary that leaving the block adds onto .grad; the target
+    is fixed when the object is made, not when it is entered; a failed launch adds nothing; no parameter, no target."""
+    from cet_pick_amd import hipops as H
+    m = torch.nn.Linear(4, 3)
+    arena = H.ParamArena(m, second_grad_arena=True)
+    p = m.weight
+    arena.zero_grad()
+    first, second, third = H._GradInto(p), H._GradInto(p), H._GradInto(p)      # all made before the first is entered (deferred launches)
+    assert (first.accumulates, second.accumulates, third.accumulates) == (False, False, True)
+    for dest, value in ((first, 1.0), (second, 2.0), (third, 4.0)):
+        with dest as tgt:
+            tgt.copy_(torch.full_like(p, value))
+    assert first.tgt.data_ptr() == p._mi_grad_view.data_ptr() and second.tgt.data_ptr() == p._mi_grad_view2.data_ptr()
+    assert torch.equal(p.grad, torch.full_like(p, 5.0))
+    assert torch.equal(p._mi_grad_view2, torch.full_like(p, 2.0))
+    with pytest.raises(RuntimeError, match="launch failed"):
+        with H._GradInto(p) as tgt:
+            tgt.copy_(torch.full_like(p, 8.0))
+            raise RuntimeError("launch failed")
+    assert torch.equal(p.grad, torch.full_like(p, 5.0))
+    with H._GradInto(None) as tgt:
+        assert tgt is None
