@@ -22,6 +22,14 @@ class ConvGeom(ctypes.Structure):
 
 _G = _c.POINTER(ConvGeom)
 
+
+class Aug2d3dRanges(ctypes.Structure):
+    """mi_aug2d3d_ranges of include/cetpick_hip.h, fields in header order"""
+    _fields_ = [(f, _F) for f in "flip_p angle_lo angle_hi erase_p scale_lo scale_hi ratio_lo ratio_hi".split()]
+
+
+_R = _c.POINTER(Aug2d3dRanges)
+
 # name -> (restype, argtypes); kept in step with include/cetpick_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "mi_abi_version": (_I, []),
@@ -48,6 +56,8 @@ SIGNATURES = {
     "mi_u8_roundtrip_normalize": (_I, [_P, _P, _Z, _F, _F, _P]),
     "mi_aug2d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _I] + [_F] * 7 + [_P, _P]),
     "mi_aug2d_apply": (_I, [_P, _c.c_int64, _I, _P, _P, _c.c_int64, _I, _F, _F, _P, _P]),
+    "mi_aug2d3d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _R, _R, _P, _P]),
+    "mi_aug2d3d_apply": (_I, [_P, _P, _c.c_int64, _I, _P, _P, _P, _P, _c.c_int64, _I, _F, _F, _F, _F, _P, _P]),
     "mi_tilt_patches": (_I, [_P, _I, _P, _P, _c.c_int64, _I, _I, _D, _D, _P, _P, _P]),
     "mi_semi_labels": (_I, [_P, _I, _I, _I, _P, _c.c_int64, _P, _I, _I, _P]),
     "mi_semi_pairs": (_I, [_P, _P, _I, _P, _P, _c.c_int64, _I, _I, _P, _P, _P, _P]),

@@ -10,8 +10,10 @@ patches.  `TOMOPreProjAngleSelect2D3D.load_data` (datasets/tomo_pre_proj_angle_s
 Batches are {'input', 'input_3d', 'input_aug', 'input_aug_3d'} and nothing else (the step engine captures every tensor of a
 batch): view 1 is the pick's patch pair, view 2 one of its valid shifted variants drawn with the epoch-seeded RNG
 (datasets/particle_pre_2d_proj_new2d3d.py:81 `np.random.randint(1, n)`), both through the per-channel 8-bit round trip and
-`Normalize((mean_subvols, mean_subvols3d), (std_subvols, std_subvols3d))` of the reference transforms.  The random flips,
-rotations and CornerErasing are out of scope, as for every dataset of this build (datasets/tomo_files.py).
+`Normalize((mean_subvols, mean_subvols3d), (std_subvols, std_subvols3d))` of the reference transforms.  With `--augment
+reference` the train split serves the reference's random views instead (:49-82): the strong chain (flips, RandomRotation(30),
+CornerErasing, quarter turn) on the pick's pair, the weak chain (the same without the rotation) on the drawn variant's, both
+channels of a view through one set of parameters, drawn and applied on the device (datasets/augment.py, two launches a batch).
 
   TomoFileSimSiam2D3DDataset     the 4-column image list (image_name, rec_path, tilt_path, angle_path) of --train_img_txt /
                                  --test_img_txt under --data_dir
@@ -133,7 +135,17 @@ class SimSiam2D3DDataset:
         self.normed_2d = S.to_uint8_normalize(self.patches_2d, self.mean_subvols, self.std_subvols)
         self.normed_3d = S.to_uint8_normalize(self.patches_3d, self.mean_subvols3d, self.std_subvols3d)
         self.num_samples = len(k_host)
+        self._build_augmenter()
         print("Loaded {} {} samples".format(self.split, self.num_samples))
+
+    def _build_augmenter(self):
+        """--augment reference, train split: the device-side augmenter over the two patch banks (datasets/augment.py)."""
+        self.augmenter = None
+        if getattr(self.opt, "augment", "mirror") != "reference" or self.split != "train":
+            return
+        from .augment import PairViewAugmenter
+        self.augmenter = PairViewAugmenter(self.patches_2d, self.patches_3d, (self.mean_subvols, self.mean_subvols3d),
+                                           (self.std_subvols, self.std_subvols3d), self.seed)
 
     def set_epoch(self, epoch):
         self.epoch = epoch
@@ -162,6 +174,10 @@ class SimSiam2D3DDataset:
         for i in range(len(self)):
             idx = torch.as_tensor(order[i * self.batch_size:(i + 1) * self.batch_size], device=dev)
             v = var[idx]
+            if self.augmenter is not None:
+                x, x3, a, a3 = self.augmenter.views(idx, v, self.epoch)
+                yield {"input": x, "input_3d": x3, "input_aug": a, "input_aug_3d": a3}
+                continue
             yield {"input": self.normed_2d[idx, 0], "input_3d": self.normed_3d[idx, 0],
                    "input_aug": self.normed_2d[idx, v], "input_aug_3d": self.normed_3d[idx, v]}
 

@@ -69,7 +69,8 @@ _FLAGS = [
     ("--hipgraph", dict(dest="hipgraph", action="store_true", default=None)),
     ("--no_hipgraph", dict(dest="hipgraph", action="store_false")),
     # MI355X build only: the two views of the simsiam3d train split - the crop and its mirror image (default), or the reference's
-    # random chains on the crop and on a neighbouring centre's crop, drawn and applied on the device (datasets/augment.py)
+    # random chains on the crop and on a neighbouring centre's crop, drawn and applied on the device (datasets/augment.py); for
+    # the simsiam2d3d train split the unaugmented pairs (default) or the reference's chains on both channels of a pair
     ("--augment", dict(default="mirror", choices=["mirror", "reference"])),
 ]
 

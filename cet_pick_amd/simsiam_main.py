@@ -7,9 +7,10 @@ with SyncBN statistics.
 
 The crops come from the DoG picker and the crop kernels, on listed MRC files (datasets/tomo_files.py) or synthetic tomograms
 (datasets/synthetic_datasets.py); task simsiam2d3d pairs tilt-series and tomogram patches (datasets/simsiam2d3d.py).  The
-second view is the mirrored crop by default; `--augment reference` serves the reference's random views of the `simsiam3d`
-dataset (flips, brightness / contrast jitter, resized crop, quarter turns, a neighbouring centre for the second view),
-made on the device (datasets/augment.py).  The 2d3d chain's random rotation and corner erasing are out of scope.
+second view is the mirrored crop by default; `--augment reference` serves the reference's random views, made on the device
+(datasets/augment.py): of the `simsiam3d` dataset flips, brightness / contrast jitter, resized crop, quarter turns and a
+neighbouring centre for the second view; of the `simsiam2d3d` dataset flips, the 30-degree random rotation (first view),
+corner erasing and quarter turns, the same parameters for the tilt and the tomogram patch of a view.
 """
 import os
 import random

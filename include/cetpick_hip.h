@@ -197,6 +197,51 @@ int mi_aug2d_params(const int64_t* sample_ids, int64_t n, uint64_t seed, int epo
 int mi_aug2d_apply(const float* bank, int64_t n_samples, int n_banks, const int64_t* sample_ids, const int32_t* table,
                    int64_t n, int bbox, float mean, float std, float* out, mi_stream_t stream);
 
+/* Random views of the 2d3d dataset (datasets/tomo_pre_proj_angle_select_new2d3d.py:49-82: ToPILImage, RandomHorizontalFlip,
+ * RandomVerticalFlip, RandomRotation [strong chain only], CenterCrop(bbox), ToTensor, CornerErasing (utils/image.py:249-321),
+ * FixedRotation, Normalize) on the two-channel image (tilt patch, tomogram patch): one record acts on both channels.
+ *
+ * mi_aug2d3d_params draws table[v][t] = the record of sample sample_ids[t] for view v (0: `strong` ranges, 1: `weak`); table
+ * is (2, n, 16) int32.  A record, 16 x 32 bit:
+ *     word 0      bit 0 hflip, bit 1 vflip, bit 2 erase (CornerErasing acts); other bits reserved, 0
+ *     word 1      k in 0..3: quarter turns, orientation of torch.rot90(img, k, dims=[1, 2])
+ *     word 2, 3   i, j: top row and left column of the erased rectangle (they may lie outside the image)
+ *     word 4, 5   h, w: its height and width; drawn whether or not bit 2 is set
+ *     word 6      the rotation angle in degrees (float32 bits) = angle_lo + (angle_hi - angle_lo) u, not contracted
+ *     word 7      reserved, 0
+ *     word 8..13  a0..a5: the rotation as the imaging library's 16.16 fixed-point affine map (below), from word 6 in fp64
+ *     word 14, 15 reserved, 0
+ * hflip, vflip ~ Bernoulli(flip_p); erase ~ Bernoulli(erase_p); k uniform; with mid = bbox / 2, share ~ U(scale), aspect =
+ * exp(U(log ratio)): h = round(sqrt(bbox^2 share aspect)), w = round(sqrt(bbox^2 share / aspect)); i uniform in
+ * [0, max(1, mid - h - 6)) or in [mid + 6, max(mid + 7, bbox - h + 6)), a fair coin choosing, j likewise with w.
+ * The map of rotate(angle, NEAREST, expand=False, fill 0): t = -radians(angle mod 360), m0 = m4 = round(cos t, 15),
+ * m1 = round(sin t, 15), m3 = -m1, c = bbox / 2, m2 = m0 (-c) + m1 (-c) + c, m5 = m3 (-c) + m4 (-c) + c, FIX(v) =
+ * floor(65536 v + 0.5): a0, a1, a3, a4 = FIX(m0, m1, m3, m4), a2 = FIX(m2 + m0 / 2 + m1 / 2), a5 = FIX(m5 + m3 / 2 + m4 / 2);
+ * output pixel (y, x) is input pixel (row (a5 + a4 y + a3 x) >> 16, column (a2 + a1 y + a0 x) >> 16), 0 outside the image.
+ * Angle range (0, 0) gives the identity map (65536, 0, 32768, 0, 65536, 32768): the weak chain.
+ * The generator is Philox-4x32-10 with counter (sample id, epoch, view | draw << 8 | 0x2D3D0000) and key seed: a record is a
+ * pure function of (seed, epoch, sample id, view) and the ranges, and its stream is disjoint from mi_aug2d_params's.
+ * MI_E_ARG for ranges with which CornerErasing could reject its first try (h or w reaching mid at the ends of the ranges:
+ * the reference's retry loop and its fallback are not built); MI_E_UNSUPPORTED unless bbox is even and in 8..128.
+ *
+ * mi_aug2d3d_apply: all four tensors of a batch in one launch.  patches_2d, patches_3d: (n_samples, n_variants, bbox, bbox)
+ * fp32 in [0, 1].  View 0 of batch row t is made of variant 0 of sample sample_ids[t] with table_strong[t], view 1 of variant
+ * variants[t] with table_weak[t].  out is (4, n, bbox, bbox): view 0 channel 2d, view 0 channel 3d, view 1 channel 2d, view 1
+ * channel 3d.  Per output pixel: undo the quarter turn; inside the erased rectangle (clipped to the image) the level is 255;
+ * else apply the map - outside the image the level is 0, inside it is floor(255 x) (x clamped to [0, 1]) of the source pixel
+ * with the flips undone; out = (level / 255 - mean_c) / std_c.  A sample id outside [0, n_samples) or a variant outside
+ * [0, n_variants) gives NaN rows and no read; whatever a record holds, no read leaves the patch.  The tables must be 16-byte
+ * aligned. */
+typedef struct mi_aug2d3d_ranges {
+    float flip_p, angle_lo, angle_hi, erase_p, scale_lo, scale_hi, ratio_lo, ratio_hi;
+} mi_aug2d3d_ranges;
+int mi_aug2d3d_params(const int64_t* sample_ids, int64_t n, uint64_t seed, int epoch, int bbox,
+                      const mi_aug2d3d_ranges* strong, const mi_aug2d3d_ranges* weak, int32_t* table, mi_stream_t stream);
+int mi_aug2d3d_apply(const float* patches_2d, const float* patches_3d, int64_t n_samples, int n_variants,
+                     const int64_t* sample_ids, const int64_t* variants, const int32_t* table_strong,
+                     const int32_t* table_weak, int64_t n, int bbox, float mean_2d, float std_2d, float mean_3d, float std_3d,
+                     float* out, mi_stream_t stream);
+
 /* Tilt-series patches of the 2d3d exploration mode (datasets/tomo_pre_proj_angle_select_new2d3d.py:91-133
  * `convert_tomo_to_tilt` + `extract_patches`), one per centre.  Centre i = (x, y, z_full) of stack owner[i]
  * (owner == NULL: stack 0).  For every tilt t of that stack, in order:

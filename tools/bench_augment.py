@@ -1,6 +1,6 @@
-"""Cost of the device-side view augmentation (csrc/augment2d.hip), one JSON line:
+"""Cost of the device-side view augmentation (csrc/augment2d.hip, csrc/augment2d3d.hip), one JSON line:
 
-    python tools/bench_augment.py [--batch 256] [--bbox 36] [--rounds 5] [--small]
+    python tools/bench_augment.py [--task simsiam3d|simsiam2d3d] [--batch 256] [--bbox 36] [--rounds 5] [--small]
 
   launches_us     the four launches of one batch (two mi_aug2d_params + two mi_aug2d_apply) alone: HIP events around
                   `ViewAugmenter.views`, median of 200 calls after a warm-up (includes the four output allocations)
@@ -10,6 +10,10 @@
                   batch copy, hipGraph replay, meters) with `--augment mirror` and with `--augment reference`, same
                   process, same synthetic tomograms, alternating epochs, --rounds epochs each; `mirror_spread` is the
                   spread between the repeated mirror epochs, the yardstick for the difference
+
+--task simsiam2d3d: the same for the 2d3d mode (simsiam2d3d_18 on tilt + tomogram patch pairs).  `launches_us` is then the
+two launches of a batch (mi_aug2d3d_params + mi_aug2d3d_apply, all four tensors) around `PairViewAugmenter.views`,
+`params_us` / `apply_us` each launch alone, and `mirror` stands for the unaugmented pairs (the step without the flag).
 """
 import argparse
 import json
@@ -40,6 +44,25 @@ def _build(augment, batch, bbox, small):
     return trainer, ds
 
 
+def _build_2d3d(augment, batch, bbox, small):
+    from cet_pick_amd.datasets.simsiam2d3d import SyntheticSimSiam2D3DDataset
+    from cet_pick_amd.models.model import create_model
+    from cet_pick_amd.opts import opts
+    from cet_pick_amd.trains.train_factory import train_factory
+    opt = opts().parse(["simsiam2d3d", "--arch", "simsiam2d3d_18", "--dataset", "simsiam2d3d", "--bbox", str(bbox), "--batch_size",
+                        str(batch), "--lr", "0.001", "--debug", "0", "--augment", augment, "--exp_id", "bench_augment2d3d"])
+    opt = opts().update_dataset_info_and_set_heads(opt, SyntheticSimSiam2D3DDataset)
+    torch.manual_seed(opt.seed)
+    model = create_model(opt.arch, opt.heads, opt.head_conv)
+    trainer = train_factory[opt.task](opt, model, torch.optim.SGD(model.parameters(), opt.lr))
+    trainer.set_device(opt.gpus, opt.chunk_sizes, torch.device("cuda"))
+    shape, n_tomos = ((32, 256, 256), 2) if small else ((48, 384, 384), 4)
+    ds = SyntheticSimSiam2D3DDataset(opt, "train", (3, bbox, bbox), sigma1=opt.dog, shape=shape, n_tomos=n_tomos)
+    if len(ds) == 0:
+        raise SystemExit("the synthetic 2d3d dataset has %d samples, fewer than one batch of %d" % (ds.num_samples, batch))
+    return trainer, ds
+
+
 def _events_us(fn, reps):
     times = []
     for _ in range(reps):
@@ -54,6 +77,7 @@ def _events_us(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--task", default="simsiam3d", choices=["simsiam3d", "simsiam2d3d"])
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--bbox", type=int, default=36)
     ap.add_argument("--rounds", type=int, default=5)
@@ -61,23 +85,35 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the MI355X"
     from cet_pick_amd.datasets import augment as A
-    runs = {m: _build(m, a.batch, a.bbox, a.small) for m in ("mirror", "reference")}
+    build = _build_2d3d if a.task == "simsiam2d3d" else _build
+    runs = {m: build(m, a.batch, a.bbox, a.small) for m in ("mirror", "reference")}
     ds = runs["reference"][1]
-    out = {"batch": a.batch, "bbox": a.bbox, "samples": int(ds.num_samples), "iterations_per_epoch": len(ds)}
+    out = {"task": a.task, "batch": a.batch, "bbox": a.bbox, "samples": int(ds.num_samples), "iterations_per_epoch": len(ds)}
 
     # (a) the launches alone
     ids = torch.randperm(ds.num_samples, device="cuda")[:a.batch].contiguous()
-    for _ in range(20):
-        ds.augmenter.views(ids, 0)
-    torch.cuda.synchronize()
-    out["launches_us"] = _events_us(lambda: ds.augmenter.views(ids, 0), 200)
-    t = A.draw_params(ids, 317, 0, A.STRONG, a.bbox)
-    out["params_us"] = _events_us(lambda: A.draw_params(ids, 317, 0, A.STRONG, a.bbox), 200)
-    out["apply_us"] = {}
-    for k in range(4):
-        tk = t.clone()
-        tk[:, 6] = k
-        out["apply_us"]["k%d" % k] = _events_us(lambda: A.apply(ds.sub_vols_3d, ids, tk, ds.mean_subvols3d, ds.std_subvols3d), 200)
+    if a.task == "simsiam2d3d":
+        aug = ds.augmenter
+        var = torch.as_tensor(ds.epoch_views()[1], device="cuda")[ids].contiguous()
+        for _ in range(20):
+            aug.views(ids, var, 0)
+        torch.cuda.synchronize()
+        out["launches_us"] = _events_us(lambda: aug.views(ids, var, 0), 200)
+        t = A.draw_params_2d3d(ids, 317, 0, a.bbox)
+        out["params_us"] = _events_us(lambda: A.draw_params_2d3d(ids, 317, 0, a.bbox), 200)
+        out["apply_us"] = _events_us(lambda: A.apply_2d3d(aug.patches_2d, aug.patches_3d, ids, var, t, aug.means, aug.stds), 200)
+    else:
+        for _ in range(20):
+            ds.augmenter.views(ids, 0)
+        torch.cuda.synchronize()
+        out["launches_us"] = _events_us(lambda: ds.augmenter.views(ids, 0), 200)
+        t = A.draw_params(ids, 317, 0, A.STRONG, a.bbox)
+        out["params_us"] = _events_us(lambda: A.draw_params(ids, 317, 0, A.STRONG, a.bbox), 200)
+        out["apply_us"] = {}
+        for k in range(4):
+            tk = t.clone()
+            tk[:, 6] = k
+            out["apply_us"]["k%d" % k] = _events_us(lambda: A.apply(ds.sub_vols_3d, ids, tk, ds.mean_subvols3d, ds.std_subvols3d), 200)
 
     # (b) the training iteration, alternating
     ms = {m: [] for m in runs}
