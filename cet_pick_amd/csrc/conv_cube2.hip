@@ -19,13 +19,12 @@
 // reducing a whole tile in one launch - no slabs, epilogue in the kernel - were measured: 64 workgroups on 64 CUs take
 // 20.7 / 24.5 us against 10.5 + 4.2 us for this form.)
 #include "common.h"
+#include "bf16x3.h"
 #include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int KQ = 4;                       // reduction quarters (split-K slabs); x 4 waves = 16 parts
 
@@ -42,31 +41,6 @@ struct Cube2Params {
     const float* mask;        // out *= (mask > 0)             (may be null)
     int relu;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of2(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-
-// exact three-way bf16 cut of 8 f32 (truncation, as conv_igemm.hip / conv_direct3.hip)
-__device__ __forceinline__ void cut8r(const float (&v)[8], bf16x8 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-    u32x4 p0, p1, p2;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        p0[d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        p1[d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        p2[d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-    o[0] = __builtin_bit_cast(bf16x8, p0); o[1] = __builtin_bit_cast(bf16x8, p1); o[2] = __builtin_bit_cast(bf16x8, p2);
-}
 
 // tap index of the pair (voxel on the reduction side kv, voxel on the column side cv): per axis t = in - out + 1
 __device__ __forceinline__ int pair_tap(int in_v, int out_v) {
@@ -91,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void cube2_kernel(Cube2Params p) {
     const int cbi = blockIdx.x, q = blockIdx.y, mt = blockIdx.z;
     const int cv = cbi / cpb, cc0 = (cbi % cpb) * 32;    // column side: voxel cv, channels cc0 .. cc0 + 31
     const int n0 = mt * 64;
-    const __amdgpu_buffer_rsrc_t ars = rsrc_of2(p.a, p.a_bytes), wrs = rsrc_of2(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t ars = rsrc(p.a, p.a_bytes), wrs = rsrc(p.w, p.w_bytes);
 
     // k-steps of this wave: global k-step g = (q * 4 + wave) * NS + s covers reduction voxel kv = g / (C / 16), channels
     // kc0 = (g % (C / 16)) * 16 .. + 15; this lane's 8 are kc0 + 8 h ..
@@ -138,7 +112,6 @@ __global__ __launch_bounds__(256, 2) void cube2_kernel(Cube2Params p) {
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     auto fetch_dyn = [&](int s) {
         switch (s % PD) {
@@ -159,11 +132,11 @@ __global__ __launch_bounds__(256, 2) void cube2_kernel(Cube2Params p) {
         for (int rb = 0; rb < 2; ++rb) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(araw[s % PD][rb][0][e]); v[4 + e] = __uint_as_float(araw[s % PD][rb][1][e]); }
-            cut8r(v, af[rb]);
+            cut8(v, af[rb]);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = __uint_as_float(braw[s % PD][e]);
-        cut8r(v, bf);
+        cut8(v, bf);
 #pragma unroll
         for (int pr = 0; pr < 6; ++pr) {
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][PA[pr]], bf[PB[pr]], acc[0], 0, 0, 0);
@@ -215,8 +188,6 @@ __global__ __launch_bounds__(256, 2) void cube2_kernel(Cube2Params p) {
     }
 }
 
-
-
 // ---- weight gradient of the convolutions whose OUTPUT is a 2 x 2 x 2 volume (round 3) -----------------------------------------
 // layer3 / feature_3d (256 -> 256 on 2^3, stride 1: four launches per step) and layer3.0.conv1 (128 -> 256, 4^3 -> 2^3, stride 2)
 // of the MoCo-3D encoder (moco_encoder_3d.py:55-84,172,178).  dW[tap][ci][co] = sum over samples n and over the (input voxel vi,
@@ -252,9 +223,6 @@ struct PairWgradParams {
     unsigned char lo[PW_MAXTAP][3], len[PW_MAXTAP][3];   // [tap][z, y, x]
 };
 
-typedef __bf16 bf16x4w __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4w lds_bf16x4w;
-
 __global__ __launch_bounds__(512, 2) void pair_wgrad_kernel(PairWgradParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * PW_OP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -276,7 +244,7 @@ __global__ __launch_bounds__(512, 2) void pair_wgrad_kernel(PairWgradParams p) {
     const int lz = p.lo[tap][0], ly = p.lo[tap][1], lx = p.lo[tap][2], ny = p.len[tap][1], nx = p.len[tap][2];
 
     // staging: thread = (sample row, 8 channels): one unit of X and one of dY per block
-    const __amdgpu_buffer_rsrc_t xrs = rsrc_of2(p.x[blockIdx.y], p.x_bytes), yrs = rsrc_of2(p.dy[blockIdx.y], p.dy_bytes);
+    const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x[blockIdx.y], p.x_bytes), yrs = rsrc(p.dy[blockIdx.y], p.dy_bytes);
     const int srow = tid >> 3, cg = tid & 7;
     const int st_lds = (cg >> 2) * PW_HALF + srow * PW_ROW + (cg & 3) * 16;
     // three blocks in flight: an iteration (12 MFMAs per wave) is far shorter than an L2 / HBM round trip
@@ -313,7 +281,7 @@ __global__ __launch_bounds__(512, 2) void pair_wgrad_kernel(PairWgradParams p) {
                 v[4 + e] = __uint_as_float(op ? ldy[S][1][e] : ldx[S][1][e]);
             }
             bf16x8 o[3];
-            cut8r(v, o);
+            cut8(v, o);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
                 *reinterpret_cast<u32x4*>(lds + boff + op * PW_OP + pl * PW_PLANE + st_lds) = __builtin_bit_cast(u32x4, o[pl]);
@@ -329,7 +297,6 @@ __global__ __launch_bounds__(512, 2) void pair_wgrad_kernel(PairWgradParams p) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     auto multiply = [&](int boff) {
 #pragma unroll
@@ -339,10 +306,10 @@ __global__ __launch_bounds__(512, 2) void pair_wgrad_kernel(PairWgradParams p) {
             for (int pl = 0; pl < 3; ++pl) {
                 const unsigned char* ap = lds + boff + a_base + pl * PW_PLANE + ks * 16 * PW_ROW;
                 const unsigned char* bp = lds + boff + b_base + pl * PW_PLANE + ks * 16 * PW_ROW;
-                const bf16x4w alo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4w*)(ap));
-                const bf16x4w ahi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4w*)(ap + 4 * PW_ROW));
-                const bf16x4w blo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4w*)(bp));
-                const bf16x4w bhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4w*)(bp + 4 * PW_ROW));
+                const bf16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(ap));
+                const bf16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(ap + 4 * PW_ROW));
+                const bf16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(bp));
+                const bf16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(bp + 4 * PW_ROW));
                 af[pl] = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
                 bf[pl] = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
             }
@@ -423,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void small_gemm_kernel(SmallGemmParams p) {
     const int h = lane >> 5, l32 = lane & 31;
     const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 64;
     const int KT = (p.K + 15) >> 4;
-    const __amdgpu_buffer_rsrc_t ars = rsrc_of2(p.a, p.a_bytes), brs = rsrc_of2(p.b, p.b_bytes);
+    const __amdgpu_buffer_rsrc_t ars = rsrc(p.a, p.a_bytes), brs = rsrc(p.b, p.b_bytes);
     constexpr int PD = NS < 4 ? NS : 4;
     unsigned araw[PD][2][8], braw[PD][8];
     const bool col_ok = n0 + l32 < p.N;
@@ -470,7 +437,6 @@ __global__ __launch_bounds__(256, 2) void small_gemm_kernel(SmallGemmParams p) {
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     auto step = [&](auto Uc) {
         constexpr int U = decltype(Uc)::value, SET = U % PD;
         if constexpr (U < NS) {
@@ -482,11 +448,11 @@ __global__ __launch_bounds__(256, 2) void small_gemm_kernel(SmallGemmParams p) {
                 for (int rb = 0; rb < 2; ++rb) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = __uint_as_float(araw[SET][rb][e]);
-                    cut8r(v, af[rb]);
+                    cut8(v, af[rb]);
                 }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = __uint_as_float(braw[SET][e]);
-                cut8r(v, bf);
+                cut8(v, bf);
 #pragma unroll
                 for (int pr = 0; pr < 6; ++pr) {
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][PA[pr]], bf[PB[pr]], acc[0], 0, 0, 0);
@@ -573,7 +539,6 @@ bool mi_cube2_usable(int N, int Di, int Hi, int Wi, int Ci, int Co, int kd, int 
     if (Ci != 128 && Ci != 256 && Ci != 512) return false;                    // k-steps per wave = C / 32: 4, 8, 16
     return N >= 1 && 4l * N * 8 * Ci < 0x7fff0000l;
 }
-
 
 // weight gradient through pair_wgrad_kernel: k^3 window (k = 3, pad 1 or k = 1, pad 0), cubic volumes, stride 1 or 2, channels multiples
 // of 64.  Round 3: outputs of 2 x 2 x 2 (layer3).  Round 4: any cubic output up to 8^3 - layer2 (4^3, up to 64 pairs per tap), layer2.0's

@@ -17,39 +17,17 @@
 //   * epilogue: + bias (folded BatchNorm), ReLU, 128-byte rows of 32 channels.
 // f32-equivalent bf16x3 arithmetic (six products of the exact three-way cut, f32 accumulation), as every convolution here.
 #include "common.h"
+#include "bf16x3.h"
 #include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int DCO = 32;                     // output channels of the 32-column form (CO = 64: two column halves per wave)
 constexpr int DW_BLK = 1024;                // one B fragment plane: 64 lanes x 16 bytes
 constexpr int DW_STEP = 3 * DW_BLK;         // bytes per k-step and 32-column half of the weight image
 constexpr int DRB = 6;                      // weight k-steps in flight (32 columns; 64 columns: 3 - the ring is 2 x 3 fragments per k-step)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t d_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void d_cut8(const float (&v)[8], u32x4 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        o[0][d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        o[1][d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        o[2][d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-}
 
 struct D32Params {
     const float* x;           // (N, D, H, W, CIN) channels-last
@@ -122,7 +100,7 @@ __global__ __launch_bounds__(256, (D32Cfg<CIN, NZT, DIL, CO, TYT, KSZ>::LDS <= 8
     constexpr bool LOOPCB = KSZ == 1 && G::NPH == 1 && CO == 64;
     const int ncb = LOOPCB ? p.co_total / CO : 1;
     int co0 = blockIdx.y * CO;
-    __amdgpu_buffer_rsrc_t wrs = d_rsrc(p.wimg + (size_t)blockIdx.y * p.w_bytes, p.w_bytes);
+    __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg + (size_t)blockIdx.y * p.w_bytes, p.w_bytes);
     bf16x8 bfr[G::RB][G::NCH][3];
     auto wload = [&](int g, auto SLOTc) {
         constexpr int SLOT = decltype(SLOTc)::value % G::RB;
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(256, (D32Cfg<CIN, NZT, DIL, CO, TYT, KSZ>::LDS <= 8
     // ---- the patch, every chunk of a phase at once: unit q = (voxel, chunk, k-half); voxels outside the volume read zeros (the padding).
     //      (256 input channels: two phases of 128 - the second patch overwrites the first behind a barrier, the accumulators stay) ----
     auto stage = [&](int ph) {
-        const __amdgpu_buffer_rsrc_t xrs = d_rsrc(p.x, p.x_bytes);
+        const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x, p.x_bytes);
         u32x4 ld[G::UNITS][2];
         int dst[G::UNITS];
 #pragma unroll
@@ -172,7 +150,7 @@ __global__ __launch_bounds__(256, (D32Cfg<CIN, NZT, DIL, CO, TYT, KSZ>::LDS <= 8
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(ld[u][0][e]); v[4 + e] = __uint_as_float(ld[u][1][e]); }
             u32x4 o[3];
-            d_cut8(v, o);
+            cut8(v, o);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(patch + dst[u] + pl * G::PL) = o[pl];
         }
@@ -189,7 +167,6 @@ __global__ __launch_bounds__(256, (D32Cfg<CIN, NZT, DIL, CO, TYT, KSZ>::LDS <= 8
         vbase[i] = ((bz_[i] * G::PY + by_[i] + (l32 >> 3)) * G::PX + bx_[i] + (l32 & 7)) * 16 + h * G::ARR;
     }
     f32x16 acc[G::BPW][G::NCH];
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     __syncthreads();
 
     bf16x8 af[2][G::BPW][3];
@@ -207,11 +184,11 @@ __global__ __launch_bounds__(256, (D32Cfg<CIN, NZT, DIL, CO, TYT, KSZ>::LDS <= 8
         if (g & 1) frags(c, tap, std::integral_constant<int, 1>{});
         else frags(c, tap, std::integral_constant<int, 0>{});
     };
-    const __amdgpu_buffer_rsrc_t ors = d_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t ors = rsrc(p.out, p.out_bytes);
   for (int cb = 0; cb < ncb; ++cb) {
     if (LOOPCB && cb > 0) {                                      // next 64-column block: its image, its ring
         co0 = cb * CO;
-        wrs = d_rsrc(p.wimg + (size_t)cb * p.w_bytes, p.w_bytes);
+        wrs = rsrc(p.wimg + (size_t)cb * p.w_bytes, p.w_bytes);
 #pragma unroll
         for (int g = 0; g < G::RB - 1; ++g) wload_dyn(g);
     }
@@ -294,7 +271,7 @@ __global__ __launch_bounds__(256, (D32Cfg<CIN, NZT, DIL, CO, TYT, KSZ>::LDS <= 8
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ors, (int)off, 0, 0);
             }
             if (NZT == 1 && DIL == 1 && KSZ == 3 && p.pool) {          // (uniform) the 2 x 2 windows of this lane's 4 x 4 patch
-                const __amdgpu_buffer_rsrc_t prs = d_rsrc(p.pool, p.pool_bytes);
+                const __amdgpu_buffer_rsrc_t prs = rsrc(p.pool, p.pool_bytes);
                 const int hp = p.H >> 1, wp = p.W >> 1;
 #pragma unroll
                 for (int py = 0; py < 2; ++py)
@@ -326,10 +303,9 @@ __global__ __launch_bounds__(256) void conv_d32_prep_kernel(const float* w, unsi
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = w[((long)tap * cin + k0 + e) * co + nn];
     u32x4 o[3];
-    d_cut8(v, o);
+    cut8(v, o);
     unsigned char* dst = img + (size_t)blockIdx.y * ((size_t)ks * ntap * nch * DW_STEP) + (size_t)((c * ntap + tap) * nch + ch) * DW_STEP + lane * 16;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * DW_BLK) = o[pl];
+    store_planes(dst, DW_BLK, o);
 }
 
 }  // namespace

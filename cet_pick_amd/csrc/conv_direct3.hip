@@ -1,5 +1,5 @@
 // Direct 3x3x3 / stride 1 / padding 1 convolution for 64 -> 64 channels on (N, D, 8, 8, 64) channels-last activations,
-// forward and data-gradient form, in the bf16x3 arithmetic of conv_igemm.hip (three-way exact bf16 cut of both operands,
+// forward and data-gradient form, in the bf16x3 arithmetic of bf16x3.h (three-way exact bf16 cut of both operands,
 // six bf16 MFMA products per f32 product, f32 accumulate).  This is layer1 of the MoCo-3D encoder
 // (cet_pick/models/networks/moco_encoder_3d.py:55-84,170 - four such convolutions per encoder pass): 12 of the 75 conv
 // launches of a training step and the largest share of its time.
@@ -27,14 +27,13 @@
 // DGRAD is the same kernel on dY with the weight image built transposed and tap-flipped:
 //   dX[i] = sum_t dY[i + 1 - t] W[t]^T = sum_t' dY[i + t' - 1] W[2 - t']^T.
 #include "common.h"
+#include "bf16x3.h"
 #include <type_traits>
 #include <algorithm>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int C = 64;                       // channels, in = out
 constexpr int PLANE = 64;                   // voxels of an 8 x 8 z-plane
@@ -71,31 +70,6 @@ struct Direct3Params {
     unsigned a_bytes;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-
-// exact three-way bf16 cut of 8 consecutive f32 (truncation keeps every step exact, conv_igemm.hip): planes o[0..2],
-// element e in half (e & 1) of dword e / 2
-__device__ __forceinline__ void cut8(const float (&v)[8], u32x4 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        const float r2 = r1 - __uint_as_float(u1[t] & 0xffff0000u);
-        u2[t] = __float_as_uint(r2);
-    }
-    constexpr unsigned HI2 = 0x07060302u;   // v_perm_b32: high halves of two dwords -> one dword (first element low)
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        o[0][d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        o[1][d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        o[2][d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-}
-
 // (Measured and rejected: eight waves per workgroup - two quartets splitting the reduction over the same tile, two waves
 // per SIMD, partial sums exchanged through LDS at the end - 36.9 us against 32.3 us for this form.)
 // TWO: only two channel chunks of the patch are resident (a ring of two slots: 59 KB), the residual / mask operands of the
@@ -116,7 +90,7 @@ __global__ __launch_bounds__(256, TWO ? 2 : 1) void direct3_kernel(Direct3Params
     const int z0 = zb * TZ;
 
     const int cb = blockIdx.y;                           // 64-channel block of the output channels
-    const __amdgpu_buffer_rsrc_t wrs = rsrc_of(p.wimg, (CT / 64) * NSTEP * WSTEP);
+    const __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg, (CT / 64) * NSTEP * WSTEP);
     const int w_voff = cw * (3 * WBLK) + lane * 16;
     const int w_cb = cb * (NSTEP * WSTEP);
     // weight fragments of k-step g (0..107; behind the image: zeros) -> ring slot g % RB
@@ -143,7 +117,7 @@ __global__ __launch_bounds__(256, TWO ? 2 : 1) void direct3_kernel(Direct3Params
 
     // ---- patch staging, one 16-channel chunk at a time: unit q = (voxel, k-half); 2 units per thread and chunk.
     // Chunk 0 is staged here; chunk c + 1 is loaded and cut in the shadow of chunk c's MFMAs.
-    const __amdgpu_buffer_rsrc_t ars = rsrc_of(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ars = rsrc(p.a, p.a_bytes);
     unsigned st_off[2];
     int st_lds[2];
 #pragma unroll
@@ -206,7 +180,6 @@ __global__ __launch_bounds__(256, TWO ? 2 : 1) void direct3_kernel(Direct3Params
     f32x16 acc[2];                      // (two chains per row block measured: no faster)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // smallest products first
 
     // epilogue operands (residual, mask), fetched during the last chunk; a null pointer reads zeros (empty descriptor)
     const long m0 = ((long)n * p.D + z0 + tz) * PLANE;
@@ -217,7 +190,7 @@ __global__ __launch_bounds__(256, TWO ? 2 : 1) void direct3_kernel(Direct3Params
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) eoff[i][r] = 4u * (unsigned)((m0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h) * CT + col);
-    const __amdgpu_buffer_rsrc_t rrs = rsrc_of(p.res, p.res ? p.a_bytes : 0u), mrs = rsrc_of(p.mask, p.mask ? p.a_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rrs = rsrc(p.res, p.res ? p.a_bytes : 0u), mrs = rsrc(p.mask, p.mask ? p.a_bytes : 0u);
 
     stage_store(0);
     stage_load(1);
@@ -373,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void direct3h_kernel(Direct3hParams p) {
     const int zb = bi % (p.D / TZ), n = bi / (p.D / TZ);
     const int z0 = zb * TZ, y0 = by * 8, x0 = bx * 8;
 
-    const __amdgpu_buffer_rsrc_t wrs = rsrc_of(p.wimg, WIMG_BYTES);
+    const __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg, WIMG_BYTES);
     const int w_voff = cw * (3 * WBLK) + lane * 16;
     bf16x8 bfr[RB][3];
     auto wload = [&](int g, auto SLOTc) {
@@ -396,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void direct3h_kernel(Direct3hParams p) {
     for (int g = 0; g < RB - 1; ++g) wload_dyn(g);
 
     // ---- patch staging, one 16-channel chunk at a time: unit q = (patch voxel, k-half); voxels outside the volume read zeros ----
-    const __amdgpu_buffer_rsrc_t ars = rsrc_of(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ars = rsrc(p.a, p.a_bytes);
     unsigned st_off[H_UNITS];
     int st_lds[H_UNITS];
 #pragma unroll
@@ -443,9 +416,8 @@ __global__ __launch_bounds__(256, 2) void direct3h_kernel(Direct3hParams p) {
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     const int col = cw * 32 + l32;
-    const __amdgpu_buffer_rsrc_t rrs = rsrc_of(p.res, p.res ? p.a_bytes : 0u), mrs = rsrc_of(p.mask, p.mask ? p.a_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rrs = rsrc(p.res, p.res ? p.a_bytes : 0u), mrs = rsrc(p.mask, p.mask ? p.a_bytes : 0u);
 
     stage_store(0);
     stage_load(1);
@@ -551,9 +523,7 @@ __device__ void direct3_prep_body(const float* w, unsigned char* img, int dgrad,
     const int nn = cb * 64 + cw * 32 + (lane & 31), k0 = ks * 16 + 8 * (lane >> 5);
     float v[8];
     if (dgrad) {        // B'[tap][k = co][n = ci] = W[26 - tap][ci = n][co = k]
-        const float* src = w + ((long)(NTAP - 1 - tap) * CT + nn) * CT + k0;
-        const float4 a = *reinterpret_cast<const float4*>(src), c = *reinterpret_cast<const float4*>(src + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+        ld8(w + ((long)(NTAP - 1 - tap) * CT + nn) * CT + k0, v);
     } else {            // B[tap][k = ci][n = co] = W[tap][ci = k][co = n]
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = w[((long)tap * CT + k0 + e) * CT + nn];
@@ -561,8 +531,7 @@ __device__ void direct3_prep_body(const float* w, unsigned char* img, int dgrad,
     u32x4 o[3];
     cut8(v, o);
     unsigned char* dst = img + (long)(((cb * KSn + ks) * NTAP + tap) * 2 + cw) * (3 * WBLK) + lane * 16;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * WBLK) = o[pl];
+    store_planes(dst, WBLK, o);
 }
 // one launch cuts every image of a batch, all formats: blockIdx.y = image, blockIdx.x = its blocks (the 64-channel format
 // uses the first 54 of them).  wide: 0 = direct3_kernel 64 channels, 1 = direct3s_kernel 128, 2 = direct3_kernel 128, 3 = direct3s_kernel 256
@@ -573,7 +542,6 @@ __global__ __launch_bounds__(256) void direct3_prep_kernel(PrepBatch b) {
     else if (fmt == 3) direct3s256_prep_body(b.w[blockIdx.y], b.img[blockIdx.y], b.dgrad[blockIdx.y], idx);
     else if (blockIdx.x < PREP_BLOCKS) direct3_prep_body<C>(b.w[blockIdx.y], b.img[blockIdx.y], b.dgrad[blockIdx.y], idx);
 }
-
 
 // ---- weight gradient of the same convolutions -----------------------------------------------------------------------
 //   dW[tap][ci][co] = sum over output voxels m of X[m + tap - 1][ci] * dY[m][co]
@@ -607,9 +575,6 @@ struct Direct3WgradParams {
     int nprob, splits;        // workgroups per (dz, dy) pair = nprob * splits
     int H, W;                 // TILED: the plane (multiples of 8); a unit is an 8 x 8 tile of it
 };
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 // Round 4: EIGHT waves per workgroup, two per SIMD: waves 0-3 take k-steps 0-1 of every plane and waves 4-7 k-steps 2-3 (same
 // four 32 x 32 blocks, same three taps); the staging of a plane is shared by 512 threads (one unit of X and one of dY each), and
@@ -649,7 +614,7 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
     const int n_planes = p.N * p.D * tiles;            // units: V4: D = 1, a "plane" is a sample; TILED: the 8 x 8 tiles of every plane
 
     // ---- staging: a thread's unit = (voxel, 8 channels) of X and the same unit of dY: 64 voxels x 8 channel groups ----
-    const __amdgpu_buffer_rsrc_t xrs = rsrc_of(p.x[pb], p.bytes), yrs = rsrc_of(p.dy[pb], p.bytes);
+    const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x[pb], p.bytes), yrs = rsrc(p.dy[pb], p.bytes);
     const int st_vox = tid >> 3, st_cg = tid & 7;
     const unsigned st_src = TILED ? 4u * (unsigned)(((st_vox >> 3) * p.W + (st_vox & 7)) * C + st_cg * 8)
                                   : 4u * (unsigned)(st_vox * CT + st_cg * 8);
@@ -669,7 +634,6 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
         return -1;
     };
     u32x4 ldx[2], ldy[2];
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     u32x2 ldh = {0u, 0u};
     // byte offsets of unit pi's operands: dY tile, X tile (TILED: + this thread's halo element), 0x80000000 = nothing to fetch (zeros)
     unsigned u_y, u_x, u_h;
@@ -701,13 +665,10 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
     // TILED: the halo unit's two floats cut into three bf16 planes, one 4-byte store per plane
     unsigned hcu[3];
     auto halo_cut = [&]() {
-        const float a = __uint_as_float(ldh[0]), b = __uint_as_float(ldh[1]);
-        const float a1 = a - __uint_as_float(ldh[0] & 0xffff0000u), b1 = b - __uint_as_float(ldh[1] & 0xffff0000u);
-        const float a2 = a1 - __uint_as_float(__float_as_uint(a1) & 0xffff0000u), b2 = b1 - __uint_as_float(__float_as_uint(b1) & 0xffff0000u);
-        constexpr unsigned HI2 = 0x07060302u;
-        hcu[0] = __builtin_amdgcn_perm(ldh[1], ldh[0], HI2);
-        hcu[1] = __builtin_amdgcn_perm(__float_as_uint(b1), __float_as_uint(a1), HI2);
-        hcu[2] = __builtin_amdgcn_perm(__float_as_uint(b2), __float_as_uint(a2), HI2);
+        const unsigned a1 = rest(ldh[0]), b1 = rest(ldh[1]), a2 = rest(a1), b2 = rest(b1);
+        hcu[0] = pack2(ldh[1], ldh[0]);
+        hcu[1] = pack2(b1, a1);
+        hcu[2] = pack2(b2, a2);
     };
     auto halo_store = [&](int buf) {
 #pragma unroll
@@ -766,7 +727,6 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
     for (int t = 0; t < 3; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     // zero rows of both buffers, both operands, all planes and halves
     for (int i = tid; i < 2 * 2 * 3 * 2 * (WROW / 16); i += 512) {
@@ -824,7 +784,7 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
             o[0] = c[0] << 16;
 #pragma unroll
             for (int j = 1; j < 4; ++j) o[j] = __builtin_amdgcn_alignbit(c[j], c[j - 1], 16);
-            if (V4) o[2] &= 0xffff0000u;               // element 4 = x 0 of the second row: nothing to its left
+            if (V4) o[2] &= HI16;                     // element 4 = x 0 of the second row: nothing to its left
             if (TILED) o[0] |= hl[set][0][pl];         // element 0 <- X[.][x0 - 1]
         } else {
 #pragma unroll
@@ -841,19 +801,14 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
     // then pack + store of plane pl
     unsigned cu[3][8];
     auto cut_a = [&](int op, int e) {
-        const float x = __uint_as_float(op ? ldy[e >> 2][e & 3] : ldx[e >> 2][e & 3]);
-        cu[0][e] = __float_as_uint(x);
-        cu[1][e] = __float_as_uint(x - __uint_as_float(cu[0][e] & 0xffff0000u));
+        cu[0][e] = op ? ldy[e >> 2][e & 3] : ldx[e >> 2][e & 3];
+        cu[1][e] = rest(cu[0][e]);
     };
-    auto cut_b = [&](int e) {
-        const float r1 = __uint_as_float(cu[1][e]);
-        cu[2][e] = __float_as_uint(r1 - __uint_as_float(cu[1][e] & 0xffff0000u));
-    };
+    auto cut_b = [&](int e) { cu[2][e] = rest(cu[1][e]); };
     auto store_piece = [&](int buf, int op, int pl) {
-        constexpr unsigned HI2 = 0x07060302u;
         u32x4 o;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) o[d] = __builtin_amdgcn_perm(cu[pl][2 * d + 1], cu[pl][2 * d], HI2);
+        for (int d = 0; d < 4; ++d) o[d] = pack2(cu[pl][2 * d + 1], cu[pl][2 * d]);
         *reinterpret_cast<u32x4*>(lds + buf * WBUF + op * WOP + st_lds + pl * WPL) = o;
     };
 
@@ -930,7 +885,6 @@ __global__ __launch_bounds__(512, 2) void direct3_wgrad_kernel(Direct3WgradParam
     }
 }
 
-
 // ---- layer2-shaped convolutions: 3^3 / stride 1 / padding 1, 128 -> 128 channels on 4 x 4 x 4 volumes --------------------
 // (moco_encoder_3d.py:55-84,171: three of them per encoder pass, 9 forward / data-gradient launches per step.)  M is small
 // (64 voxels per sample), so the parallelism comes from the reduction - and since round 4 the reduction is split INSIDE the
@@ -986,7 +940,7 @@ __global__ __launch_bounds__(256, 1) void direct3s_kernel(Direct3sParams p) {
     const int h = lane >> 5, l32 = lane & 31;
     const int ct = blockIdx.x % NCB, n0 = blockIdx.x / NCB;           // column block of 32 output channels, sample
 
-    const __amdgpu_buffer_rsrc_t wrs = rsrc_of(p.wimg, NCB * S_STEPS * WST);
+    const __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg, NCB * S_STEPS * WST);
     const int w_voff = ct * (3 * WBLK) + lane * 16;
     int w_soff = cc * (S_STEPS * WST);
     bf16x8 bfr[RB][3];
@@ -1009,7 +963,7 @@ __global__ __launch_bounds__(256, 1) void direct3s_kernel(Direct3sParams p) {
             default: wload(g, std::integral_constant<int, 5>{}); break;
         }
     };
-    const __amdgpu_buffer_rsrc_t ars = rsrc_of(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ars = rsrc(p.a, p.a_bytes);
     for (int i = tid; i < 12 * S_CHUNKS * S_ZREC; i += 256) {
         const int arr = i / S_ZREC, r = i % S_ZREC;
         *reinterpret_cast<u32x4*>(patch + arr * S_ARR + S_ZBASE + r * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -1059,7 +1013,6 @@ __global__ __launch_bounds__(256, 1) void direct3s_kernel(Direct3sParams p) {
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     bf16x8 af[2][2][3];
     auto frags = [&](int g, auto SETc) {
@@ -1147,9 +1100,7 @@ __device__ void direct3s_prep_body_t(const float* w, unsigned char* img, int dgr
     const int nn = cb * 32 + (lane & 31), k0 = cc * 32 + ksx * 16 + 8 * (lane >> 5);
     float v[8];
     if (dgrad) {
-        const float* src = w + ((long)(NTAP - 1 - tap) * CT + nn) * CT + k0;
-        const float4 a = *reinterpret_cast<const float4*>(src), c = *reinterpret_cast<const float4*>(src + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+        ld8(w + ((long)(NTAP - 1 - tap) * CT + nn) * CT + k0, v);
     } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = w[((long)tap * CT + k0 + e) * CT + nn];
@@ -1157,8 +1108,7 @@ __device__ void direct3s_prep_body_t(const float* w, unsigned char* img, int dgr
     u32x4 o[3];
     cut8(v, o);
     unsigned char* dst = img + (long)(((cc * NTAP + tap) * 2 + ksx) * NCB + cb) * (3 * WBLK) + lane * 16;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * WBLK) = o[pl];
+    store_planes(dst, WBLK, o);
 }
 __device__ void direct3s_prep_body(const float* w, unsigned char* img, int dgrad, int idx) { direct3s_prep_body_t<CS>(w, img, dgrad, idx); }
 __device__ void direct3s256_prep_body(const float* w, unsigned char* img, int dgrad, int idx) { direct3s_prep_body_t<256>(w, img, dgrad, idx); }

@@ -1,6 +1,6 @@
 // 3-D convolution as implicit GEMM on the gfx950 matrix cores, f32 in / f32 accumulate, in two arithmetics:
 // BF3 = false: v_mfma_f32_32x32x2_f32 - bit-for-bit an fmaf chain; BF3 = true (the default, MI_CONV_ARITH): the same
-// products formed on the bf16 pipe from an exact three-way bf16 cut of both operands (see the kernel's header below).
+// products formed on the bf16 pipe from an exact three-way bf16 cut of both operands (bf16x3.h).
 // Either way parity with the fp32 reference holds.
 //
 // Replaces the nn.Conv3d / nn.Linear calls of the reference encoders
@@ -31,6 +31,7 @@
 // Small-M layers are split along the reduction (grid.z) into fp32 slabs, summed by a second
 // kernel that also applies the epilogue (deterministic, no atomics).
 #include "common.h"
+#include "bf16x3.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -102,10 +103,7 @@ int mi_small_gemm_launch(const float* a, long lda_m, long lda_k, long a_elems, c
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
 constexpr int NTHREADS = 256;
@@ -162,11 +160,6 @@ struct ConvParams {
 // behind the last slice need no select on loaded data and no branch: an invalid element just gets the
 // offset OOR (tensors are < 2 GiB, checked on the host, so OOR plus any in-tensor displacement stays outside).
 constexpr unsigned OOR = 0x80000000u;
-__device__ __forceinline__ float4 ld4(const float* ptr) { return *reinterpret_cast<const float4*>(ptr); }
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ float4 bld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
@@ -220,14 +213,8 @@ struct Cursor {
 // STEM: Cin == 1 (the 7x7x7 stride-2 stem, moco_encoder_3d.py:163-169): the reduction index is
 // the tap itself and each of a chunk's 4 taps is gathered separately through a tap LUT in LDS.
 //
-// BF3 = true: the same GEMM on the bf16 matrix pipe with f32-equivalent arithmetic.  Every f32 operand element is cut
-// (exactly: a = a0 + a1 + a2, three bf16 values of 8 significant bits each) while it is staged into LDS, and the six
-// products of weight <= 2 (a0 b0, a0 b1, a1 b0, a1 b1, a0 b2, a2 b0) are accumulated in f32 by
-// v_mfma_f32_32x32x16_bf16: each product is exact in f32, the dropped terms (a1 b2, a2 b1, a2 b2) are <= 2^-23 |a b|,
-// i.e. of the size of ONE f32 rounding - the result differs from the f32 fmaf chain by rounding-order noise only
-// (tests/test_train_gpu.py::test_conv_bf16x3_is_f32_equivalent measures both against float64; an Inf operand
-// becomes NaN - Inf - Inf in the cut - where an f32 multiply would keep Inf).  Six bf16 MFMAs of K = 16 take 192 cycles against 512 for
-// the eight f32 MFMAs they replace.  LDS holds three bf16 planes per operand:
+// BF3 = true: the same GEMM on the bf16 matrix pipe with f32-equivalent arithmetic (bf16x3.h): every f32 operand element is cut
+// into three bf16 planes while it is staged into LDS, six products per k-step.  LDS holds three bf16 planes per operand:
 //   "RowK" plane [row][BK] bf16, 16-byte chunks XOR-swizzled by row : fragments by ds_read_b128 (8 k's)
 //   "KRow" plane, one [BK][32 columns] sub-tile per 32 columns (64-byte rows) : fragments by ds_read_b64_tr_b16
 //          (the transposing LDS read of gfx950: 4 k's x 16 columns per 16-lane group, conflict-free on 64-byte rows)
@@ -379,8 +366,8 @@ __global__ __launch_bounds__(NTHREADS, BF3 ? ((BM == 128 && BN == 32) ? 2 : 3) :
                                               : make_dec(Dz, Dy, Dx);          // class grid
 
     // ---- per-thread staging state --------------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t a_rs = make_rsrc(p.nbatch ? p.a_tab[blockIdx.y] : p.a_src, p.a_bytes),
-                                 b_rs = make_rsrc(p.nbatch ? p.b_tab[blockIdx.y] : p.b_src, p.b_bytes);
+    const __amdgpu_buffer_rsrc_t a_rs = rsrc(p.nbatch ? p.a_tab[blockIdx.y] : p.a_src, p.a_bytes),
+                                 b_rs = rsrc(p.nbatch ? p.b_tab[blockIdx.y] : p.b_src, p.b_bytes);
     unsigned a_off[A_CH];            // byte offset of the row base (+ chunk) in a_src, mod 2^32 (padding rows
                                      // start "before" the tensor); WGRAD: tap + ci offset
     unsigned a_msk[A_CH];            // RowK: per-axis validity bits (z | y<<8 | x<<16), 0 = row off
@@ -617,29 +604,10 @@ __global__ __launch_bounds__(NTHREADS, BF3 ? ((BM == 128 && BN == 32) ? 2 : 3) :
 #pragma unroll
         for (int part = 0; part < NPARTS; ++part) load_part(kt, live, part, SETc);
     };
-    // bf16x3: exact three-way cut of 4 consecutive f32 (one 16-byte chunk) into 3 x 4 bf16, one 8-byte store per plane.
-    // Truncation keeps every step exact: a0 = top 16 bits of a, r1 = a - a0 (<= 16 significant bits), a1 = top 16 bits
-    // of r1, a2 = r1 - a1 (<= 8 significant bits: a bf16 value).
-    auto split_cut = [&](const float4 v, uint2 (&o)[3]) {
-        const float e[4] = {v.x, v.y, v.z, v.w};
-        unsigned u0[4], u1[4], u2[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            u0[t] = __float_as_uint(e[t]);
-            const float r1 = e[t] - __uint_as_float(u0[t] & 0xffff0000u);
-            u1[t] = __float_as_uint(r1);
-            const float r2 = r1 - __uint_as_float(u1[t] & 0xffff0000u);
-            u2[t] = __float_as_uint(r2);
-        }
-        // v_perm_b32: the high halves of two dwords -> one dword of two bf16 (element t in the low half)
-        constexpr unsigned HI2 = 0x07060302u;
-        o[0] = make_uint2(__builtin_amdgcn_perm(u0[1], u0[0], HI2), __builtin_amdgcn_perm(u0[3], u0[2], HI2));
-        o[1] = make_uint2(__builtin_amdgcn_perm(u1[1], u1[0], HI2), __builtin_amdgcn_perm(u1[3], u1[2], HI2));
-        o[2] = make_uint2(__builtin_amdgcn_perm(u2[1], u2[0], HI2), __builtin_amdgcn_perm(u2[3], u2[2], HI2));
-    };
+    // bf16x3: the cut of one 16-byte chunk, one 8-byte store per plane
     auto split_store = [&](unsigned char* dst, int plane_bytes, const float4 v) {
         uint2 o[3];
-        split_cut(v, o);
+        cut4(v, o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint2*>(dst + pl * plane_bytes) = o[pl];
     };
@@ -714,15 +682,14 @@ __global__ __launch_bounds__(NTHREADS, BF3 ? ((BM == 128 && BN == 32) ? 2 : 3) :
             constexpr int NCH = A_CH + B_CH;
             uint2 cv[NCH][3];
 #pragma unroll
-            for (int i = 0; i < A_CH; ++i) split_cut(a_reg[CUR ^ 1][i], cv[i]);
+            for (int i = 0; i < A_CH; ++i) cut4(a_reg[CUR ^ 1][i], cv[i]);
 #pragma unroll
-            for (int i = 0; i < B_CH; ++i) split_cut(b_reg[CUR ^ 1][i], cv[A_CH + i]);
+            for (int i = 0; i < B_CH; ++i) cut4(b_reg[CUR ^ 1][i], cv[A_CH + i]);
             unsigned char* const An = ldsb + (buf ^ 1) * STAGE_B;
             unsigned char* const Bn = An + 3 * A_PLANE;
             __builtin_amdgcn_sched_barrier(0);
             // Phase 2: six products per k-step, smallest first; the gather pieces of slice kt+2 and the LDS stores of
             // slice kt+1 (other buffer: nobody reads it before the barrier) ride behind the MFMAs
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
             constexpr int NMF3 = 6 * KS * MT * NT;
             static_assert(NPARTS <= NMF3, "more gather pieces than MFMAs");
 #pragma unroll
@@ -896,8 +863,8 @@ int env_int(const char* name) {
     return v ? atoi(v) : 0;
 }
 
-// Arithmetic of the generic kernel: "bf16x3" (default; f32-equivalent three-way bf16 cut on the bf16 matrix pipe, see
-// the kernel's header) or "f32" (v_mfma_f32_32x32x2_f32: bit-for-bit an fmaf chain) - MI_CONV_ARITH selects.
+// Arithmetic of the generic kernel: "bf16x3" (default; f32-equivalent three-way bf16 cut on the bf16 matrix pipe,
+// bf16x3.h) or "f32" (v_mfma_f32_32x32x2_f32: bit-for-bit an fmaf chain) - MI_CONV_ARITH selects.
 bool conv_arith_bf16x3() {
     const char* v = getenv("MI_CONV_ARITH");
     return !(v && v[0] == 'f');

@@ -17,13 +17,12 @@
 //   * epilogue: (+ residual) (ReLU) (x (mask > 0)), rows of the flat voxel order: out[o C + col].
 // f32-equivalent bf16x3 arithmetic (six products of the exact three-way cut, f32 accumulation), as every convolution here.
 #include "common.h"
+#include "bf16x3.h"
 #include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int PW_BLK = 1024;                // one B fragment plane: 64 lanes x 16 bytes
 constexpr int PW_STEP = 2 * 3 * PW_BLK;     // bytes per k-step: [column half][plane]
@@ -35,27 +34,6 @@ constexpr int PW_STEP = 2 * 3 * PW_BLK;     // bytes per k-step: [column half][p
 #endif
 constexpr int P_RB = P2D_RB;                // weight k-steps in flight (tuning builds: -DP2D_RB=3|6|9)
 constexpr int P_TM = 128;                   // output voxels per workgroup (wave tile: 64 voxels x 32 columns)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t p_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void p_cut8(const float (&v)[8], u32x4 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        o[0][d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        o[1][d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        o[2][d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-}
 
 struct P2DParams {
     const float* a;           // X (forward) or dY (data gradient): (N, H, W, CT) channels-last
@@ -112,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void p2d_kernel(P2DParams p) {
     const int n0 = (int)(o0 / HW), y0 = (int)(o0 - (long)n0 * HW) / Wd;
     const int pstart = n0 * (p.H + 1) + y0;              // = P(o0) - 1
 
-    const __amdgpu_buffer_rsrc_t wrs = p_rsrc(p.wimg, (unsigned)((CT / 64) * G::NSTEP * PW_STEP));
+    const __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg, (unsigned)((CT / 64) * G::NSTEP * PW_STEP));
     const int w_voff = cw * (3 * PW_BLK) + lane * 16;
     const int w_cb = cb * (G::NSTEP * PW_STEP);
     bf16x8 bfr[P_RB][3];
@@ -139,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void p2d_kernel(P2DParams p) {
 
     // ---- patch staging, one 16-channel chunk at a time: unit q = (patch voxel, k-half); separator rows, halo columns and rows
     //      outside the batch read zeros (offset out of range) ----
-    const __amdgpu_buffer_rsrc_t ars = p_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ars = rsrc(p.a, p.a_bytes);
     unsigned st_off[G::UNITS];
     int st_lds[G::UNITS];
 #pragma unroll
@@ -168,7 +146,7 @@ __global__ __launch_bounds__(256, 2) void p2d_kernel(P2DParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(ld[u][0][e]); v[4 + e] = __uint_as_float(ld[u][1][e]); }
             u32x4 o[3];
-            p_cut8(v, o);
+            cut8(v, o);
             unsigned char* dst = patch + slot * KSBd + st_lds[u];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * PLd) = o[pl];
@@ -190,7 +168,6 @@ __global__ __launch_bounds__(256, 2) void p2d_kernel(P2DParams p) {
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // smallest products first
 
     stage_store(0);
     stage_load(1);
@@ -252,8 +229,8 @@ __global__ __launch_bounds__(256, 2) void p2d_kernel(P2DParams p) {
     // ---- epilogue: C/D layout col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 h of row block i; a row IS a flat voxel ----
     const bool has_mask = p.mask != nullptr;
     const int col = cb * 64 + cw * 32 + l32;
-    const __amdgpu_buffer_rsrc_t rrs = p_rsrc(p.res, p.res ? p.a_bytes : 0u), mrs = p_rsrc(p.mask, p.mask ? p.a_bytes : 0u);
-    const __amdgpu_buffer_rsrc_t ors = p_rsrc(p.out, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rrs = rsrc(p.res, p.res ? p.a_bytes : 0u), mrs = rsrc(p.mask, p.mask ? p.a_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t ors = rsrc(p.out, p.a_bytes);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         float rr[16], mm[16];
@@ -293,18 +270,14 @@ __global__ __launch_bounds__(256) void p2d_prep_kernel(P2DPrepBatch b) {
     const int nn = cb * 64 + cw * 32 + (lane & 31), k0 = c * 16 + 8 * (lane >> 5);
     float v[8];
     if (b.dgrad[blockIdx.y]) {      // B'[tap][k = co][n = ci] = W[8 - tap][ci = n][co = k]
-        const float* src = w + ((long)(8 - tap) * ct + nn) * ct + k0;
-        const float4 a = *reinterpret_cast<const float4*>(src), d = *reinterpret_cast<const float4*>(src + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = d.x; v[5] = d.y; v[6] = d.z; v[7] = d.w;
+        ld8(w + ((long)(8 - tap) * ct + nn) * ct + k0, v);
     } else {                        // B[tap][k = ci][n = co] = W[tap][ci = k][co = n]
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = w[((long)tap * ct + k0 + e) * ct + nn];
     }
     u32x4 o[3];
-    p_cut8(v, o);
-    unsigned char* dst = b.img[blockIdx.y] + (size_t)(((cb * ks + c) * 9 + tap) * 2 + cw) * (3 * PW_BLK) + lane * 16;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * PW_BLK) = o[pl];
+    cut8(v, o);
+    store_planes(b.img[blockIdx.y] + (size_t)(((cb * ks + c) * 9 + tap) * 2 + cw) * (3 * PW_BLK) + lane * 16, PW_BLK, o);
 }
 
 // ---- the encoder's first layer: Conv2d(1, Co, 3, padding=1) (simsiam_model_2d.py:634) - nine taps of ONE input channel ----
@@ -398,8 +371,6 @@ __global__ __launch_bounds__(256) void stem3_wgrad_final_kernel(const float* par
 // [9][32][64] tile goes into its split-K slab; p2d_wgrad_reduce_kernel adds the slabs in slab order.
 constexpr int PW_KB = 64;                   // output voxels per K-block (4 k-steps)
 constexpr int PW_ROW = 64;                  // bytes of a (voxel, 32 channels) bf16 row
-typedef __bf16 bf16x4p __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4p lds_bf16x4p;
 
 // W_ = 0: the generic instance (any H, W whose window has <= 192 rows: run-time geometry, divisions through a float reciprocal)
 template <int W_>
@@ -466,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void p2d_wgrad_kernel(P2WParams p) {
     const int per = (p.nkb + p.splits - 1) / p.splits;
     const int kb0 = split * per, kb1 = kb0 + per < p.nkb ? kb0 + per : p.nkb;
 
-    const __amdgpu_buffer_rsrc_t xrs = p_rsrc(p.x, p.bytes), yrs = p_rsrc(p.dy, p.bytes);
+    const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x, p.bytes), yrs = rsrc(p.dy, p.bytes);
     // fragment addressing (transposing read): this lane names row q4 of its 16-lane group's 4-row block, columns 16 g16 + 4 (i16 & 3)
     const int q4 = i16 >> 2;
     const int coloff = (16 * g16 + 4 * (i16 & 3)) * 2;
@@ -476,7 +447,6 @@ __global__ __launch_bounds__(256, 2) void p2d_wgrad_kernel(P2WParams p) {
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     // staging registers: the NEXT K-block's operands are fetched while this one's products run
     u32x4 ldy[2][2], ldx[G::UX][2];
@@ -518,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void p2d_wgrad_kernel(P2WParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { vv[e] = __uint_as_float(ldy[u][0][e]); vv[4 + e] = __uint_as_float(ldy[u][1][e]); }
             u32x4 o3[3];
-            p_cut8(vv, o3);
+            cut8(vv, o3);
             unsigned char* dst = lds + YBd + (cg >> 2) * G::YH + v * PW_ROW + (cg & 3) * 16;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * G::YPL) = o3[pl];
@@ -531,7 +501,7 @@ __global__ __launch_bounds__(256, 2) void p2d_wgrad_kernel(P2WParams p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { vv[e] = __uint_as_float(ldx[u][0][e]); vv[4 + e] = __uint_as_float(ldx[u][1][e]); }
                 u32x4 o3[3];
-                p_cut8(vv, o3);
+                cut8(vv, o3);
                 unsigned char* dst = lds + r * PW_ROW + cg * 16;
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * XPLd) = o3[pl];
@@ -566,8 +536,8 @@ __global__ __launch_bounds__(256, 2) void p2d_wgrad_kernel(P2WParams p) {
             const unsigned char* yb = lds + YBd + wn * G::YH + (16 * (2 * kh + lk) + 8 * h + q4) * PW_ROW + coloff;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
-                const bf16x4p lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4p*)(yb + pl * G::YPL));
-                const bf16x4p hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4p*)(yb + pl * G::YPL + 4 * PW_ROW));
+                const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(yb + pl * G::YPL));
+                const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(yb + pl * G::YPL + 4 * PW_ROW));
                 bfg[pl] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
             }
             bf16x8 af[2][3];
@@ -575,8 +545,8 @@ __global__ __launch_bounds__(256, 2) void p2d_wgrad_kernel(P2WParams p) {
                 const int sh = ((t / 3) * PW + t % 3) * PW_ROW;
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
-                    const bf16x4p lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4p*)(lds + pl * XPLd + xrow[lk][0] + sh));
-                    const bf16x4p hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4p*)(lds + pl * XPLd + xrow[lk][1] + sh));
+                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds + pl * XPLd + xrow[lk][0] + sh));
+                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds + pl * XPLd + xrow[lk][1] + sh));
                     af[set][pl] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 }
             };

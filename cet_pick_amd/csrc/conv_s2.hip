@@ -21,38 +21,15 @@
 //     reduce launch.  Heaviest classes are launched first.
 // 60 - 72 KB of LDS: two workgroups (of eight waves) per CU.
 #include "common.h"
+#include "bf16x3.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int S2_WBLK = 1024;                // one B fragment: 64 lanes x 16 bytes
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_s2(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void cut8s(const float (&v)[8], u32x4 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        o[0][d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        o[1][d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        o[2][d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-}
 
 // class c = (pz << 2) | (py << 1) | px, parities of the input voxel; local tap j enumerates the odd axes (z, y, x order):
 // bit = 1 -> delta = 1 (tap 0), bit = 0 -> delta = 0 (tap 2); an even axis has delta = 0 (tap 1)
@@ -111,7 +88,7 @@ __global__ __launch_bounds__(512, OCC) void s2_dgrad_kernel(S2DgradParams p) {
     const int pz = (cls >> 2) & 1, py = (cls >> 1) & 1, px = cls & 1;
     const int ntaps = 1 << (pz + py + px);
 
-    const __amdgpu_buffer_rsrc_t wrs = rsrc_s2(p.wimg, p.wimg_bytes), drs = rsrc_s2(p.dsimg, p.dsimg ? p.dsimg_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg, p.wimg_bytes), drs = rsrc(p.dsimg, p.dsimg ? p.dsimg_bytes : 0u);
     const int w_voff = cbk * (3 * S2_WBLK) + lane * 16;
     bf16x8 bfr[RING][3];
 
@@ -119,7 +96,7 @@ __global__ __launch_bounds__(512, OCC) void s2_dgrad_kernel(S2DgradParams p) {
     constexpr int UPT = NV * CR / 8 / 512;
     static_assert(UPT * 512 * 8 == NV * CR, "staging divides");
     auto stage = [&](const float* src) {
-        const __amdgpu_buffer_rsrc_t ars = rsrc_s2(src, p.a_bytes);
+        const __amdgpu_buffer_rsrc_t ars = rsrc(src, p.a_bytes);
         u32x4 ld[UPT][2];
 #pragma unroll
         for (int u = 0; u < UPT; ++u) {
@@ -136,7 +113,7 @@ __global__ __launch_bounds__(512, OCC) void s2_dgrad_kernel(S2DgradParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(ld[u][0][e]); v[4 + e] = __uint_as_float(ld[u][1][e]); }
             u32x4 o[3];
-            cut8s(v, o);
+            cut8(v, o);
             unsigned char* dst = patch + ((cg >> 1) * 6 + (cg & 1)) * ARR + vox * 16;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * 2 * ARR) = o[pl];
@@ -154,7 +131,6 @@ __global__ __launch_bounds__(512, OCC) void s2_dgrad_kernel(S2DgradParams p) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     auto wload = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned so, auto SLOTc) {
         constexpr int SLOT = decltype(SLOTc)::value;
@@ -261,7 +237,6 @@ bool s2_shape(int Gi, int Ci, int Co, int* G) {
 size_t s2_img_bytes(int Ci, int Co) { return (size_t)27 * (Co / 16) * (Ci / 32) * 3 * S2_WBLK; }
 size_t s2_dsimg_bytes(int Ci, int Co) { return (size_t)(Co / 16) * (Ci / 32) * 3 * S2_WBLK; }
 
-
 // ===========================================================================================================================
 // FORWARD of a stride-2 block front: hmid = relu(conv3x3x3 stride 2 (x; W1)) and the 1x1 stride-2 shortcut r = x[2o] . Wds in ONE
 // launch (the implicit GEMM took a launch + a split-K reduce for the first and a launch for the second: 32 + 30 us per encoder).
@@ -313,7 +288,7 @@ __global__ __launch_bounds__(512, OCC) void s2_fwd_kernel(S2FwdParams p) {
     const int n0 = blockIdx.x * SPW;
 
     // ---- staging: unit q = (input voxel of the group, 8 of the k-step's 16 channels) ----
-    const __amdgpu_buffer_rsrc_t xrs = rsrc_s2(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x, p.x_bytes);
     u32x4 ld[UPT][2];
     auto gload = [&](int ks) {
 #pragma unroll
@@ -337,7 +312,7 @@ __global__ __launch_bounds__(512, OCC) void s2_fwd_kernel(S2FwdParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(ld[u][0][e]); v[4 + e] = __uint_as_float(ld[u][1][e]); }
             u32x4 o[3];
-            cut8s(v, o);
+            cut8(v, o);
             unsigned char* dst = patch + slot * SLOT + half * ARR + rec * 16;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * 2 * ARR) = o[pl];
@@ -362,7 +337,7 @@ __global__ __launch_bounds__(512, OCC) void s2_fwd_kernel(S2FwdParams p) {
         sel[j] = ok ? (sm * VI + cls * VO + (a * G + b) * G + c) * 16 + h * ARR : zaddr;
     }
 
-    const __amdgpu_buffer_rsrc_t wrs = rsrc_s2(p.wimg, p.wimg_bytes);
+    const __amdgpu_buffer_rsrc_t wrs = rsrc(p.wimg, p.wimg_bytes);
     const int w_voff = cbk * (3 * S2_WBLK) + lane * 16;
     bf16x8 bfr[RING][3];
     // flat step s = ks * NTW + j of this wave -> image offset of entry kw * NTW + j at k-step ks (out of range: zeros)
@@ -381,7 +356,6 @@ __global__ __launch_bounds__(512, OCC) void s2_fwd_kernel(S2FwdParams p) {
     f32x16 acc, acc2;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     // first RING - 1 fragments in flight, then the patch
     wload(woff(0), std::integral_constant<int, 0>{});
@@ -486,10 +460,9 @@ __global__ __launch_bounds__(256) void s2_prep_batch_kernel(S2PrepBatch b) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) v[t] = src[(long)t * jb.Co];
         u32x4 o[3];
-        cut8s(v, o);
+        cut8(v, o);
         unsigned char* dst = jb.img + (((long)e * KS + ks) * CB + cbk) * (3 * S2_WBLK) + lane * 16;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * S2_WBLK) = o[pl];
+        store_planes(dst, S2_WBLK, o);
         return;
     }
     // data-gradient image (s2_dgrad_prep_kernel): reduction = the convolution's output channels, columns = its input channels
@@ -506,10 +479,9 @@ __global__ __launch_bounds__(256) void s2_prep_batch_kernel(S2PrepBatch b) {
     const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 4);
     const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     u32x4 o[3];
-    cut8s(v, o);
+    cut8(v, o);
     unsigned char* dst = (ds ? jb.dsimg : jb.img) + (((long)(ds ? 0 : slot) * KS + ks) * CB + cbk) * (3 * S2_WBLK) + lane * 16;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * S2_WBLK) = o[pl];
+    store_planes(dst, S2_WBLK, o);
 }
 
 // class order of the data-gradient image (heaviest first) and the image slot -> convolution tap table

@@ -9,38 +9,12 @@
 // in fragment order (smallk_prep_kernel, built once per set of weights by the caller).  A workgroup = four waves = 128 rows x (32 NB)
 // columns; bias and ReLU in the epilogue.  (3, 1, 1): tap t reads the row one z-plane below / at / above - zeros outside the volume.
 #include "common.h"
+#include "bf16x3.h"
 #include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_sk(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-
-// exact three-way bf16 cut of 8 f32 (truncation, as conv_igemm.hip / conv_direct3.hip / conv_cube2.hip)
-__device__ __forceinline__ void cut8k(const float (&v)[8], bf16x8 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-    u32x4 p0, p1, p2;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        p0[d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        p1[d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        p2[d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-    o[0] = __builtin_bit_cast(bf16x8, p0); o[1] = __builtin_bit_cast(bf16x8, p1); o[2] = __builtin_bit_cast(bf16x8, p2);
-}
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 // weight image: [k-step][32-column block][plane 3][lane 64] x 16 bytes; lane (j = lane & 31, h = lane >> 5) holds W[16 ks + 8 h + e][32 cb + j]
 __global__ __launch_bounds__(256) void smallk_prep_kernel(const float* w, unsigned char* img, int K, int Co) {
@@ -54,11 +28,10 @@ __global__ __launch_bounds__(256) void smallk_prep_kernel(const float* w, unsign
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = w[(long)(16 * ks + 8 * h + e) * Co + 32 * cb + j];
-        bf16x8 o[3];
-        cut8k(v, o);
+        u32x4 o[3];
+        cut8(v, o);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            *reinterpret_cast<u32x4*>(img + ((q * 3 + pl) * 64 + lane) * 16) = __builtin_bit_cast(u32x4, o[pl]);
+        for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(img + ((q * 3 + pl) * 64 + lane) * 16) = o[pl];
     }
 }
 
@@ -80,7 +53,7 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(SmallKParams p) {
     const int h = lane >> 5, l32 = lane & 31;
     const long m0 = (long)blockIdx.x * 128 + wave * 32;
     const int cb0 = blockIdx.y * NB, ncb = p.Co >> 5;
-    const __amdgpu_buffer_rsrc_t xrs = rsrc_sk(p.x, p.x_bytes), irs = rsrc_sk(p.img, p.img_bytes);
+    const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x, p.x_bytes), irs = rsrc(p.img, p.img_bytes);
     const long m = m0 + l32;
     const bool row_ok = m < p.M;
     const int cpt = p.Ci >> 4, KS = p.ntaps * cpt;         // k-steps per tap, in all
@@ -99,7 +72,6 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(SmallKParams p) {
     for (int j = 0; j < NB; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     u32x4 araw[2][2], braw[2][NB][3];
     auto fetch = [&](int ks, auto SETc) {
         constexpr int SET = decltype(SETc)::value;
@@ -120,7 +92,7 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(SmallKParams p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(araw[SET][0][e]); v[4 + e] = __uint_as_float(araw[SET][1][e]); }
         bf16x8 af[3];
-        cut8k(v, af);
+        cut8(v, af);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             bf16x8 bf[3];
@@ -184,7 +156,7 @@ __global__ __launch_bounds__(256) void smallk_head_kernel(SmallKHeadParams hp) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, l32 = lane & 31;
     const long m0 = (long)blockIdx.x * 128 + wave * 32;
-    const __amdgpu_buffer_rsrc_t xrs = rsrc_sk(p.x, p.x_bytes), irs = rsrc_sk(p.img, p.img_bytes);
+    const __amdgpu_buffer_rsrc_t xrs = rsrc(p.x, p.x_bytes), irs = rsrc(p.img, p.img_bytes);
     const long m = m0 + l32;
     const bool row_ok = m < p.M;
     const int cpt = p.Ci >> 4, KS = 3 * cpt;
@@ -201,7 +173,6 @@ __global__ __launch_bounds__(256) void smallk_head_kernel(SmallKHeadParams hp) {
     float hm[KH];
 #pragma unroll
     for (int k = 0; k < KH; ++k) hm[k] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     u32x4 araw[2][2], braw[2][3];
     auto fetch = [&](int ks, auto SETc) {
         constexpr int SET = decltype(SETc)::value;
@@ -226,7 +197,7 @@ __global__ __launch_bounds__(256) void smallk_head_kernel(SmallKHeadParams hp) {
 #pragma unroll
             for (int k = 0; k < KH; ++k) hm[k] = fmaf(v[e], wr[e * KH + k], hm[k]);
         bf16x8 af[3], bf[3];
-        cut8k(v, af);
+        cut8(v, af);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) bf[pl] = __builtin_bit_cast(bf16x8, braw[SET][pl]);
 #pragma unroll

@@ -15,13 +15,13 @@
 // where a scalar v_sub_f32 is hidden, tools/probes/mfma_coissue.hip)
 // hipcc-flags: -fno-slp-vectorize
 #include "common.h"
+#include "bf16x3.h"
 #include <type_traits>
 #include "../../include/cetpick_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int K7 = 7, S2 = 2, P3 = 3;
 constexpr int TX = 8, TY = 4, TZ = 4;                    // output tile
@@ -46,10 +46,6 @@ struct StemParams {
     unsigned x_bytes;
     double* stats;       // bf16x3 kernel only, may be null: per-workgroup column sums of y and y^2, [2][64][gridDim.x]
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
 
 __global__ __launch_bounds__(256) void stem_fwd_kernel(StemParams p) {
     constexpr int NP = (PATCH + PW + 255) / 256;         // 16 patch elements per thread
@@ -162,7 +158,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(StemParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// FWD on the bf16 matrix pipe with f32-equivalent arithmetic (the "bf16x3" cut of conv_igemm.hip: a = a0 + a1 + a2
+// FWD on the bf16 matrix pipe with f32-equivalent arithmetic (bf16x3.h: a = a0 + a1 + a2
 // exactly, six products of weight <= 2 per f32 product, f32 accumulate).  The patch is cut ONCE while it is staged
 // (three bf16 planes of 48-byte rows); the weights are cut once per call by stem_wprep_kernel into the LDS image
 // [slab][plane][row 0..7][co][kx 0..7] (rows r = 7 kz + ky, eight to a slab; rows 49..55 and kx = 7 are zero padding), streamed one
@@ -170,21 +166,11 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(StemParams p) {
 // kx taps are eight CONSECUTIVE patch elements (stride-2 convolution: x = 2 ox + kx) - four ds_read_b32 per plane,
 // conflict-free on 48-byte rows.  25 k-steps (round 4; 28 with the rows padded per kz) x 6 products x 2 column tiles = 300 MFMAs
 // of 32 cycles per wave and z-plane against 350 of 64 cycles in the f32 kernel.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int PYP = PY + 1;                              // + one zero row: the padded tap ky = 7 of the last output row
 constexpr int PROW = 2 * PW;                             // bytes per bf16 patch row
 constexpr int WPL = 8 * CO * 16;                         // bytes per plane of a kz slab: [ky8][co][kx8] bf16
 constexpr int WSLAB = 3 * WPL;                           // 24576 bytes
 constexpr size_t WPREP_BYTES = (size_t)K7 * WSLAB;       // 172032 bytes
-
-// exact three-way bf16 cut of one f32 (truncation; see conv_igemm.hip): the three bf16 bit patterns
-__device__ __forceinline__ void cut3(float a, unsigned& h0, unsigned& h1, unsigned& h2) {
-    const unsigned u0 = __float_as_uint(a);
-    const float r1 = a - __uint_as_float(u0 & 0xffff0000u);
-    const unsigned u1 = __float_as_uint(r1);
-    const float r2 = r1 - __uint_as_float(u1 & 0xffff0000u);
-    h0 = u0 >> 16; h1 = u1 >> 16; h2 = __float_as_uint(r2) >> 16;
-}
 
 __global__ __launch_bounds__(256) void stem_wprep_kernel(const float* w, unsigned short* out) {
     const int i = blockIdx.x * 256 + threadIdx.x;        // (slab, row j of the slab, co, kx8)
@@ -284,7 +270,6 @@ __global__ __launch_bounds__(256, ZPW == 2 ? 2 : (NBUF == 1 ? 3 : 2)) void stem_
     for (int zi = 0; zi < ZPW; ++zi)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc0[zi][r] = 0.f; acc1[zi][r] = 0.f; }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // smallest products first
 
     // fragments of k-step (kz, u) -> register set u & 1; the reads of step g+1 are issued before the MFMAs of step g
     bf16x8 af[2][ZPW][3], bf0[2][3], bf1[2][3];
@@ -570,7 +555,6 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(StemWgradParams p) {
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------
 // WGRAD on the bf16 matrix pipe (round 3), f32-equivalent arithmetic as everywhere (three-way exact bf16 cut of both
 // operands, six products, f32 accumulate).  Same decomposition as stem_wgrad_kernel - rows = taps, columns = channels,
@@ -591,8 +575,6 @@ constexpr int WG_NQT = (WG_NQ + 255) / 256;              // 4 per thread
 constexpr int WG_DROW = 64;                              // bytes of a (voxel, 32 channels) bf16 row
 constexpr int WG_DHALF = VOX * WG_DROW;                  // 8192
 constexpr int WG_DPLANE = 2 * WG_DHALF;                  // 16384
-typedef __bf16 bf16x4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4s lds_bf16x4s;
 
 template <int OCC>
 __global__ __launch_bounds__(256, OCC) void stem_wgrad_bf3_kernel(StemWgradParams p) {
@@ -717,7 +699,6 @@ __global__ __launch_bounds__(256, OCC) void stem_wgrad_bf3_kernel(StemWgradParam
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 
     const int tile0 = blockIdx.x * p.tiles_per_block;
     gload_patch(tile0);
@@ -737,8 +718,8 @@ __global__ __launch_bounds__(256, OCC) void stem_wgrad_bf3_kernel(StemWgradParam
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
                     const unsigned char* bp = dyb + pl * WG_DPLANE + j * WG_DHALF + b_base + ks * 16 * WG_DROW;
-                    const bf16x4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4s*)(bp));
-                    const bf16x4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4s*)(bp + 4 * WG_DROW));
+                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(bp));
+                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(bp + 4 * WG_DROW));
                     bf[SET][j][pl] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 }
 #pragma unroll

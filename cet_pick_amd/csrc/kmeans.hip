@@ -3,7 +3,7 @@
 //   xnorm   |x_i|^2                                                                                      (once per fit)
 //   assign  labels[i] = argmin_j |x_i|^2 + (|c_j|^2 - 2 x_i . c_j), lowest index on ties; dist[i]; per-workgroup objective
 //           partials.  The N x k x d product runs on v_mfma_f32_32x32x16_bf16 in the library's bf16x3 arithmetic (six
-//           products of an exact 3-way cut, smallest terms first: loss_ops.hip UclS).
+//           products of an exact 3-way cut, smallest terms first: bf16x3.h).
 //   update  a stable counting sort of the point indices by label (integers only), sums over fixed 64-position segments
 //           of the sorted order in position order, per-cluster reduction of the segment partials in segment order (f64),
 //           then the empty-cluster rule and the objective on one workgroup.  No floating-point atomics: same inputs,
@@ -11,43 +11,22 @@
 // Rows are addressed with 64-bit offsets throughout (N x d may exceed 2 GiB); N < 2^31.
 // hipcc-flags: -fno-slp-vectorize
 #include "common.h"
+#include "bf16x3.h"
 #include "../../include/cetpick_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 constexpr int KM_DMAX = 512, KM_KMAX = 1024;
 constexpr int KM_CHUNK = 1024;            // points per workgroup of the counting sort
 constexpr int KM_SEG = 64;                // sorted positions per first-level partial sum (one wave)
 constexpr float KM_EPS = 1.f / 1024.f;
 
-// exact 3-way bf16 cut of eight f32 values, as loss_ops.hip ucl_cut8
-__device__ __forceinline__ void km_cut8(const float (&v)[8], u32x4 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        o[0][q] = __builtin_amdgcn_perm(u0[2 * q + 1], u0[2 * q], HI2);
-        o[1][q] = __builtin_amdgcn_perm(u1[2 * q + 1], u1[2 * q], HI2);
-        o[2][q] = __builtin_amdgcn_perm(u2[2 * q + 1], u2[2 * q], HI2);
-    }
-}
-
 // eight consecutive features k8 .. k8 + 7 of one row (zero past d or when the row does not exist)
 __device__ __forceinline__ void km_load8(const float* row, bool ok, int k8, int d, bool vec, float (&v)[8]) {
     if (ok && vec && k8 + 8 <= d) {
-        const float4 a = *reinterpret_cast<const float4*>(row + k8), b = *reinterpret_cast<const float4*>(row + k8 + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        ld8(row + k8, v);
     } else {
 #pragma unroll
         for (int t = 0; t < 8; ++t) v[t] = (ok && k8 + t < d) ? row[k8 + t] : 0.f;
@@ -73,7 +52,7 @@ __global__ __launch_bounds__(64) void km_prep_kernel(const float* cent, int d, i
 #pragma unroll
         for (int t = 0; t < 8; ++t) s = fmaf(v[t], v[t], s);
         u32x4 o[3];
-        km_cut8(v, o);
+        cut8(v, o);
         const int ks = g >> 1, h = g & 1, ct = j >> 5, l32 = j & 31;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
@@ -121,7 +100,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* x, const fl
         float v[8];
         km_load8(x + (size_t)(row0 + r) * d, row0 + r < n, g * 8, d, vec, v);
         u32x4 o[3];
-        km_cut8(v, o);
+        cut8(v, o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(km_lds + pl * PLANE + r * PITCH + g * 16) = o[pl];
     }
@@ -134,7 +113,6 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* x, const fl
 #pragma unroll
         for (int r = 0; r < 16; ++r) { best[m][r] = INFINITY; bidx[m][r] = 0; }
 
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // smallest terms first
     for (int ct = wave; ct < KT; ct += 4) {
         f32x16 acc[RM];
 #pragma unroll

@@ -14,39 +14,12 @@
 // throughput each next to the MFMAs where the scalar FP32 operations they replace are hidden - tools/probes/mfma_coissue.hip)
 // hipcc-flags: -fno-slp-vectorize
 #include "common.h"
+#include "bf16x3.h"
 #include "../../include/cetpick_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4w __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4w lds_bf16x4w;
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-// Exact 3-way bf16 cut of eight f32 values (a = a0 + a1 + a2, truncation: every subtraction is exact), packed as the three
-// MFMA operand planes - the arithmetic of the convolution kernels (conv_cube2.hip cut8r): six bf16 products of
-// weight <= 2 accumulated in f32 are an f32-equivalent product on the bf16 matrix pipe (16x the f32 MFMA rate).
-__device__ __forceinline__ void ucl_cut8(const float (&v)[8], bf16x8 (&o)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        u0[t] = __float_as_uint(v[t]);
-        const float r1 = v[t] - __uint_as_float(u0[t] & 0xffff0000u);
-        u1[t] = __float_as_uint(r1);
-        u2[t] = __float_as_uint(r1 - __uint_as_float(u1[t] & 0xffff0000u));
-    }
-    constexpr unsigned HI2 = 0x07060302u;
-    u32x4 p0, p1, p2;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        p0[d] = __builtin_amdgcn_perm(u0[2 * d + 1], u0[2 * d], HI2);
-        p1[d] = __builtin_amdgcn_perm(u1[2 * d + 1], u1[2 * d], HI2);
-        p2[d] = __builtin_amdgcn_perm(u2[2 * d + 1], u2[2 * d], HI2);
-    }
-    o[0] = __builtin_bit_cast(bf16x8, p0); o[1] = __builtin_bit_cast(bf16x8, p1); o[2] = __builtin_bit_cast(bf16x8, p2);
-}
+using namespace bf3;        // the bf16x3 arithmetic, its types and helpers: bf16x3.h
 
 // The similarity tile S = F_rows . F_cols^T of the contrastive loss on the bf16 pipe.  A (this wave's 32 rows, constant over
 // the column walk): lane = (row l32, features 16 ks + 8 h .. + 7), cut once into registers.  B (the 64 columns of a tile):
@@ -66,13 +39,13 @@ template <int DIM> struct UclS {
             const float4 a = ok ? ld4(feat + (long)row * DIM + 16 * ks + 8 * h) : make_float4(0, 0, 0, 0);
             const float4 b = ok ? ld4(feat + (long)row * DIM + 16 * ks + 8 * h + 4) : make_float4(0, 0, 0, 0);
             v[0] = a.x * fs; v[1] = a.y * fs; v[2] = a.z * fs; v[3] = a.w * fs; v[4] = b.x * fs; v[5] = b.y * fs; v[6] = b.z * fs; v[7] = b.w * fs;
-            ucl_cut8(v, af[ks]);
+            cut8(v, af[ks]);
         }
     }
     // one unit of the tile (column c, features k8 .. k8 + 7) -> the three planes
     static __device__ __forceinline__ void stage(unsigned char* planes, int c, int k8, const float (&v)[8]) {
         bf16x8 o[3];
-        ucl_cut8(v, o);
+        cut8(v, o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
             *reinterpret_cast<u32x4*>(planes + pl * PLANE + c * PITCH + k8 * 2) = __builtin_bit_cast(u32x4, o[pl]);
@@ -83,7 +56,6 @@ template <int DIM> struct UclS {
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // smallest terms first
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 bf[3];
@@ -629,7 +601,6 @@ __global__ __launch_bounds__(256, (DIM == 64 || TRANS == 2) ? 2 : 3) void ucl_bw
         // [column = k][feature = n] rows, the fragment wants n per lane and k along its registers; a lane names row q4 of its
         // 16-lane group's 4 x 16 block and gets the block's column i16 - conv_cube2.hip pair_wgrad_kernel has the same read)
         {
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
             const int i16 = lane & 15, g16 = (lane >> 4) & 1, q4 = i16 >> 2;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -638,7 +609,7 @@ __global__ __launch_bounds__(256, (DIM == 64 || TRANS == 2) ? 2 : 3) void ucl_bw
                 const float4 a1 = *reinterpret_cast<const float4*>(wrow + l32 * WP + 16 * ks + 8 * h + 4);
                 v[0] = a0.x; v[1] = a0.y; v[2] = a0.z; v[3] = a0.w; v[4] = a1.x; v[5] = a1.y; v[6] = a1.z; v[7] = a1.w;
                 bf16x8 aw[3];
-                ucl_cut8(v, aw);
+                cut8(v, aw);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     bf16x8 bf[3];
@@ -646,8 +617,8 @@ __global__ __launch_bounds__(256, (DIM == 64 || TRANS == 2) ? 2 : 3) void ucl_bw
                     for (int pl = 0; pl < 3; ++pl) {
                         const unsigned char* bp = colb + pl * SP::PLANE + (wn * 32 + 16 * ks + 8 * h + q4) * SP::PITCH +
                                                   (32 * j + 16 * g16 + 4 * (i16 & 3)) * 2;
-                        const bf16x4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4w*)(bp));
-                        const bf16x4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4w*)(bp + 4 * SP::PITCH));
+                        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(bp));
+                        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(bp + 4 * SP::PITCH));
                         bf[pl] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                     }
 #pragma unroll

@@ -8,12 +8,13 @@
 // trains/tomo_moco_trainer.py:52,73 (CrossEntropyLoss); torch.optim.SGD at moco_main.py:79.
 // All are HBM-bound elementwise / column-reduction passes.
 #include "common.h"
+#include "bf16x3.h"     // ld4 / st4
 #include <algorithm>
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+using bf3::ld4;
+using bf3::st4;
 
 // ---------------------------------------------------------------------------------------------
 // column reductions over [M][C] (C % 4 == 0, 256 % (C/4) == 0)

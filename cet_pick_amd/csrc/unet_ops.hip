@@ -3,12 +3,13 @@
 // convolution's pixel shuffle, the skip concatenation and the (3,1,1) heads with a handful of outputs.
 // Channels-last fp32 everywhere; every kernel moves float4s and is bound by HBM bandwidth.
 #include "common.h"
+#include "bf16x3.h"     // ld4 / st4
 #include "../../include/cetpick_hip.h"
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+using bf3::ld4;
+using bf3::st4;
 int ew_blocks(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
 
 // nn.MaxPool2d(k, stride=k, ceil_mode=True) per image (unet.py:231-233): windows may hang over the far edge
