@@ -182,6 +182,10 @@ SIGNATURES = {
     "mi_kmeans_xnorm": (_I, [_P, _L, _I, _P, _P]),
     "mi_kmeans_assign": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _Z, _P]),
     "mi_kmeans_update": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    # k-nearest-neighbour search over embeddings (csrc/knn.hip)
+    "mi_knn_image_bytes": (_Z, [_L, _I]),
+    "mi_knn_workspace_bytes": (_Z, [_L, _L, _I, _I, _I, _I]),
+    "mi_knn_search": (_I, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

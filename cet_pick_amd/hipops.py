@@ -2545,3 +2545,35 @@ def kmeans_update(x, labels, centroids, counts=None, obj=None, nsplit=None, ws=N
     L.check(L.lib().mi_kmeans_update(L.ptr(x), L.ptr(labels), n, d, k, L.ptr(c), L.ptr(counts), L.ptr(obj), L.ptr(nsplit),
                                      L.ptr(ws), ws.numel(), L.stream()), "mi_kmeans_update")
     return counts
+
+
+# ---- k-nearest-neighbour search over embeddings (csrc/knn.hip) -----------------------------------------------------------
+
+KNN_METRICS = {"ip": 0, "l2": 1}          # MI_KNN_IP, MI_KNN_L2
+
+
+def knn_search(q, x, k, metric="ip", exclude_self=False, n_split=0, out=None):
+    """(index (M, k) int32, value (M, k) fp32): the k best rows of x (N, d) for every row of q (M, d), best first, the lowest
+    index first among equal values.  metric "ip": value q.x, larger is better; "l2": value |q|^2 + (|x|^2 - 2 q.x) clamped
+    at 0, smaller is better.  exclude_self leaves column j out for query row j.  n_split: parts the database is divided
+    into (0: chosen by the library); the result does not depend on it."""
+    q, x = _km_x(q, "q"), _km_x(x)
+    if metric not in KNN_METRICS:
+        raise L.HipExtensionError("metric must be 'ip' or 'l2', got %r" % (metric,))
+    (m, d), n = q.shape, x.shape[0]
+    k, n_split, excl = int(k), int(n_split), int(bool(exclude_self))
+    if x.shape[1] != d or x.device != q.device:
+        raise L.HipExtensionError("q is %s on %s, x is %s on %s" % (tuple(q.shape), q.device, tuple(x.shape), x.device))
+    what = "(M=%d, N=%d, d=%d, k=%d, exclude_self=%d, n_split=%d)" % (m, n, d, k, excl, n_split)
+    nbytes = L.lib().mi_knn_workspace_bytes(m, n, d, k, excl, n_split)
+    if nbytes == 0:
+        L.check(-3, "mi_knn_workspace_bytes" + what)
+    if out is None:
+        out = (torch.empty(m, k, dtype=torch.int32, device=q.device), torch.empty(m, k, dtype=torch.float32, device=q.device))
+    index, value = L.require_cuda(out[0], "out[0]", torch.int32), L.require_cuda(out[1], "out[1]")
+    if tuple(index.shape) != (m, k) or tuple(value.shape) != (m, k) or not index.is_contiguous() or not value.is_contiguous():
+        raise L.HipExtensionError("out must be contiguous (%d, %d) tensors" % (m, k))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    L.check(L.lib().mi_knn_search(L.ptr(q), L.ptr(x), m, n, d, k, KNN_METRICS[metric], excl, n_split, L.ptr(index), L.ptr(value),
+                                  L.ptr(ws), ws.numel(), L.stream()), "mi_knn_search" + what)
+    return index, value

@@ -1,7 +1,7 @@
 """Cluster the exploration embeddings and write the per-pick class table (the reference's plot_2d.py without its plots):
 
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
-                                   [--seed 1234] [--gpus 0] [--host 7000]
+                                   [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -11,6 +11,9 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
                                           name, coords: numpy only, always written
     OUT/interactive_info_parquet.gzip     the reference's table (name, coord, embeddings, label, image) where pandas with a
                                           parquet engine imports
+    OUT/knn_graph.npz                     with --num_neighbor K only: index (N, K) i32 and dist (N, K) f32, the K nearest other
+                                          picks of every pick by squared L2 distance over `pred`, ascending (utils: csrc/knn.hip,
+                                          lowest index on ties), and k - the graph a UMAP / t-SNE map starts from
 
 The UMAP / t-SNE plots, the PNG thumbnails and all_colors.npy are not made here.
 """
@@ -29,8 +32,9 @@ def add_arguments(parser):
     parser.add_argument("--seed", type=int, default=1234, help="seed of the initial centroids (the reference passes 1234 to faiss)")
     parser.add_argument("--host", type=int, default=7000, help="port in the image URLs of the parquet table")
     parser.add_argument("--gpus", default="0", help="GPU index; -1 (CPU) is refused")
+    parser.add_argument("--num_neighbor", type=int, default=None,
+                        help="also write knn_graph.npz: the K nearest other picks of every pick (squared L2 over pred)")
     # accepted for the reference's command lines; they only steer its plots
-    parser.add_argument("--num_neighbor", type=int, default=None)
     parser.add_argument("--mode", default="umap")
     parser.add_argument("--min_dist_umap", type=float, default=0.5)
     parser.add_argument("--min_dist_vis", type=float, default=None)
@@ -68,6 +72,16 @@ def write_parquet(path, names, coords, projs, labels, host):
     return True
 
 
+def knn_graph(projs, k, device):
+    """index (N, k) int32, dist (N, k) fp32: the k nearest other rows of every row of projs, squared L2, ascending."""
+    import torch
+    from . import hipops as H
+    with torch.cuda.device(device):
+        x = torch.from_numpy(projs).to(device)
+        index, dist = H.knn_search(x, x, k, metric="l2", exclude_self=True)
+        return index.cpu().numpy(), dist.cpu().numpy()
+
+
 def main(args):
     gpu = int(str(args.gpus).split(",")[0])
     if gpu < 0:
@@ -78,8 +92,13 @@ def main(args):
     projs = np.ascontiguousarray(data["pred"], dtype=np.float32)
     projs = projs.reshape(projs.shape[0], -1)
     names, coords = data["name"], data["coords"]
-    print("[cet_pick_amd] plot_2d: the 2-D plots, thumbnails and colour map are not made here (--num_neighbor, --mode, "
-          "--min_dist_umap, --min_dist_vis, --save_out_img are ignored)")
+    if args.num_neighbor is None:
+        print("[cet_pick_amd] plot_2d: the 2-D plots, thumbnails and colour map are not made here (--num_neighbor, --mode, "
+              "--min_dist_umap, --min_dist_vis, --save_out_img are ignored)")
+    else:
+        print("[cet_pick_amd] plot_2d: the 2-D plots, thumbnails and colour map are not made here (--mode, --min_dist_umap, "
+              "--min_dist_vis, --save_out_img are ignored); --num_neighbor %d writes the neighbour graph knn_graph.npz"
+              % args.num_neighbor)
     os.makedirs(args.path, exist_ok=True)
     km = Kmeans(projs.shape[1], args.k, niter=args.niter, seed=args.seed, device=torch.device("cuda", gpu))
     with torch.cuda.device(gpu):
@@ -98,6 +117,11 @@ def main(args):
     write_parquet(os.path.join(args.path, "interactive_info_parquet.gzip"), names, coords, projs, label, args.host)
     print("[cet_pick_amd] plot_2d: %d picks, %d centroids, %d classes, objective %.6g -> %s"
           % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
+    if args.num_neighbor is not None:
+        index, dist = knn_graph(projs, args.num_neighbor, torch.device("cuda", gpu))
+        np.savez(os.path.join(args.path, "knn_graph.npz"), index=index, dist=dist, k=np.int32(args.num_neighbor))
+        print("[cet_pick_amd] plot_2d: %d nearest neighbours of %d picks (squared L2, self excluded) -> %s"
+              % (args.num_neighbor, len(index), os.path.join(args.path, "knn_graph.npz")))
 
 
 if __name__ == "__main__":

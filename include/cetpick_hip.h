@@ -771,6 +771,28 @@ int mi_kmeans_assign(const float* x, const float* xnorm, const void* image, long
 int mi_kmeans_update(const float* x, const int32_t* labels, long n, int d, int k, float* centroids, int32_t* counts,
                      float* obj, int32_t* nsplit, void* ws, size_t ws_bytes, mi_stream_t stream);
 
+/* Exact k-nearest-neighbour search (reference utils/memory_bank.py: faiss.IndexFlatIP, matmul + topk), DESIGN.md 4.11.
+ * q (m, d) and x (n, d) fp32 rows, 1 <= d <= 512, 1 <= k <= 128, 1 <= m < 2^31, k <= n < 2^31 (k + 1 <= n with exclude_self),
+ * 0 <= n_split <= 32 (MI_E_UNSUPPORTED outside; the size entries return 0).  Rows are addressed with 64-bit offsets: n x d may
+ * exceed 2 GiB.  One arithmetic: bf16x3 on the matrix cores (MI_CONV_ARITH is not consulted).
+ *   mi_knn_search  out_index (m, k) int32 = the k best rows of x for every row of q, best first, out_value (m, k) fp32 their
+ *                  values.  MI_KNN_IP: the value is q.x, larger is better.  MI_KNN_L2: the value is |q|^2 + (|x|^2 - 2 q.x)
+ *                  evaluated in that order and clamped at 0, smaller is better.  Equal values: the LOWEST index first.
+ *                  exclude_self: column j is left out for query row j (a set searched against itself).  The database is cut
+ *                  once per call into its MFMA operand image (mi_knn_image_bytes(n, d) of ws); the m x n values are never
+ *                  stored: a workgroup keeps the running top k of its query rows and takes only the values that beat a row's
+ *                  k-th.  The columns are divided into n_split parts (0: the library chooses) whose partial results a second
+ *                  launch merges; the result does not depend on n_split, and the same inputs give the same bytes.  A NaN value
+ *                  counts as the worst.
+ * ws: mi_knn_workspace_bytes(m, n, d, k, exclude_self, n_split) (the image included), 16-byte aligned; q and x 16-byte aligned
+ * when d is a multiple of 4. */
+#define MI_KNN_IP 0
+#define MI_KNN_L2 1
+size_t mi_knn_image_bytes(long n, int d);
+size_t mi_knn_workspace_bytes(long m, long n, int d, int k, int exclude_self, int n_split);
+int mi_knn_search(const float* q, const float* x, long m, long n, int d, int k, int metric, int exclude_self, int n_split,
+                  int32_t* out_index, float* out_value, void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
