@@ -186,6 +186,11 @@ SIGNATURES = {
     "mi_knn_image_bytes": (_Z, [_L, _I]),
     "mi_knn_workspace_bytes": (_Z, [_L, _L, _I, _I, _I, _I]),
     "mi_knn_search": (_I, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    # t-SNE over the neighbour graph (csrc/tsne.hip)
+    "mi_tsne_affinities": (_I, [_P, _L, _I, _F, _P, _P, _P]),
+    "mi_tsne_workspace_bytes": (_Z, [_L, _I, _I]),
+    "mi_tsne_gradient": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
+    "mi_tsne_update": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _P]),
 }
 
 _lib = None

@@ -2577,3 +2577,73 @@ def knn_search(q, x, k, metric="ip", exclude_self=False, n_split=0, out=None):
     L.check(L.lib().mi_knn_search(L.ptr(q), L.ptr(x), m, n, d, k, KNN_METRICS[metric], excl, n_split, L.ptr(index), L.ptr(value),
                                   L.ptr(ws), ws.numel(), L.stream()), "mi_knn_search" + what)
     return index, value
+
+
+# ---- t-SNE over the neighbour graph (csrc/tsne.hip) ------------------------------------------------------------------------
+
+def _ts_table(t, name, shape, dtype=torch.float32):
+    L.require_cuda(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.HipExtensionError("%s must be a contiguous %s tensor, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def tsne_affinities(dist, perplexity):
+    """(p (N, K) fp32, beta (N,) fp32): the conditional affinities exp(-beta d) / sum of every row of dist (N, K), the row's
+    beta found by sklearn's binary search for the entropy ln(perplexity); p is evaluated at the fp32 beta returned."""
+    dist = _km_x(dist, "dist")
+    n, k = dist.shape
+    p = torch.empty(n, k, dtype=torch.float32, device=dist.device)
+    beta = torch.empty(n, dtype=torch.float32, device=dist.device)
+    L.check(L.lib().mi_tsne_affinities(L.ptr(dist), n, k, float(perplexity), L.ptr(p), L.ptr(beta), L.stream()),
+            "mi_tsne_affinities(N=%d, K=%d, perplexity=%g)" % (n, k, perplexity))
+    return p, beta
+
+
+def tsne_workspace(n, k, n_split, device):
+    nbytes = L.lib().mi_tsne_workspace_bytes(n, k, n_split)
+    if nbytes == 0:
+        L.check(-3, "mi_tsne_workspace_bytes(N=%d, K=%d, n_split=%d)" % (n, k, n_split))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def tsne_gradient(y, index, p, rev_ptr, rev_edge, exaggeration=1.0, n_split=0, kl=True, out=None, ws=None):
+    """(grad (N, 2) fp32, z (1,) fp32, kl (1,) fp32 or None): the exact t-SNE gradient of y (N, 2) for the graph index (N, K)
+    int32 with conditional affinities p (N, K) and its transpose (rev_ptr, rev_edge: utils/tsne.reverse_graph); z = the sum
+    of q over i != j; kl (kl=True) the divergence without the exaggeration.  n_split: parts of the all-pairs sum (0: from N)."""
+    y = _km_x(y, "y")
+    n = y.shape[0]
+    if y.shape[1] != 2:
+        raise L.HipExtensionError("y must be (N, 2), got %s" % (tuple(y.shape),))
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2 or index.shape[0] != n:
+        raise L.HipExtensionError("index must be (N, K) with N = %d, got %s" % (n, tuple(index.shape)))
+    k, n_split = index.shape[1], int(n_split)
+    _ts_table(index, "index", (n, k), torch.int32)
+    _ts_table(p, "p", (n, k))
+    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
+    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    if ws is None:
+        ws = tsne_workspace(n, k, n_split, y.device)
+    if out is None:
+        out = (torch.empty(n, 2, dtype=torch.float32, device=y.device), torch.empty(1, dtype=torch.float32, device=y.device),
+               torch.empty(1, dtype=torch.float32, device=y.device) if kl else None)
+    grad, z, klt = _ts_table(out[0], "out[0]", (n, 2)), _ts_table(out[1], "out[1]", (1,)), out[2] if kl else None
+    if klt is not None:
+        _ts_table(klt, "out[2]", (1,))
+    L.check(L.lib().mi_tsne_gradient(L.ptr(y), L.ptr(index), L.ptr(p), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, float(exaggeration),
+                                     n_split, L.ptr(grad), L.ptr(z), L.ptr(klt), L.ptr(ws), ws.numel(), L.stream()),
+            "mi_tsne_gradient(N=%d, K=%d, n_split=%d)" % (n, k, n_split))
+    return grad, z, klt
+
+
+def tsne_update(y, grad, velocity, gains, momentum, lr, min_gain=0.01):
+    """sklearn's gradient-descent step with gains, in place on y, velocity and gains (all (N, 2) fp32)."""
+    y = _km_x(y, "y")
+    for t, name in ((grad, "grad"), (velocity, "velocity"), (gains, "gains")):
+        _ts_table(t, name, tuple(y.shape))
+    if y.shape[1] != 2:
+        raise L.HipExtensionError("y must be (N, 2), got %s" % (tuple(y.shape),))
+    L.check(L.lib().mi_tsne_update(L.ptr(y), L.ptr(grad), L.ptr(velocity), L.ptr(gains), y.shape[0], float(momentum), float(lr),
+                                   float(min_gain), L.stream()), "mi_tsne_update(N=%d)" % y.shape[0])
+    return y

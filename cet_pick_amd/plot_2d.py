@@ -1,7 +1,8 @@
-"""Cluster the exploration embeddings and write the per-pick class table (the reference's plot_2d.py without its plots):
+"""Cluster the exploration embeddings, write the per-pick class table and the 2-D t-SNE map (the reference's plot_2d.py
+without its plots):
 
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
-                                   [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K]
+                                   [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode tsne] [--map_seed 42]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -14,8 +15,14 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
     OUT/knn_graph.npz                     with --num_neighbor K only: index (N, K) i32 and dist (N, K) f32, the K nearest other
                                           picks of every pick by squared L2 distance over `pred`, ascending (utils: csrc/knn.hip,
                                           lowest index on ties), and k - the graph a UMAP / t-SNE map starts from
+    OUT/embeddings_2d.npz                 with --mode tsne --num_neighbor P only: the exact t-SNE map of `pred` at perplexity P
+                                          (utils/tsne.py, csrc/tsne.hip: sklearn's schedule, 1000 iterations, its init="random"
+                                          from --map_seed, the reference's --seed): y (N, 2) f32, y01 = (y - min) / (max - min)
+                                          per axis as the reference normalises, kl, n_iter, perplexity, seed.  One search with
+                                          min(N - 1, 3 P + 1) neighbours serves the map and, by its first P columns, the graph.
 
-The UMAP / t-SNE plots, the PNG thumbnails and all_colors.npy are not made here.
+Not made here: --mode umap (the default; it writes no map), all_colors.npy (the reference's colour tables are
+its data files), the WebP plots and PNG thumbnails, and the label-supervised second map.
 """
 import argparse
 import os
@@ -34,8 +41,10 @@ def add_arguments(parser):
     parser.add_argument("--gpus", default="0", help="GPU index; -1 (CPU) is refused")
     parser.add_argument("--num_neighbor", type=int, default=None,
                         help="also write knn_graph.npz: the K nearest other picks of every pick (squared L2 over pred)")
+    parser.add_argument("--mode", default="umap", help="tsne with --num_neighbor P: also write embeddings_2d.npz, the t-SNE map "
+                        "at perplexity P; umap (the default) makes no map")
+    parser.add_argument("--map_seed", type=int, default=42, help="seed of the map's random start (the reference's --seed)")
     # accepted for the reference's command lines; they only steer its plots
-    parser.add_argument("--mode", default="umap")
     parser.add_argument("--min_dist_umap", type=float, default=0.5)
     parser.add_argument("--min_dist_vis", type=float, default=None)
     parser.add_argument("--save_out_img", type=int, default=1)
@@ -82,6 +91,25 @@ def knn_graph(projs, k, device):
         return index.cpu().numpy(), dist.cpu().numpy()
 
 
+def tsne_map(projs, perplexity, seed, device):
+    """One search with min(N - 1, 3 perplexity + 1) neighbours, then the map: (index, dist) cut to the first `perplexity`
+    columns - the strict (distance, index) order makes them the search for that many - y (N, 2) fp32, kl, n_iter."""
+    import torch
+    from .utils.tsne import TSNE
+    with torch.cuda.device(device):
+        ts = TSNE(perplexity, seed=seed, device=device)
+        x = torch.from_numpy(projs).to(device)
+        index, dist = ts.graph(x)
+        y = ts.fit_transform(x, graph=(index, dist))
+        return (index[:, :perplexity].cpu().numpy(), dist[:, :perplexity].cpu().numpy(), y, ts.kl_divergence_, ts.n_iter_)
+
+
+def unit_square(y):
+    """(y - min) / (max - min) per axis, as the reference normalises its map (an axis of one value maps to 0)."""
+    lo, hi = y.min(0), y.max(0)
+    return ((y - lo) / np.where(hi > lo, hi - lo, 1)).astype(np.float32)
+
+
 def main(args):
     gpu = int(str(args.gpus).split(",")[0])
     if gpu < 0:
@@ -92,7 +120,14 @@ def main(args):
     projs = np.ascontiguousarray(data["pred"], dtype=np.float32)
     projs = projs.reshape(projs.shape[0], -1)
     names, coords = data["name"], data["coords"]
-    if args.num_neighbor is None:
+    with_map = args.mode == "tsne" and args.num_neighbor is not None
+    if with_map:
+        from .utils.tsne import check_range
+        check_range(len(projs), args.num_neighbor)
+        print("[cet_pick_amd] plot_2d: the plots, thumbnails and colour map are not made here (--min_dist_umap, --min_dist_vis, "
+              "--save_out_img are ignored); --mode tsne --num_neighbor %d writes the neighbour graph knn_graph.npz and the "
+              "t-SNE map embeddings_2d.npz" % args.num_neighbor)
+    elif args.num_neighbor is None:
         print("[cet_pick_amd] plot_2d: the 2-D plots, thumbnails and colour map are not made here (--num_neighbor, --mode, "
               "--min_dist_umap, --min_dist_vis, --save_out_img are ignored)")
     else:
@@ -118,10 +153,19 @@ def main(args):
     print("[cet_pick_amd] plot_2d: %d picks, %d centroids, %d classes, objective %.6g -> %s"
           % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
     if args.num_neighbor is not None:
-        index, dist = knn_graph(projs, args.num_neighbor, torch.device("cuda", gpu))
+        if with_map:
+            index, dist, y, kl, n_iter = tsne_map(projs, args.num_neighbor, args.map_seed, torch.device("cuda", gpu))
+        else:
+            index, dist = knn_graph(projs, args.num_neighbor, torch.device("cuda", gpu))
         np.savez(os.path.join(args.path, "knn_graph.npz"), index=index, dist=dist, k=np.int32(args.num_neighbor))
         print("[cet_pick_amd] plot_2d: %d nearest neighbours of %d picks (squared L2, self excluded) -> %s"
               % (args.num_neighbor, len(index), os.path.join(args.path, "knn_graph.npz")))
+    if with_map:
+        y = np.asarray(y, np.float32)
+        np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=unit_square(y), kl=np.float32(kl), n_iter=np.int32(n_iter),
+                 perplexity=np.int32(args.num_neighbor), seed=np.int32(args.map_seed))
+        print("[cet_pick_amd] plot_2d: t-SNE map of %d picks, perplexity %d, %d iterations, KL %.6g -> %s"
+              % (len(y), args.num_neighbor, n_iter, kl, os.path.join(args.path, "embeddings_2d.npz")))
 
 
 if __name__ == "__main__":

@@ -793,6 +793,35 @@ size_t mi_knn_workspace_bytes(long m, long n, int d, int k, int exclude_self, in
 int mi_knn_search(const float* q, const float* x, long m, long n, int d, int k, int metric, int exclude_self, int n_split,
                   int32_t* out_index, float* out_value, void* ws, size_t ws_bytes, mi_stream_t stream);
 
+/* Exact t-SNE over a k-nearest-neighbour graph (reference plot_2d.py --mode tsne: sklearn.manifold.TSNE, 2 components, one
+ * degree of freedom), DESIGN.md 4.12.  2 <= n <= 2^24, 1 <= k <= 127, k <= n - 1, 0 <= n_split <= 32 (MI_E_UNSUPPORTED
+ * outside, nothing launched; the size entry returns 0).  Edge e = i k + c of the graph runs from row i to row index[e].
+ *   mi_tsne_affinities  dist (n, k) fp32, ascending in a row: per row sklearn's _binary_search_perplexity in double (bisection
+ *                       on beta, doubling while unbounded, at most 100 steps, until |H(beta) - ln perplexity| <= 1e-5), the
+ *                       row's smallest distance subtracted first.  out_beta (n) = beta as fp32, out_p (n, k) = exp(-beta d) /
+ *                       sum at that fp32 value.  A row of equal distances gives 1 / k.  1 <= perplexity <= k.
+ *   mi_tsne_gradient    y (n, 2) fp32; index, p (n, k): the graph and its conditional affinities; rev_ptr (n + 1), rev_edge
+ *                       (n k): the ids of the edges that END in row i are rev_edge[rev_ptr[i] .. rev_ptr[i + 1]), ascending.
+ *                       The joint affinity of a pair is P = (p[i -> j] + p[j -> i]) / 2n, a missing direction counting 0; the
+ *                       rows of index hold distinct neighbours.  With q_ij = 1 / (1 + |y_i - y_j|^2) and Z = sum over i != j
+ *                       of q_ij (out_z): out_grad_i = 4 (exaggeration sum_j P_ij q_ij (y_i - y_j) - sum_{j != i} q_ij^2
+ *                       (y_i - y_j) / Z), and out_kl (may be NULL: not computed) = sum over the pairs with P > 0 of
+ *                       P ln(P Z / q), without the exaggeration.  The all-pairs sums are taken in fp32 over tiles of 128
+ *                       points and in double above that; the j range is divided into n_split parts (0: chosen from n alone)
+ *                       merged in split order.  No floating-point atomics: the same inputs and the same n_split give the same
+ *                       bytes.  Edges that point outside [0, n) and edge ids outside [0, n k) are passed over.
+ *   mi_tsne_update      sklearn's _gradient_descent step on the 2n components: gains + 0.2 where velocity grad < 0, gains 0.8
+ *                       elsewhere, floored at min_gain; velocity = momentum velocity - lr (grad gains); y += velocity.  Every
+ *                       product and sum is rounded once.
+ * ws: mi_tsne_workspace_bytes(n, k, n_split), 16-byte aligned. */
+int mi_tsne_affinities(const float* dist, long n, int k, float perplexity, float* out_p, float* out_beta, mi_stream_t stream);
+size_t mi_tsne_workspace_bytes(long n, int k, int n_split);
+int mi_tsne_gradient(const float* y, const int32_t* index, const float* p, const int32_t* rev_ptr, const int32_t* rev_edge, long n,
+                     int k, float exaggeration, int n_split, float* out_grad, float* out_z, float* out_kl, void* ws,
+                     size_t ws_bytes, mi_stream_t stream);
+int mi_tsne_update(float* y, const float* grad, float* velocity, float* gains, long n, float momentum, float lr, float min_gain,
+                   mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
