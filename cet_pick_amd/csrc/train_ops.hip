@@ -809,7 +809,7 @@ __global__ void scale_by_scalar_kernel(const float* b, const float* g, float mul
     const float s = (*g) * mul;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) da[i] = s * b[i];
 }
-// mean over columns of the unbiased std over rows: torch.std(x, 0).mean()
+// mean over columns of the unbiased std over rows: torch.std(x, 0).mean(); a single row (B = 1) gives 0 where torch gives NaN
 __global__ __launch_bounds__(256) void column_std_mean_kernel(const float* x, float* out, int B, int C) {
     __shared__ float red[4];
     float acc = 0.f;
@@ -917,6 +917,11 @@ __global__ __launch_bounds__(256) void moco_logits_bwd_kernel(const float* dlogi
 // itself, so launches on different streams - the key branch's side stream, a second model, an eager step beside a graph
 // replay - never share tickets.  A null counter falls back to one process-wide word (one call at a time per device).
 __device__ unsigned g_ce0_arrivals = 0;
+// lse = max + log(sum) in ONE fp32 number rounds at the size of the maximum: a common offset of a row's logits then does not cancel
+// in lse - l[0] and exp(l[j] - lse) (offset 1e4: dlogits 1e-4 off).  Below 32 that rounding is under 2^-19 and the one-number form
+// stays (unit dot products over T >= 0.04 never leave it: the training step's arithmetic is what it was); from 32 on the maximum is
+// subtracted first and the log of the sum second.
+__device__ __forceinline__ bool ce0_split(float lse) { return fabsf(lse) >= 32.f; }
 __global__ __launch_bounds__(256) void ce0_rows_kernel(const float* logits, float* loss, float* loss_copy, float* row_loss,
                                                       float* row_lse, int B, int n, unsigned* counter) {
     __shared__ float red[4];
@@ -936,9 +941,13 @@ __global__ __launch_bounds__(256) void ce0_rows_kernel(const float* logits, floa
     if ((tid & 63) == 0) red[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) {
-        const float lse = m + logf(red[0] + red[1] + red[2] + red[3]);
-        row_lse[b] = lse;
-        __hip_atomic_store(&row_loss[b], lse - l[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through
+        // the row's maximum and the log of its sum are kept apart (row_lse[b], row_lse[B + b]): see ce0_split
+        const float ls = logf(red[0] + red[1] + red[2] + red[3]);
+        const float lse = m + ls;
+        row_lse[b] = m;
+        row_lse[B + b] = ls;
+        __hip_atomic_store(&row_loss[b], ce0_split(lse) ? (m - l[0]) + ls : lse - l[0], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);   // write-through
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         s_ticket = atomicAdd(counter ? counter : &g_ce0_arrivals, 1u);
@@ -957,9 +966,13 @@ __global__ __launch_bounds__(256) void ce0_rows_kernel(const float* logits, floa
 __global__ __launch_bounds__(256) void ce0_bwd_kernel(const float* logits, const float* row_lse, const float* g_dev,
                                                      float* dlogits, int B, int n) {
     const int b = blockIdx.x;
-    const float g = (*g_dev) / (float)B, lse = row_lse[b];
+    const float g = (*g_dev) / (float)B, m = row_lse[b], ls = row_lse[B + b], lse = m + ls;
+    const bool split = ce0_split(lse);
     const float* l = logits + (long)b * n;
-    for (int j = threadIdx.x; j < n; j += 256) dlogits[(long)b * n + j] = g * (expf(l[j] - lse) - (j == 0 ? 1.f : 0.f));
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const float e = split ? expf((l[j] - m) - ls) : expf(l[j] - lse);
+        dlogits[(long)b * n + j] = g * (e - (j == 0 ? 1.f : 0.f));
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1209,9 +1222,26 @@ extern "C" int mi_bn_param_grads(const double* sums, int C, float* dgamma, float
     return MI_OK;
 }
 
+// column sums for a channel count the float4 column reduction does not take (a 3-channel bias): one wave per column, rows
+// strided over its lanes, added in double in a fixed order
+__global__ __launch_bounds__(256) void colsum_any_kernel(const float* dy, long M, int C, float* out) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    double s = 0;
+    for (long r = lane; r < M; r += 64) s += (double)dy[r * C + c];
+    s = wave_sum(s);
+    if (lane == 0) out[c] = (float)s;
+}
+
 extern "C" int mi_colsum(const float* dy, long M, int C, float* out, double* sums_scratch, void* ws,
                          size_t ws_bytes, mi_stream_t stream) {
     if (!dy || !out || !sums_scratch) return MI_E_ARG;
+    if (!colreduce_ok(C)) {
+        if (M <= 0 || C <= 0) return MI_E_ARG;
+        hipLaunchKernelGGL(colsum_any_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, M, C, out);
+        MI_RETURN_IF_LAUNCH_FAILED();
+        return MI_OK;
+    }
     ColReduceParams p = {};
     p.a = dy; p.M = M; p.C = C;
     return run_colreduce<CR_SUM>(p, sums_scratch, ws, ws_bytes, (hipStream_t)stream, out, C);

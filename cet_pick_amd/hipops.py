@@ -2156,7 +2156,7 @@ class _CELabel0Fn(torch.autograd.Function):
     def forward(ctx, logits, out):
         b, n = logits.shape
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        rows = torch.empty(2 * b, dtype=torch.float32, device=logits.device)          # row losses | row log-sum-exps
+        rows = torch.empty(3 * b, dtype=torch.float32, device=logits.device)          # row losses | row maxima | log row sums
         word = _ce0_counter(logits.device)
         rc = L.lib().mi_ce_label0_fwd(L.ptr(logits), L.ptr(loss), L.ptr(out), L.ptr(rows), L.ptr(rows[b:]), b, n,
                                       L.ptr(word), L.stream())
@@ -2207,7 +2207,8 @@ def rowdot_mean(a, b):
 
 
 def column_std_mean(x):
-    """torch.std(x, 0).mean() (the SimSiam `output_std` monitor)."""
+    """torch.std(x, 0).mean() (the SimSiam `output_std` monitor).  A single row (B = 1) has no spread: the result is 0,
+    where torch.std gives NaN; a column whose variance rounds below zero counts as 0."""
     out = torch.empty((), dtype=torch.float32, device=x.device)
     L.check(L.lib().mi_column_std_mean(L.ptr(_f32c(x, "x")), L.ptr(out), x.shape[0], x.shape[1], L.stream()),
             "mi_column_std_mean")

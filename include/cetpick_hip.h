@@ -644,7 +644,7 @@ int mi_rowdot_mean_bwd(const float* b, const float* grad_out, float* da, int B, 
 int mi_column_std_mean(const float* x, float* out, int B, int C, mi_stream_t stream);
 /* nn.CrossEntropyLoss against label 0 (trains/tomo_moco_trainer.py:52,73; models/moco.py:141): loss = mean_b(logsumexp(l_b) - l_b[0])
  * in ONE launch (a workgroup per row; the last one to finish takes the mean, in row order), row_loss[B] and
- * row_lse[B] scratch / kept for the backward pass; the backward reads the upstream gradient from the device (no host
+ * row_lse[2B] (the rows' maxima, then the logs of their sums) scratch / kept for the backward pass; the backward reads the upstream gradient from the device (no host
  * value, no extra scaling launch): dlogits = grad_loss * (softmax - onehot0) / B.
  * counter: the arrival counter of the "last workgroup" - ONE 4-byte word owned by the caller, zero before the first call and
  * left zero by every call; give each stream (and each model) its own.  NULL: a process-wide word - one call at a time per device. */
