@@ -327,13 +327,17 @@ __global__ __launch_bounds__(256, 3) void ucl_fwd_kernel(const float* feat, cons
     if (tid < UB && row0 + tid < n2) {
         const float m0 = mrg[0][tid][0], m1 = mrg[1][tid][0], m = fmaxf(m0, m1);
         const float c0 = __builtin_amdgcn_exp2f(m0 - m), c1 = __builtin_amdgcn_exp2f(m1 - m);
+        // 2N <= 32: the second column half saw no column at all, its maximum is -inf like every lane's reference and its three sums
+        // are 0 * exp2(-inf - -inf) = NaN, which c1 = 0 does not clear: they are read as 0 (the first half always holds column 0)
+        const bool half1 = m1 != -INFINITY;
+        const float a1 = half1 ? mrg[1][tid][1] : 0.f, p1 = half1 ? mrg[1][tid][2] : 0.f, o1 = half1 ? mrg[1][tid][3] : 0.f;
         const int row = row0 + tid;
         rowmax[row] = m * 0.6931471805599453f;           // back to natural units
         // the masked diagonal contributes exp(0) = 1 to every column sum it belongs to (loss.py:622-624)
         const uint8_t rc = cls[row];
-        s_all[row] = mrg[0][tid][1] * c0 + mrg[1][tid][1] * c1 + 1.f;
-        s_pos[row] = mrg[0][tid][2] * c0 + mrg[1][tid][2] * c1 + ((rc & 1) ? 1.f : 0.f);
-        s_other[row] = mrg[0][tid][3] * c0 + mrg[1][tid][3] * c1 + ((rc & 2) ? 1.f : 0.f);
+        s_all[row] = mrg[0][tid][1] * c0 + a1 * c1 + 1.f;
+        s_pos[row] = mrg[0][tid][2] * c0 + p1 * c1 + ((rc & 1) ? 1.f : 0.f);
+        s_other[row] = mrg[0][tid][3] * c0 + o1 * c1 + ((rc & 2) ? 1.f : 0.f);
         e_pair[row] = __builtin_amdgcn_exp2f(s_pair[tid] - m);
     }
 }

@@ -28,6 +28,8 @@ class _VoxelLossFn(torch.autograd.Function):
         if p.numel() != g.numel():
             raise ValueError("pred and gt differ in size: %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
         n = p.numel()
+        if n == 0:
+            raise ValueError("voxel loss of an empty tensor: pred %s, gt %s" % (tuple(pred.shape), tuple(gt.shape)))
         lib = L.lib()
         ws = L.workspace(lib.mi_voxel_loss_workspace_bytes(n), p.device, "voxloss")
         sums = torch.empty(11, dtype=torch.float64, device=p.device)
@@ -87,6 +89,10 @@ class FocalLoss(nn.Module):
 
 
 class PULoss(nn.Module):
+    """loss.py:310-324.  Labels without an unlabeled (-1) voxel make the negative risk 0 / 0: the loss is NaN, as the reference's
+    is.  The gradient is then unspecified - the reference's is NaN everywhere, this one's is finite (no voxel takes the 1 / 0
+    coefficient)."""
+
     def __init__(self, tau, beta=0, gamma=1):
         super().__init__()
         self.tau, self.beta, self.gamma = tau, beta, gamma
@@ -104,6 +110,13 @@ class ConsistencyLoss(nn.Module):
 class _UclRowSumsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, cls, inv_T):
+        if feat.dim() != 2 or feat.shape[0] < 2 or feat.shape[0] % 2 or feat.shape[1] not in (32, 64):
+            raise L.HipExtensionError("mi_ucl_rowsums takes (2N, 32) or (2N, 64) features with N >= 1, got %s" % (tuple(feat.shape),))
+        L.require_cuda(feat, "features")
+        L.require_cuda(cls, "class bytes", dtype=torch.uint8)
+        if not feat.is_contiguous() or not cls.is_contiguous() or tuple(cls.shape) != (feat.shape[0],):
+            raise L.HipExtensionError("mi_ucl_rowsums takes contiguous features %s and one contiguous class byte per row, got %s"
+                                      % (tuple(feat.shape), tuple(cls.shape)))
         n2, dim = feat.shape
         dev = feat.device
         outs = [torch.empty(n2, dtype=torch.float32, device=dev) for _ in range(5)]
