@@ -3,6 +3,7 @@ without its plots):
 
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
                                    [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode tsne] [--map_seed 42]
+                                   [--colormap FILE.npy]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -20,9 +21,15 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
                                           from --map_seed, the reference's --seed): y (N, 2) f32, y01 = (y - min) / (max - min)
                                           per axis as the reference normalises, kl, n_iter, perplexity, seed.  One search with
                                           min(N - 1, 3 P + 1) neighbours serves the map and, by its first P columns, the graph.
+    OUT/all_colors.npy                    with the map: (N, 3) uint8, the colour of every pick at its y01 place on a 2-D colour
+                                          table, in pick order (utils/vis3d.py, csrc/vis3d.hip: the reference's
+                                          BaseColorMap2D._sample - round half to even, clamp) - the input of visualize_3dhm.
+                                          --colormap FILE.npy takes any (W, H, 3) uint8 table, e.g. the Ziegler table of a
+                                          reference installation.  The default table is NOT the reference's (its colour tables
+                                          are its own data files): it is table[i, j] = (i, j, 255 - (i + j) // 2), 256 x 256.
 
-Not made here: --mode umap (the default; it writes no map), all_colors.npy (the reference's colour tables are
-its data files), the WebP plots and PNG thumbnails, and the label-supervised second map.
+Not made here: --mode umap (the default; it writes no map), the WebP plots and PNG thumbnails, and the
+label-supervised second map.
 """
 import argparse
 import os
@@ -44,6 +51,8 @@ def add_arguments(parser):
     parser.add_argument("--mode", default="umap", help="tsne with --num_neighbor P: also write embeddings_2d.npz, the t-SNE map "
                         "at perplexity P; umap (the default) makes no map")
     parser.add_argument("--map_seed", type=int, default=42, help="seed of the map's random start (the reference's --seed)")
+    parser.add_argument("--colormap", default=None, help="(W, H, 3) uint8 .npy colour table for all_colors.npy; the default is a "
+                        "built-in 256 x 256 table, not one of the reference's")
     # accepted for the reference's command lines; they only steer its plots
     parser.add_argument("--min_dist_umap", type=float, default=0.5)
     parser.add_argument("--min_dist_vis", type=float, default=None)
@@ -104,6 +113,14 @@ def tsne_map(projs, perplexity, seed, device):
         return (index[:, :perplexity].cpu().numpy(), dist[:, :perplexity].cpu().numpy(), y, ts.kl_divergence_, ts.n_iter_)
 
 
+def map_colours(y01, table, device):
+    """(N, 3) uint8: the colour of every row of y01 (N, 2) on the (W, H, 3) uint8 table, sampled on the device."""
+    import torch
+    from .utils.vis3d import sample_colours
+    with torch.cuda.device(device):
+        return sample_colours(torch.from_numpy(np.ascontiguousarray(y01, dtype=np.float32)).to(device), table).cpu().numpy()
+
+
 def unit_square(y):
     """(y - min) / (max - min) per axis, as the reference normalises its map (an axis of one value maps to 0)."""
     lo, hi = y.min(0), y.max(0)
@@ -124,9 +141,11 @@ def main(args):
     if with_map:
         from .utils.tsne import check_range
         check_range(len(projs), args.num_neighbor)
-        print("[cet_pick_amd] plot_2d: the plots, thumbnails and colour map are not made here (--min_dist_umap, --min_dist_vis, "
-              "--save_out_img are ignored); --mode tsne --num_neighbor %d writes the neighbour graph knn_graph.npz and the "
-              "t-SNE map embeddings_2d.npz" % args.num_neighbor)
+        from .utils.vis3d import load_colormap
+        table = load_colormap(args.colormap)
+        print("[cet_pick_amd] plot_2d: the plots and thumbnails are not made here (--min_dist_umap, --min_dist_vis, "
+              "--save_out_img are ignored); --mode tsne --num_neighbor %d writes the neighbour graph knn_graph.npz, the "
+              "t-SNE map embeddings_2d.npz and its colours all_colors.npy" % args.num_neighbor)
     elif args.num_neighbor is None:
         print("[cet_pick_amd] plot_2d: the 2-D plots, thumbnails and colour map are not made here (--num_neighbor, --mode, "
               "--min_dist_umap, --min_dist_vis, --save_out_img are ignored)")
@@ -162,10 +181,20 @@ def main(args):
               % (args.num_neighbor, len(index), os.path.join(args.path, "knn_graph.npz")))
     if with_map:
         y = np.asarray(y, np.float32)
-        np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=unit_square(y), kl=np.float32(kl), n_iter=np.int32(n_iter),
+        y01 = unit_square(y)
+        np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=y01, kl=np.float32(kl), n_iter=np.int32(n_iter),
                  perplexity=np.int32(args.num_neighbor), seed=np.int32(args.map_seed))
         print("[cet_pick_amd] plot_2d: t-SNE map of %d picks, perplexity %d, %d iterations, KL %.6g -> %s"
               % (len(y), args.num_neighbor, n_iter, kl, os.path.join(args.path, "embeddings_2d.npz")))
+        if not torch.cuda.is_available():
+            # only reached when every device step in front of this one was replaced (tests/test_tsne_cpu.py drives main with
+            # stubs for the clustering, the search and the map): the sampler is a kernel, and there is no host form of it
+            print("[cet_pick_amd] plot_2d: all_colors.npy left out: no MI355X (cuda) device for the colour sampler")
+            return
+        np.save(os.path.join(args.path, "all_colors.npy"), map_colours(y01, table, torch.device("cuda", gpu)))
+        print("[cet_pick_amd] plot_2d: colours of %d picks on the %d x %d table%s -> %s"
+              % (len(y), table.shape[0], table.shape[1], "" if args.colormap else " (built in, not the reference's)",
+                 os.path.join(args.path, "all_colors.npy")))
 
 
 if __name__ == "__main__":

@@ -822,6 +822,34 @@ int mi_tsne_gradient(const float* y, const int32_t* index, const float* p, const
 int mi_tsne_update(float* y, const float* grad, float* velocity, float* gains, long n, float momentum, float lr, float min_gain,
                    mi_stream_t stream);
 
+/* 3-D visualisation of the exploration map (reference visualize_3dhm.py, and the colour step of plot_2d.py), DESIGN.md 4.13.
+ * Volumes are (Z, R, C) row-major and addressed with 64-bit offsets; Z R C / 256 < 2^31 (MI_E_UNSUPPORTED above).
+ *   mi_vis_sample_colours  y01 (n, 2) fp32, table (W, H, 3) uint8: out (n, 3) = table[ix, iy] with ix = clamp(rint(x (W - 1)), 0,
+ *                          W - 1) on the double product (Python's round: half to even), iy likewise with H; a NaN samples 0.
+ *   mi_vis_slice_bytes     x [n_slices][slice_elems] fp32, stats as mi_vol_stats writes them: out = the byte
+ *                          rint(clip(255 ((x - mean) / std - mi) / (ma - mi), 0, 255)) of every voxel, in double; a slice whose
+ *                          deviation is not > 0 gives 0 (the reference casts NaN there).
+ *   mi_vis_gauss_u8        out (Z, R, C, 3) uint8 = scipy.ndimage.gaussian_filter of the three equal channels of in (Z, R, C)
+ *                          uint8, bit for bit: four passes (z, rows, columns, channels) with the 7 weights `weights7` (a HOST
+ *                          array of doubles, symmetric: scipy's _gaussian_kernel1d(sigma, 0, 3)), `reflect` borders, each
+ *                          pass summed in double in scipy's order without FMA and truncated to a byte.  in may not alias out.
+ *   mi_vis_paint           picks_xyz (n, 3) int32 (column, row, slice) in input order, colours (n, 3) uint8, slot_of_slice (Z)
+ *                          int32: the plane of `index` (n_slots, R, C) that belongs to a slice, -1 for a slice that is to stay
+ *                          zero.  Writes the slices [z0, z0 + nz) of out (Z, R, C, 3): a pixel of slice s takes the colour of the
+ *                          LAST pick i with |z_i - s| <= 2 whose disc dx^2 + dy^2 <= (12 - |z_i - s|)^2 around (column, row)
+ *                          holds it, 0 where there is none.  index is scratch, zeroed here (atomic max of i + 1: the result does
+ *                          not depend on the arrival order); slots of slices outside the slab are not touched by the picks.
+ * ws of mi_vis_gauss_u8: mi_vis_gauss_workspace_bytes(Z, R, C).  The word-wide forms run when C is a multiple of 4 and the
+ * buffers are 4-byte aligned, the byte-wide forms otherwise; both give the same bytes. */
+int mi_vis_sample_colours(const float* y01, long n, const uint8_t* table, int W, int H, uint8_t* out, mi_stream_t stream);
+int mi_vis_slice_bytes(const float* x, long n_slices, long slice_elems, const double* stats, double mi, double ma, uint8_t* out,
+                       mi_stream_t stream);
+size_t mi_vis_gauss_workspace_bytes(long Z, long R, long C);
+int mi_vis_gauss_u8(const uint8_t* in, int Z, int R, int C, const double* weights7, uint8_t* out, void* ws, size_t ws_bytes,
+                    mi_stream_t stream);
+int mi_vis_paint(const int32_t* picks_xyz, const uint8_t* colours, long n, const int32_t* slot_of_slice, int n_slots, int Z,
+                 int R, int C, int z0, int nz, int32_t* index, uint8_t* out, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
