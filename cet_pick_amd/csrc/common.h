@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <atomic>
 #include "../../include/cetpick_hip.h"
 
 #define MI_RETURN_IF_LAUNCH_FAILED()                  \
@@ -17,6 +18,21 @@
     } while (0)
 
 static inline size_t mi_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Lets `kernels` take up to `bytes` of dynamic LDS (the default limit is 64 KB): once per device, remembered in the call
+// site's `static std::atomic<bool> done[64]`.  Two host threads that race here both set the same value, and a failed
+// attempt is made again by the next call.  Returns a status as MI_HIP does.
+template <typename... Kernels>
+inline int mi_allow_dynamic_lds(std::atomic<bool> (&done)[64], int bytes, Kernels... kernels) {
+    int dev = 0;
+    MI_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return MI_E_UNSUPPORTED;
+    if (done[dev].load(std::memory_order_acquire)) return MI_OK;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        MI_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done[dev].store(true, std::memory_order_release);
+    return MI_OK;
+}
 
 // BatchNorm1d (training mode) + optional ReLU in the epilogue of a small dense product (conv_cube2.hip small_gemm_kernel)
 struct MiSmallGemmBN {

@@ -263,12 +263,9 @@ extern "C" int mi_crop_normalize(const float* vol, int D, int H, int W, const in
     if (mode == CROP_ZNORM_RESCALE_ZNORM) {
         const size_t bytes = sizeof(float) * (size_t)cz * cy * cx;
         if (bytes > 128 * 1024) return MI_E_UNSUPPORTED;            // (6, 48, 48) = 54 KiB; 32^3 = 128 KiB
-        static bool attr_set = false;
-        if (!attr_set) {
-            MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(crop_chain_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            attr_set = true;
-        }
+        static std::atomic<bool> lds_allowed[64];
+        const int ra = mi_allow_dynamic_lds(lds_allowed, 128 * 1024, crop_chain_kernel);
+        if (ra != MI_OK) return ra;
         hipLaunchKernelGGL(crop_chain_kernel, dim3(n), dim3(256), bytes, (hipStream_t)stream, vol, D, H, W,
                            (const int*)centres_xyz, cz, cy, cx, flip_x, out);
         MI_RETURN_IF_LAUNCH_FAILED();

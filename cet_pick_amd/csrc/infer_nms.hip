@@ -768,13 +768,9 @@ extern "C" int mi_sigmoid_nms_topk(const float* logits, float* heat_out, int D, 
     apply_sigmoid &= 1;
     if (!self_clean) MI_HIP(hipMemsetAsync(hdr, 0, sizeof(DecodeHeader), s));
     // 128 KiB of dynamic LDS for the single-workgroup sorter (above the 64 KiB default limit)
-    static bool attr_set = false;
-    if (!attr_set) {
-        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_final_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(MI_SEL_CAP * sizeof(unsigned long long))));
-        attr_set = true;
-    }
+    static std::atomic<bool> lds_allowed[64];
+    const int ra = mi_allow_dynamic_lds(lds_allowed, (int)(MI_SEL_CAP * sizeof(unsigned long long)), topk_final_kernel);
+    if (ra != MI_OK) return ra;
     float* val_out = apply_sigmoid ? heat_out : nullptr;
 
     if (!fiber && k == 3 && mi_decode1_usable(logits, val_out, D, H, W, K))

@@ -1,9 +1,11 @@
 // k-means over the exploration embeddings (reference plot_2d.py: faiss.Kmeans(d, 256, niter=300, gpu=True)), DESIGN.md 4.9.
-//   prep    centroids (k, d) f32 -> an image of their bf16x3 cut in B-fragment order + |c_j|^2           (once per iteration)
+//   prep    centroids (k, d) f32 -> the operand image of rowdot.h: their bf16x3 cut in B-fragment order + |c_j|^2, +inf
+//           for the columns that pad k to 32                                                             (once per iteration)
 //   xnorm   |x_i|^2                                                                                      (once per fit)
 //   assign  labels[i] = argmin_j |x_i|^2 + (|c_j|^2 - 2 x_i . c_j), lowest index on ties; dist[i]; per-workgroup objective
 //           partials.  The N x k x d product runs on v_mfma_f32_32x32x16_bf16 in the library's bf16x3 arithmetic (six
-//           products of an exact 3-way cut, smallest terms first: bf16x3.h).
+//           products of an exact 3-way cut, smallest terms first: bf16x3.h) through the row-product tile of
+//           rowdot.h, which knn.hip shares: dist and the squared L2 distance of knn_search are the same bytes.
 //   update  a stable counting sort of the point indices by label (integers only), sums over fixed 64-position segments
 //           of the sorted order in position order, per-cluster reduction of the segment partials in segment order (f64),
 //           then the empty-cluster rule and the objective on one workgroup.  No floating-point atomics: same inputs,
@@ -11,7 +13,7 @@
 // Rows are addressed with 64-bit offsets throughout (N x d may exceed 2 GiB); N < 2^31.
 // hipcc-flags: -fno-slp-vectorize
 #include "common.h"
-#include "bf16x3.h"
+#include "rowdot.h"
 #include "../../include/cetpick_hip.h"
 
 namespace {
@@ -23,54 +25,12 @@ constexpr int KM_CHUNK = 1024;            // points per workgroup of the countin
 constexpr int KM_SEG = 64;                // sorted positions per first-level partial sum (one wave)
 constexpr float KM_EPS = 1.f / 1024.f;
 
-// eight consecutive features k8 .. k8 + 7 of one row (zero past d or when the row does not exist)
-__device__ __forceinline__ void km_load8(const float* row, bool ok, int k8, int d, bool vec, float (&v)[8]) {
-    if (ok && vec && k8 + 8 <= d) {
-        ld8(row + k8, v);
-    } else {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = (ok && k8 + t < d) ? row[k8 + t] : 0.f;
-    }
-}
-
-struct KmShape { int KS, KT; };           // k-steps of 16 features, column tiles of 32 centroids
-inline KmShape km_shape(int d, int k) { return {(d + 15) / 16, (k + 31) / 32}; }
-inline size_t km_image_planes_bytes(int d, int k) { const KmShape s = km_shape(d, k); return (size_t)s.KT * s.KS * 3 * 1024; }
-
-// image[((ct KS + ks) 3 + plane) 64 + lane] (16 bytes) = plane `plane` of centroid ct 32 + (lane & 31), features
-// 16 ks + 8 (lane >> 5) .. + 7: the B operand of one MFMA is one contiguous 1 KB read.  Behind the planes: |c_j|^2 for
-// KT 32 columns, +inf for the columns past k.  One 64-thread workgroup per column.
-__global__ __launch_bounds__(64) void km_prep_kernel(const float* cent, int d, int k, int KS, unsigned char* img, float* cnorm) {
-    const int j = blockIdx.x, lane = threadIdx.x;
-    const bool ok = j < k;
-    const float* row = cent + (size_t)j * d;
-    const bool vec = (d & 3) == 0;
-    float s = 0.f;
-    for (int g = lane; g < 2 * KS; g += 64) {
-        float v[8];
-        km_load8(row, ok, g * 8, d, vec, v);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) s = fmaf(v[t], v[t], s);
-        u32x4 o[3];
-        cut8(v, o);
-        const int ks = g >> 1, h = g & 1, ct = j >> 5, l32 = j & 31;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            *reinterpret_cast<u32x4*>(img + ((((size_t)ct * KS + ks) * 3 + pl) * 64 + h * 32 + l32) * 16) = o[pl];
-    }
-    s = wave_sum(s);
-    if (lane == 0) cnorm[j] = ok ? s : INFINITY;
-}
-
-// one wave per row
+// |x_i|^2, one wave per row
 __global__ __launch_bounds__(256) void km_xnorm_kernel(const float* x, long n, int d, float* xnorm) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     const int lane = threadIdx.x & 63;
-    const float* p = x + (size_t)row * d;
-    float s = 0.f;
-    for (int f = lane; f < d; f += 64) s = fmaf(p[f], p[f], s);
-    s = wave_sum(s);
+    const float s = rowdot::row_sqnorm(x + (size_t)row * d, d, lane);
     if (lane == 0) xnorm[row] = s;
 }
 
@@ -78,10 +38,9 @@ __device__ __forceinline__ void km_better(float& v, int& i, float v2, int i2) {
     if (v2 < v || (v2 == v && i2 < i)) { v = v2; i = i2; }
 }
 
-// A workgroup owns 32 RM points: their bf16x3 cut is staged once into LDS (three planes, row pitch KS 32 + 16 bytes: the
-// 16-byte fragment reads of eight consecutive lanes fall on disjoint banks) and stays for all k centroids.  The four waves
-// share the rows and take the column tiles ct = wave, wave + 4, ...; the centroid fragments stream from the image (L2) to
-// registers and serve RM row tiles each.  Epilogue per column tile: v = |c|^2 - 2 acc, a running (min, index) per
+// A workgroup owns 32 RM points: their bf16x3 cut is staged once into LDS (rowdot.h) and stays for all k centroids.  The four
+// waves share the rows and take the column tiles ct = wave, wave + 4, ...; the centroid fragments stream from the image (L2)
+// to registers and serve RM row tiles each.  Epilogue per column tile: v = |c|^2 - 2 acc, a running (min, index) per
 // accumulator register (columns ascend within a lane: strict < keeps the lowest index), merged across the 32 lanes of a
 // row and then across the four waves with the (value, lowest index) rule.
 template <int RM>
@@ -90,20 +49,10 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* x, const fl
                                                         float* dist, double* objpart) {
     extern __shared__ __attribute__((aligned(16))) unsigned char km_lds[];
     constexpr int RT = 32 * RM;
-    const int PITCH = KS * 32 + 16, PLANE = RT * PITCH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l32 = lane & 31;
     const long row0 = (long)blockIdx.x * RT;
-    const bool vec = (d & 3) == 0;
 
-    for (int q = tid; q < RT * 2 * KS; q += 256) {
-        const int r = q / (2 * KS), g = q - r * 2 * KS;
-        float v[8];
-        km_load8(x + (size_t)(row0 + r) * d, row0 + r < n, g * 8, d, vec, v);
-        u32x4 o[3];
-        cut8(v, o);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(km_lds + pl * PLANE + r * PITCH + g * 16) = o[pl];
-    }
+    rowdot::stage_rows<RM>(km_lds, x, row0, n, d, KS, tid);
     __syncthreads();
 
     float best[RM][16];
@@ -115,28 +64,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* x, const fl
 
     for (int ct = wave; ct < KT; ct += 4) {
         f32x16 acc[RM];
-#pragma unroll
-        for (int m = 0; m < RM; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-        const unsigned char* bp = img + ((size_t)ct * KS * 3 * 64 + lane) * 16;
-        for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 bf[3];
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-                bf[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bp + (size_t)(ks * 3 + pl) * 1024));
-#pragma unroll
-            for (int m = 0; m < RM; ++m) {
-                bf16x8 af[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)
-                    af[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(km_lds + pl * PLANE + (m * 32 + l32) * PITCH +
-                                                                                         ks * 32 + h * 16));
-#pragma unroll
-                for (int pr = 0; pr < 6; ++pr)
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[pr]], bf[PB[pr]], acc[m], 0, 0, 0);
-            }
-        }
+        rowdot::tile_product<RM>(acc, km_lds, img, ct, KS, lane, h, l32);
         const int col = ct * 32 + l32;
         const float cn = cnorm[col];
 #pragma unroll
@@ -160,7 +88,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* x, const fl
 #pragma unroll
             for (int o = 16; o > 0; o >>= 1) km_better(v, i, __shfl_xor(v, o, 64), __shfl_xor(i, o, 64));
             if (l32 == 0) {
-                const int tr = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int tr = rowdot::acc_row(m, r, h);
                 mv[wave * RT + tr] = v;
                 mi[wave * RT + tr] = i;
             }
@@ -410,7 +338,7 @@ inline int km_check(long n, int d, int k) {
 
 extern "C" size_t mi_kmeans_image_bytes(int d, int k) {
     if (d < 1 || d > KM_DMAX || k < 2 || k > KM_KMAX) return 0;
-    return km_image_planes_bytes(d, k) + (size_t)km_shape(d, k).KT * 32 * 4;
+    return rowdot::image_bytes(k, d);
 }
 
 extern "C" size_t mi_kmeans_workspace_bytes(long n, int d, int k) {
@@ -422,10 +350,10 @@ extern "C" int mi_kmeans_prep(const float* centroids, int d, int k, void* image,
     if (!centroids || !image) return MI_E_ARG;
     if (d < 1 || d > KM_DMAX || k < 2 || k > KM_KMAX) return MI_E_UNSUPPORTED;
     if ((uintptr_t)image & 15) return MI_E_ARG;
-    const KmShape s = km_shape(d, k);
+    const rowdot::Shape s = rowdot::shape(k, d);
     unsigned char* img = (unsigned char*)image;
-    hipLaunchKernelGGL(km_prep_kernel, dim3((unsigned)(s.KT * 32)), dim3(64), 0, (hipStream_t)stream, centroids, d, k, s.KS, img,
-                       (float*)(img + km_image_planes_bytes(d, k)));
+    hipLaunchKernelGGL(rowdot::prep_kernel, dim3((unsigned)(s.KT * 32)), dim3(64), 0, (hipStream_t)stream, centroids, (long)k, d, s.KS,
+                       INFINITY, img, (float*)(img + rowdot::planes_bytes(k, d)));
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
@@ -446,27 +374,21 @@ extern "C" int mi_kmeans_assign(const float* x, const float* xnorm, const void* 
     if (((uintptr_t)image & 15) || ((uintptr_t)ws & 15) || (((uintptr_t)x & 15) && !(d & 3))) return MI_E_ARG;
     const KmWs w = km_ws(n, d, k);
     if (ws_bytes < w.total) return MI_E_WORKSPACE;
-    const KmShape s = km_shape(d, k);
+    const rowdot::Shape s = rowdot::shape(k, d);
     const unsigned char* img = (const unsigned char*)image;
-    const float* cnorm = (const float*)(img + km_image_planes_bytes(d, k));
+    const float* cnorm = (const float*)(img + rowdot::planes_bytes(k, d));
     double* objpart = (double*)((unsigned char*)ws + w.objpart);
     const int rt = km_rows_per_wg(d);
-    const size_t lds = (size_t)rt * (s.KS * 32 + 16) * 3;              // <= 100 KB of the CU's 160 KB
-    static bool attr_done[64] = {};                                     // per device
-    int dev = 0;
-    MI_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return MI_E_UNSUPPORTED;
-    if (!attr_done[dev]) {
-        MI_HIP(hipFuncSetAttribute((const void*)km_assign_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-        MI_HIP(hipFuncSetAttribute((const void*)km_assign_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-        attr_done[dev] = true;
-    }
+    const size_t lds = rowdot::lds_planes_bytes(rt, s.KS);             // <= 100 KB of the CU's 160 KB
+    static std::atomic<bool> lds_allowed[64];
+    const int ra = mi_allow_dynamic_lds(lds_allowed, 112 * 1024, km_assign_kernel<2>, km_assign_kernel<1>);
+    if (ra != MI_OK) return ra;
     if (rt == 64)
         hipLaunchKernelGGL(km_assign_kernel<2>, dim3((unsigned)w.npart), dim3(256), lds, (hipStream_t)stream, x, xnorm, img, cnorm, n, d,
-                           s.KS, s.KT, labels, dist, objpart);
+                           s.KS, (int)s.KT, labels, dist, objpart);
     else
         hipLaunchKernelGGL(km_assign_kernel<1>, dim3((unsigned)w.npart), dim3(256), lds, (hipStream_t)stream, x, xnorm, img, cnorm, n, d,
-                           s.KS, s.KT, labels, dist, objpart);
+                           s.KS, (int)s.KT, labels, dist, objpart);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }

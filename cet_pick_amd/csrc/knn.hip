@@ -1,23 +1,23 @@
 // Exact k-nearest-neighbour search over embeddings (reference utils/memory_bank.py: faiss.IndexFlatIP / matmul + topk),
 // DESIGN.md 4.11.  Queries q (M, d), database x (N, d), 1 <= k <= 128: the k best database rows of every query, best first.
-//   prep    database -> an image of its bf16x3 cut in B-fragment order (the layout of km_prep_kernel, kmeans.hip, for N columns)
-//           + |x_j|^2                                                                                     (once per search)
+//   prep    database -> the operand image of rowdot.h: its bf16x3 cut in B-fragment order + |x_j|^2, 0 for the columns
+//           that pad N to 32 (the search never takes such a column)                                       (once per search)
 //   search  a workgroup owns 64 queries (32 when the LDS bill of 64 passes 160 KB; their cut staged once in LDS) and one split
-//           of the column tiles.  The M x N x d
-//           product runs on v_mfma_f32_32x32x16_bf16 in the library's bf16x3 arithmetic (bf16x3.h).  The
-//           similarity matrix is never written: every query row has a sorted top-k list in LDS, the list's last entry is the
-//           row's threshold, and only accumulator entries that beat it are inserted.  Every split writes its lists.
+//           of the column tiles.  The M x N x d product runs on v_mfma_f32_32x32x16_bf16 in the library's bf16x3 arithmetic
+//           (bf16x3.h) through the row-product tile of rowdot.h, which kmeans.hip shares.  The similarity
+//           matrix is never written: every query row has a sorted top-k list in LDS, the list's last entry is the row's
+//           threshold, and only accumulator entries that beat it are inserted.  Every split writes its lists.
 //   merge   one workgroup per query: the rank of every partial entry among all partials of the row, lists visited in split
 //           order; ranks < k are the result.
-// Order: keys are "larger is better" (q.x, or 2 q.x - |x|^2 for squared L2: the exact negative of |x|^2 - 2 q.x), and
-// (key, lower index) is a strict total order on the columns of a row.  The top k of a total order do not depend on the order
-// in which candidates arrive or on how the columns are split, and the key of a (row, column) pair is one fixed MFMA chain:
-// no floating-point atomics, same inputs -> same bytes, for any split count.  A NaN key counts as -inf.
+// Order: keys are "larger is better" (q.x, or 2 q.x - |x|^2 for squared L2: the exact negative of |x|^2 - 2 q.x, so the
+// squared L2 distance to the nearest row and the dist of kmeans_assign are the same bytes), and (key, lower index) is a
+// strict total order on the columns of a row.  The top k of a total order do not depend on the order in which candidates
+// arrive or on how the columns are split, and the key of a (row, column) pair is one fixed MFMA chain: no floating-point
+// atomics, same inputs -> same bytes, for any split count.  A NaN key counts as -inf.
 // Rows are addressed with 64-bit offsets throughout (N x d may exceed 2 GiB); M, N < 2^31.
 // hipcc-flags: -fno-slp-vectorize
-#include <atomic>
 #include "common.h"
-#include "bf16x3.h"
+#include "rowdot.h"
 #include "../../include/cetpick_hip.h"
 
 namespace {
@@ -28,49 +28,8 @@ constexpr int KNN_DMAX = 512, KNN_KMAX = 128, KNN_SMAX = 32;
 constexpr int KNN_LDS_MAX = 160 * 1024;  // one workgroup may take the CU's whole LDS
 constexpr int KNN_NONE = 0x7fffffff;     // index of a list entry that holds no column (key -inf): loses every tie
 
-// eight consecutive features k8 .. k8 + 7 of one row (zero past d or when the row does not exist)
-__device__ __forceinline__ void knn_load8(const float* row, bool ok, int k8, int d, bool vec, float (&v)[8]) {
-    if (ok && vec && k8 + 8 <= d) {
-        ld8(row + k8, v);
-    } else {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = (ok && k8 + t < d) ? row[k8 + t] : 0.f;
-    }
-}
-
 // (v2, i2) comes before (v, i): larger key, lowest index on ties
 __device__ __forceinline__ bool knn_before(float v2, int i2, float v, int i) { return v2 > v || (v2 == v && i2 < i); }
-
-struct KnnShape { int KS; long KT; };     // k-steps of 16 features, column tiles of 32 database rows
-inline KnnShape knn_shape(long n, int d) { return {(d + 15) / 16, (n + 31) / 32}; }
-inline size_t knn_planes_bytes(long n, int d) { const KnnShape s = knn_shape(n, d); return (size_t)s.KT * s.KS * 3 * 1024; }
-
-// image[((ct KS + ks) 3 + plane) 64 + lane] (16 bytes) = plane `plane` of database row ct 32 + (lane & 31), features
-// 16 ks + 8 (lane >> 5) .. + 7: the B operand of one MFMA is one contiguous 1 KB read.  Behind the planes: |x_j|^2 for
-// KT 32 columns (0 past N; the search never takes such a column).  One wave per column.
-__global__ __launch_bounds__(256) void knn_prep_kernel(const float* x, long n, int d, int KS, unsigned char* img, float* xnorm) {
-    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const bool ok = j < n;
-    const float* row = x + (size_t)j * d;
-    const bool vec = (d & 3) == 0;
-    float s = 0.f;
-    for (int g = lane; g < 2 * KS; g += 64) {
-        float v[8];
-        knn_load8(row, ok, g * 8, d, vec, v);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) s = fmaf(v[t], v[t], s);
-        u32x4 o[3];
-        cut8(v, o);
-        const int ks = g >> 1, h = g & 1, l32 = (int)(j & 31);
-        const long ct = j >> 5;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            *reinterpret_cast<u32x4*>(img + ((((size_t)ct * KS + ks) * 3 + pl) * 64 + h * 32 + l32) * 16) = o[pl];
-    }
-    s = wave_sum(s);
-    if (lane == 0) xnorm[j] = ok ? s : 0.f;
-}
 
 // The whole wave puts (cv, cc) into the sorted list (lv, li) of k entries, if it comes before the list's last entry.
 // Entry e is held by lane e & 63; the entries that come before the candidate are a prefix, so its place is their number.
@@ -95,8 +54,8 @@ __device__ __forceinline__ void knn_insert(float* lv, int* li, int k, int lane, 
     if (k > 64 && e1 < k && e1 >= place) { lv[e1] = e1 == place ? cv : p1; li[e1] = e1 == place ? cc : q1; }
 }
 
-// LDS: three planes of the queries' cut (row pitch KS 32 + 16 bytes as in km_assign_kernel), the lists' keys [RT][k] and
-// indices [RT][k], and two sets of four flags.  The four waves share the rows; in step t wave w takes column tile
+// LDS: three planes of the queries' cut (rowdot.h), the lists' keys [RT][k] and indices [RT][k], and two sets of four
+// flags.  The four waves share the rows; in step t wave w takes column tile
 // ct0 + 4 t + w of the split.  A step: the products; the filter against the lists' last entries (nobody writes a list
 // then); one barrier; then the waves that found candidates insert them one wave after the other, a barrier behind each, so a
 // list has one writer at a time.  Once the lists have filled, most steps find nothing and cost the one barrier.
@@ -106,23 +65,14 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float* q, const u
                                                          int* pidx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char knn_lds[];
     constexpr int RT = 32 * RM;
-    const int PITCH = KS * 32 + 16, PLANE = RT * PITCH;
-    float* lv = reinterpret_cast<float*>(knn_lds + 3 * PLANE);
+    float* lv = reinterpret_cast<float*>(knn_lds + 3 * RT * rowdot::lds_pitch(KS));
     int* li = reinterpret_cast<int*>(lv + RT * k);
     int* has = li + RT * k;                                // [2][4]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l32 = lane & 31;
     const long row0 = (long)blockIdx.x * RT;
     const long ct0 = (long)blockIdx.y * tps, ct1 = ct0 + tps < KT ? ct0 + tps : KT;
-    const bool vec = (d & 3) == 0;
 
-    for (int s = tid; s < RT * 2 * KS; s += 256) {
-        const int r = s / (2 * KS), g = s - r * 2 * KS;
-        float v[8];
-        knn_load8(q + (size_t)(row0 + r) * d, row0 + r < M, g * 8, d, vec, v);
-        u32x4 o[3];
-        cut8(v, o);
-        store_planes(knn_lds + r * PITCH + g * 16, PLANE, o);
-    }
+    rowdot::stage_rows<RM>(knn_lds, q, row0, M, d, KS, tid);
     for (int s = tid; s < RT * k; s += 256) { lv[s] = -INFINITY; li[s] = KNN_NONE; }
     __syncthreads();
 
@@ -133,38 +83,17 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float* q, const u
         f32x16 acc[RM];
         unsigned cand[RM];
 #pragma unroll
-        for (int m = 0; m < RM; ++m) {
-            cand[m] = 0u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-        }
+        for (int m = 0; m < RM; ++m) cand[m] = 0u;
         const long col = ct * 32 + l32;
         if (live) {
-            const unsigned char* bp = img + ((size_t)ct * KS * 3 * 64 + lane) * 16;
-            for (int ks = 0; ks < KS; ++ks) {
-                bf16x8 bf[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)
-                    bf[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bp + (size_t)(ks * 3 + pl) * 1024));
-#pragma unroll
-                for (int m = 0; m < RM; ++m) {
-                    bf16x8 af[3];
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl)
-                        af[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(knn_lds + pl * PLANE + (m * 32 + l32) * PITCH +
-                                                                                             ks * 32 + h * 16));
-#pragma unroll
-                    for (int pr = 0; pr < 6; ++pr)
-                        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[pr]], bf[PB[pr]], acc[m], 0, 0, 0);
-                }
-            }
+            rowdot::tile_product<RM>(acc, knn_lds, img, ct, KS, lane, h, l32);
             const float cn = l2 ? xnorm[col] : 0.f;        // xnorm has KT 32 entries
             const bool colok = col < N;
 #pragma unroll
             for (int m = 0; m < RM; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int tr = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int tr = rowdot::acc_row(m, r, h);
                     float key = l2 ? fmaf(2.f, acc[m][r], -cn) : acc[m][r];
                     key = key == key ? key : -INFINITY;
                     acc[m][r] = key;
@@ -195,7 +124,7 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float* q, const u
                             const int src = __builtin_ctzll(mask);
                             mask &= mask - 1;
                             const float cv = __shfl(acc[m][r], src, 64);
-                            const int tr = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (src >> 5);
+                            const int tr = rowdot::acc_row(m, r, src >> 5);
                             knn_insert(lv + tr * k, li + tr * k, k, lane, cv, (int)(ct * 32 + (src & 31)));
                         }
                     }
@@ -230,13 +159,8 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* q, const fl
         mv[e] = pval[o];
         mi[e] = pidx[o];
     }
-    if (tid < 64) {                                        // |q|^2 as km_xnorm_kernel sums it
-        float s = 0.f;
-        if (l2) {
-            const float* p = q + (size_t)row * d;
-            for (int f = tid; f < d; f += 64) s = fmaf(p[f], p[f], s);
-            s = wave_sum(s);
-        }
+    if (tid < 64) {
+        const float s = l2 ? rowdot::row_sqnorm(q + (size_t)row * d, d, tid) : 0.f;
         if (tid == 0) qn_s = s;
     }
     __syncthreads();
@@ -269,7 +193,9 @@ inline int knn_check(long m, long n, int d, int k, int excl, int n_split) {
         return MI_E_UNSUPPORTED;
     return MI_OK;
 }
-inline size_t knn_lds_bytes(int rt, int d, int k) { return (size_t)rt * (((d + 15) / 16) * 32 + 16) * 3 + (size_t)rt * k * 8 + 32; }
+inline size_t knn_lds_bytes(int rt, int d, int k) {
+    return rowdot::lds_planes_bytes(rt, rowdot::shape(0, d).KS) + (size_t)rt * k * 8 + 32;
+}
 inline int knn_rows_per_wg(int d, int k) { return knn_lds_bytes(64, d, k) <= (size_t)KNN_LDS_MAX ? 64 : 32; }
 struct KnnPlan { int rt, S; long tps, rtiles; };
 // Splits: enough workgroups for two rounds over the chip's 256 CUs, at least eight column tiles each; a forced count is
@@ -278,7 +204,7 @@ inline KnnPlan knn_plan(long m, long n, int d, int k, int n_split) {
     KnnPlan p;
     p.rt = knn_rows_per_wg(d, k);
     p.rtiles = (m + p.rt - 1) / p.rt;
-    const long KT = knn_shape(n, d).KT;
+    const long KT = rowdot::shape(n, d).KT;
     long S = n_split;
     if (S == 0) {
         S = (512 + p.rtiles - 1) / p.rtiles;
@@ -296,8 +222,8 @@ inline KnnWs knn_ws(long m, long n, int d, int k, int n_split) {
     const KnnPlan p = knn_plan(m, n, d, k, n_split);
     KnnWs w;
     size_t o = 0;
-    w.image = o; o += mi_align_up(knn_planes_bytes(n, d), 256);
-    w.xnorm = o; o += mi_align_up((size_t)knn_shape(n, d).KT * 32 * 4, 256);
+    w.image = o; o += mi_align_up(rowdot::planes_bytes(n, d), 256);
+    w.xnorm = o; o += mi_align_up((size_t)rowdot::shape(n, d).KT * 32 * 4, 256);
     w.pval = o; o += mi_align_up((size_t)p.S * m * k * 4, 256);
     w.pidx = o; o += mi_align_up((size_t)p.S * m * k * 4, 256);
     w.total = o;
@@ -308,7 +234,7 @@ inline KnnWs knn_ws(long m, long n, int d, int k, int n_split) {
 
 extern "C" size_t mi_knn_image_bytes(long n, int d) {
     if (d < 1 || d > KNN_DMAX || n < 1 || n >= (1l << 31)) return 0;
-    return knn_planes_bytes(n, d) + (size_t)knn_shape(n, d).KT * 32 * 4;
+    return rowdot::image_bytes(n, d);
 }
 
 extern "C" size_t mi_knn_workspace_bytes(long m, long n, int d, int k, int exclude_self, int n_split) {
@@ -326,25 +252,17 @@ extern "C" int mi_knn_search(const float* q, const float* x, long m, long n, int
     const KnnWs w = knn_ws(m, n, d, k, n_split);
     if (ws_bytes < w.total) return MI_E_WORKSPACE;
     const KnnPlan p = knn_plan(m, n, d, k, n_split);
-    const KnnShape s = knn_shape(n, d);
+    const rowdot::Shape s = rowdot::shape(n, d);
     unsigned char* b = (unsigned char*)ws;
     unsigned char* img = b + w.image;
     float* xnorm = (float*)(b + w.xnorm);
     float* pval = (float*)(b + w.pval);
     int* pidx = (int*)(b + w.pidx);
     hipStream_t st = (hipStream_t)stream;
-    // Per device, once: two host threads that race here both set the same value, and a failed attempt is made again by the
-    // next call.
-    static std::atomic<bool> attr_done[64];
-    int dev = 0;
-    MI_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return MI_E_UNSUPPORTED;
-    if (!attr_done[dev].load(std::memory_order_acquire)) {
-        MI_HIP(hipFuncSetAttribute((const void*)knn_search_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, KNN_LDS_MAX));
-        MI_HIP(hipFuncSetAttribute((const void*)knn_search_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, KNN_LDS_MAX));
-        attr_done[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)(s.KT * 8)), dim3(256), 0, st, x, n, d, s.KS, img, xnorm);
+    static std::atomic<bool> lds_allowed[64];
+    const int ra = mi_allow_dynamic_lds(lds_allowed, KNN_LDS_MAX, knn_search_kernel<2>, knn_search_kernel<1>);
+    if (ra != MI_OK) return ra;
+    hipLaunchKernelGGL(rowdot::prep_kernel, dim3((unsigned)(s.KT * 8)), dim3(256), 0, st, x, n, d, s.KS, 0.f, img, xnorm);
     const size_t lds = knn_lds_bytes(p.rt, d, k);
     const dim3 grid((unsigned)p.rtiles, (unsigned)p.S);
     const int l2 = metric == MI_KNN_L2, excl = exclude_self != 0;

@@ -107,6 +107,32 @@ def test_ties_go_to_the_lowest_index(metric, k):
         assert np.array_equal(value.astype(np.float64), want_v)
 
 
+@pytest.mark.parametrize("n_split", [1, 2])
+@pytest.mark.parametrize("d", [17, 100, 300])
+def test_l2_nearest_neighbour_is_the_kmeans_assignment_bit_for_bit(d, n_split):
+    """The contract of csrc/rowdot.h: the squared L2 distance of knn_search and the dist of kmeans_assign are
+    one product chain, one column-norm sum and one row-norm sum, and both orders take the lowest index on ties - so the
+    nearest of k centroids is the k-means label and its value the same bytes.  M = 257: four 64-row workgroups and one row;
+    48 centroids: a full column tile and half of one (the padding columns carry +inf in one image and 0 in the other);
+    duplicates inside a tile and across the tile boundary; d = 17 scalar loads and a ragged k-step, 100 vector loads with a
+    scalar last group, 300 32-row workgroups in k-means against 64-row ones here."""
+    import torch
+    from cet_pick_amd import hipops as H
+    M, k = 257, 48
+    x = _dev(R.make(M, d, seed=7, spread=0.15))
+    c = R.make(k, d, seed=11, spread=0.15)
+    c[40], c[33] = c[5], c[2]
+    c = _dev(c)
+    labels, dist = H.kmeans_assign(x, H.kmeans_xnorm(x), H.kmeans_prep(c), k)
+    index, value = H.knn_search(x, c, 1, metric="l2", n_split=n_split)
+    differ = index[:, 0] != labels
+    print("d=%d n_split=%d: %d of %d indices differ, %d values differ" % (
+        d, n_split, int(differ.sum()), M, int((value[:, 0].view(torch.int32) != dist.view(torch.int32)).sum())))
+    assert not bool(((labels == 40) | (labels == 33)).any())          # a duplicate never wins over its lower-index twin
+    assert torch.equal(index[:, 0], labels)
+    assert torch.equal(value[:, 0].contiguous().view(torch.int32), dist.view(torch.int32))
+
+
 # 6 ------------------------------------------------------------------------------------------------------------------------
 def test_unsupported_arguments_are_refused():
     import torch

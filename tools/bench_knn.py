@@ -97,7 +97,7 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the MI355X"
     from cet_pick_amd.build import source_sha16
-    out = {"kernels_sha16": source_sha16(["knn", "bf16x3"]), "device": torch.cuda.get_device_name(0),
+    out = {"kernels_sha16": source_sha16(["knn", "rowdot", "bf16x3"]), "device": torch.cuda.get_device_name(0),
            "ceilings": {"bf16x3_tflops": BF16X3_CEILING / 1e12}, "sizes": []}
     for s in a.sizes.split(","):
         N, d, k = (int(v) for v in s.split("x"))
