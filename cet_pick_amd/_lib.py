@@ -191,6 +191,11 @@ SIGNATURES = {
     "mi_tsne_workspace_bytes": (_Z, [_L, _I, _I]),
     "mi_tsne_gradient": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
     "mi_tsne_update": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _P]),
+    # UMAP over the neighbour graph (csrc/umap.hip)
+    "mi_umap_check": (_I, [_L, _I]),
+    "mi_umap_smooth_knn": (_I, [_P, _L, _I, _D, _P, _P, _P, _P]),
+    "mi_umap_union": (_I, [_P, _P, _P, _P, _L, _I, _P, _I, _P, _P, _P, _P]),
+    "mi_umap_epoch": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _D, _D, _c.c_uint64, _P]),
     # colours of the map, 8-bit Gaussian and disc painter of the 3-D visualisation (csrc/vis3d.hip)
     "mi_vis_sample_colours": (_I, [_P, _L, _P, _I, _I, _P, _P]),
     "mi_vis_slice_bytes": (_I, [_P, _L, _L, _P, _D, _D, _P, _P]),

@@ -2648,3 +2648,66 @@ def tsne_update(y, grad, velocity, gains, momentum, lr, min_gain=0.01):
     L.check(L.lib().mi_tsne_update(L.ptr(y), L.ptr(grad), L.ptr(velocity), L.ptr(gains), y.shape[0], float(momentum), float(lr),
                                    float(min_gain), L.stream()), "mi_tsne_update(N=%d)" % y.shape[0])
     return y
+
+
+# ---- UMAP over the neighbour graph (csrc/umap.hip) -------------------------------------------------------------------------
+
+def umap_smooth_knn(dist2, mean_all):
+    """(rho (N,), sigma (N,), w (N, k)) fp32 of the squared distances dist2 (N, k) to the k = n_neighbors - 1 nearest other
+    points: umap-learn's smooth_knn_dist and membership weights.  mean_all: sum of all sqrt(dist2) / (N (k + 1))."""
+    dist2 = _km_x(dist2, "dist2")
+    n, k = dist2.shape
+    rho = torch.empty(n, dtype=torch.float32, device=dist2.device)
+    sigma, w = torch.empty_like(rho), torch.empty_like(dist2)
+    L.check(L.lib().mi_umap_smooth_knn(L.ptr(dist2), n, k, float(mean_all), L.ptr(rho), L.ptr(sigma), L.ptr(w), L.stream()),
+            "mi_umap_smooth_knn(N=%d, k=%d)" % (n, k))
+    return rho, sigma, w
+
+
+def umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=None, out=None):
+    """(wsym (N, k) fp32, mutual (N, k) uint8, eps (N, k) float64) of the graph index (N, k) int32 with membership weights w and
+    its transpose (utils/tsne.reverse_graph).  wmax: a (1,) fp32 device tensor holding the largest wsym; without it eps is not
+    written (the first of the two launches: wsym, its maximum by torch, then the spacings)."""
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2:
+        raise L.HipExtensionError("index must be (N, k), got %s" % (tuple(index.shape),))
+    n, k = index.shape
+    _ts_table(index, "index", (n, k), torch.int32)
+    _ts_table(w, "w", (n, k))
+    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
+    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    if wmax is not None:
+        _ts_table(wmax, "wmax", (1,))
+    if out is None:
+        out = (torch.empty(n, k, dtype=torch.float32, device=w.device), torch.empty(n, k, dtype=torch.uint8, device=w.device),
+               torch.empty(n, k, dtype=torch.float64, device=w.device))
+    wsym, mutual, eps = _ts_table(out[0], "out[0]", (n, k)), _ts_table(out[1], "out[1]", (n, k), torch.uint8), \
+        _ts_table(out[2], "out[2]", (n, k), torch.float64)
+    L.check(L.lib().mi_umap_union(L.ptr(index), L.ptr(w), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, L.ptr(wmax), int(n_epochs),
+                                  L.ptr(wsym), L.ptr(mutual), L.ptr(eps), L.stream()), "mi_umap_union(N=%d, k=%d)" % (n, k))
+    return wsym, mutual, eps
+
+
+def umap_epoch(y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epochs, a, b, seed):
+    """y_out = y_in + alpha (the attractions and negatives of the incident pairs that fire at `epoch` of n_epochs), every vertex
+    from y_in alone (the epoch-synchronous form of umap-learn's loop); y_in, y_out (N, 2) fp32, two different buffers."""
+    y_in = _km_x(y_in, "y_in")
+    n = y_in.shape[0]
+    if y_in.shape[1] != 2:
+        raise L.HipExtensionError("y_in must be (N, 2), got %s" % (tuple(y_in.shape),))
+    _ts_table(y_out, "y_out", (n, 2))
+    if y_out.data_ptr() == y_in.data_ptr():
+        raise L.HipExtensionError("y_out may not alias y_in")
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2 or index.shape[0] != n:
+        raise L.HipExtensionError("index must be (N, k) with N = %d, got %s" % (n, tuple(index.shape)))
+    k = index.shape[1]
+    _ts_table(index, "index", (n, k), torch.int32)
+    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
+    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    _ts_table(mutual, "mutual", (n, k), torch.uint8)
+    _ts_table(eps, "eps", (n, k), torch.float64)
+    L.check(L.lib().mi_umap_epoch(L.ptr(y_in), L.ptr(y_out), L.ptr(index), L.ptr(rev_ptr), L.ptr(rev_edge), L.ptr(mutual), L.ptr(eps),
+                                  n, k, int(epoch), int(n_epochs), float(a), float(b), int(seed) & (2 ** 64 - 1), L.stream()),
+            "mi_umap_epoch(N=%d, k=%d, epoch %d of %d)" % (n, k, epoch, n_epochs))
+    return y_out

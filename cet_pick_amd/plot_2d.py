@@ -1,9 +1,9 @@
-"""Cluster the exploration embeddings, write the per-pick class table and the 2-D t-SNE map (the reference's plot_2d.py
-without its plots):
+"""Cluster the exploration embeddings, write the per-pick class table and the 2-D UMAP or t-SNE map (the reference's
+plot_2d.py without its plots):
 
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
-                                   [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode tsne] [--map_seed 42]
-                                   [--colormap FILE.npy]
+                                   [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode umap | --mode tsne]
+                                   [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -21,6 +21,11 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
                                           from --map_seed, the reference's --seed): y (N, 2) f32, y01 = (y - min) / (max - min)
                                           per axis as the reference normalises, kl, n_iter, perplexity, seed.  One search with
                                           min(N - 1, 3 P + 1) neighbours serves the map and, by its first P columns, the graph.
+                                          With --mode umap --num_neighbor K, given EXPLICITLY: the UMAP map of `pred` with
+                                          n_neighbors K and min_dist --min_dist_umap (utils/umap.py, csrc/umap.hip: umap-learn's
+                                          constants in an epoch-synchronous form, its init="random" from --map_seed): y, y01,
+                                          n_epochs, n_neighbors, min_dist, a, b, seed.  One search with K neighbours serves the
+                                          graph and, by its first K - 1 columns (UMAP counts the pick itself), the map.
     OUT/all_colors.npy                    with the map: (N, 3) uint8, the colour of every pick at its y01 place on a 2-D colour
                                           table, in pick order (utils/vis3d.py, csrc/vis3d.hip: the reference's
                                           BaseColorMap2D._sample - round half to even, clamp) - the input of visualize_3dhm.
@@ -28,13 +33,21 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
                                           reference installation.  The default table is NOT the reference's (its colour tables
                                           are its own data files): it is table[i, j] = (i, j, 255 - (i + j) // 2), 256 x 256.
 
-Not made here: --mode umap (the default; it writes no map), the WebP plots and PNG thumbnails, and the
-label-supervised second map.
+Only an explicit `--mode umap` makes the UMAP map.  The reference's default mode is umap too, but a command line without
+--mode has always run here without a map (with --num_neighbor: the graph alone), and scripts and tests rely on its output and on
+the files it does not write; the parser therefore tells the given value from the default one (DefaultMode), and making the bare
+default draw the map is a one-line change in main.
+
+Not made here: UMAP's spectral start, the WebP plots and PNG thumbnails, and the label-supervised second map.
 """
 import argparse
 import os
 
 import numpy as np
+
+
+class DefaultMode(str):
+    """The value of --mode on a command line that does not give it: equal to "umap", and told from a given "umap" by its type."""
 
 
 def add_arguments(parser):
@@ -48,13 +61,14 @@ def add_arguments(parser):
     parser.add_argument("--gpus", default="0", help="GPU index; -1 (CPU) is refused")
     parser.add_argument("--num_neighbor", type=int, default=None,
                         help="also write knn_graph.npz: the K nearest other picks of every pick (squared L2 over pred)")
-    parser.add_argument("--mode", default="umap", help="tsne with --num_neighbor P: also write embeddings_2d.npz, the t-SNE map "
-                        "at perplexity P; umap (the default) makes no map")
+    parser.add_argument("--mode", default=DefaultMode("umap"), help="with --num_neighbor K also write embeddings_2d.npz: tsne, the "
+                        "t-SNE map at perplexity K; umap, given explicitly, the UMAP map with n_neighbors K.  Without --mode no "
+                        "map is made")
     parser.add_argument("--map_seed", type=int, default=42, help="seed of the map's random start (the reference's --seed)")
     parser.add_argument("--colormap", default=None, help="(W, H, 3) uint8 .npy colour table for all_colors.npy; the default is a "
                         "built-in 256 x 256 table, not one of the reference's")
+    parser.add_argument("--min_dist_umap", type=float, default=0.5, help="min_dist of the UMAP map (the reference: 0.5)")
     # accepted for the reference's command lines; they only steer its plots
-    parser.add_argument("--min_dist_umap", type=float, default=0.5)
     parser.add_argument("--min_dist_vis", type=float, default=None)
     parser.add_argument("--save_out_img", type=int, default=1)
     return parser
@@ -113,6 +127,19 @@ def tsne_map(projs, perplexity, seed, device):
         return (index[:, :perplexity].cpu().numpy(), dist[:, :perplexity].cpu().numpy(), y, ts.kl_divergence_, ts.n_iter_)
 
 
+def umap_map(projs, n_neighbors, min_dist, seed, device):
+    """One search with n_neighbors other picks, then the map from its first n_neighbors - 1 columns: index, dist, y (N, 2)
+    fp32, n_epochs and the curve parameters a, b."""
+    import torch
+    from .utils.umap import UMAP
+    with torch.cuda.device(device):
+        um = UMAP(n_neighbors, min_dist=min_dist, seed=seed, device=device)
+        x = torch.from_numpy(projs).to(device)
+        index, dist = um.graph(x)
+        y = um.fit_transform(x, graph=(index, dist))
+        return index.cpu().numpy(), dist.cpu().numpy(), y, um.n_epochs_, um.a_, um.b_
+
+
 def map_colours(y01, table, device):
     """(N, 3) uint8: the colour of every row of y01 (N, 2) on the (W, H, 3) uint8 table, sampled on the device."""
     import torch
@@ -137,12 +164,24 @@ def main(args):
     projs = np.ascontiguousarray(data["pred"], dtype=np.float32)
     projs = projs.reshape(projs.shape[0], -1)
     names, coords = data["name"], data["coords"]
-    with_map = args.mode == "tsne" and args.num_neighbor is not None
+    with_tsne = args.mode == "tsne" and args.num_neighbor is not None
+    # the bare default is "umap" as well, and keeps writing no map (the module docstring says why); to change that, drop the
+    # isinstance test
+    with_umap = args.mode == "umap" and not isinstance(args.mode, DefaultMode) and args.num_neighbor is not None
+    with_map = with_tsne or with_umap
     if with_map:
-        from .utils.tsne import check_range
-        check_range(len(projs), args.num_neighbor)
         from .utils.vis3d import load_colormap
+        if with_umap:
+            from .utils.umap import check_range
+        else:
+            from .utils.tsne import check_range
+        check_range(len(projs), args.num_neighbor)
         table = load_colormap(args.colormap)
+    if with_umap:
+        print("[cet_pick_amd] plot_2d: the plots and thumbnails are not made here (--min_dist_vis, --save_out_img are ignored); "
+              "--mode umap --num_neighbor %d writes the neighbour graph knn_graph.npz, the UMAP map embeddings_2d.npz (min_dist "
+              "%g) and its colours all_colors.npy" % (args.num_neighbor, args.min_dist_umap))
+    elif with_tsne:
         print("[cet_pick_amd] plot_2d: the plots and thumbnails are not made here (--min_dist_umap, --min_dist_vis, "
               "--save_out_img are ignored); --mode tsne --num_neighbor %d writes the neighbour graph knn_graph.npz, the "
               "t-SNE map embeddings_2d.npz and its colours all_colors.npy" % args.num_neighbor)
@@ -172,7 +211,9 @@ def main(args):
     print("[cet_pick_amd] plot_2d: %d picks, %d centroids, %d classes, objective %.6g -> %s"
           % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
     if args.num_neighbor is not None:
-        if with_map:
+        if with_umap:
+            index, dist, y, n_epochs, a, b = umap_map(projs, args.num_neighbor, args.min_dist_umap, args.map_seed, torch.device("cuda", gpu))
+        elif with_tsne:
             index, dist, y, kl, n_iter = tsne_map(projs, args.num_neighbor, args.map_seed, torch.device("cuda", gpu))
         else:
             index, dist = knn_graph(projs, args.num_neighbor, torch.device("cuda", gpu))
@@ -182,10 +223,17 @@ def main(args):
     if with_map:
         y = np.asarray(y, np.float32)
         y01 = unit_square(y)
-        np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=y01, kl=np.float32(kl), n_iter=np.int32(n_iter),
-                 perplexity=np.int32(args.num_neighbor), seed=np.int32(args.map_seed))
-        print("[cet_pick_amd] plot_2d: t-SNE map of %d picks, perplexity %d, %d iterations, KL %.6g -> %s"
-              % (len(y), args.num_neighbor, n_iter, kl, os.path.join(args.path, "embeddings_2d.npz")))
+        if with_umap:
+            np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=y01, n_epochs=np.int32(n_epochs),
+                     n_neighbors=np.int32(args.num_neighbor), min_dist=np.float32(args.min_dist_umap), a=np.float64(a),
+                     b=np.float64(b), seed=np.int32(args.map_seed))
+            print("[cet_pick_amd] plot_2d: UMAP map of %d picks, n_neighbors %d, min_dist %g, %d epochs -> %s"
+                  % (len(y), args.num_neighbor, args.min_dist_umap, n_epochs, os.path.join(args.path, "embeddings_2d.npz")))
+        else:
+            np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=y01, kl=np.float32(kl), n_iter=np.int32(n_iter),
+                     perplexity=np.int32(args.num_neighbor), seed=np.int32(args.map_seed))
+            print("[cet_pick_amd] plot_2d: t-SNE map of %d picks, perplexity %d, %d iterations, KL %.6g -> %s"
+                  % (len(y), args.num_neighbor, n_iter, kl, os.path.join(args.path, "embeddings_2d.npz")))
         if not torch.cuda.is_available():
             # only reached when every device step in front of this one was replaced (tests/test_tsne_cpu.py drives main with
             # stubs for the clustering, the search and the map): the sampler is a kernel, and there is no host form of it

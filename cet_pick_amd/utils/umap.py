@@ -1,0 +1,114 @@
+"""UMAP on the MI355X (csrc/umap.hip) with the constants of the `umap.UMAP(n_neighbors=K, min_dist=m, random_state=seed)` the
+reference's plot_2d.py runs:
+
+    um = UMAP(n_neighbors=40, min_dist=0.5, seed=42); y = um.fit_transform(x); um.n_epochs_; um.a_; um.b_
+
+The K - 1 nearest other points of every point by L2 (n_neighbors counts the point itself; hipops.knn_search returns the squared
+distance), umap-learn's smooth distances (rho the nearest positive distance, sigma by bisection to log2 K, floored at 1e-3 of
+the mean distance), the fuzzy union a + b - a b kept on the directed graph, (a, b) fitted to min_dist by scipy on the host,
+500 epochs up to 10000 points and 200 above, every pair sampled every wmax / w epochs, 5 negatives per sample, the learning
+rate falling linearly from 1.
+
+Departures from umap-learn:
+  1. The epoch is SYNCHRONOUS.  umap-learn moves points in place, pair after pair (and, run in parallel, races on them); here
+     every force of an epoch is evaluated from the positions at its start, summed per vertex in a fixed order in double and
+     applied once.  The map is then a pure function of (graph, seed): repeated runs give identical bytes, and every term can be
+     checked against a float64 restatement.
+  2. The start is umap-learn's init="random" (numpy.random.RandomState(seed).uniform(-10, 10, (N, 2))); its default, the
+     spectral start, is not built.
+  3. Exactly 5 negatives per sample (umap-learn's floating-point bookkeeping gives 5, now and then 4 or 6), drawn by
+     Philox-4x32-10 from (vertex, incident slot, epoch, seed).
+2 <= n_neighbors <= 128, N >= n_neighbors + 1.  There is no CPU path.
+"""
+import numpy as np
+import torch
+
+from .. import _lib as L
+from .. import hipops as H
+from .tsne import reverse_graph
+
+N_NEIGHBORS_MIN, N_NEIGHBORS_MAX = 2, 128       # K - 1 <= 127 columns, and the neighbour search's k <= 128
+EPOCHS_SMALL, EPOCHS_LARGE, SMALL_N = 500, 200, 10000
+
+
+def check_range(n, n_neighbors):
+    """ValueError outside the supported range, before anything is launched."""
+    if int(n_neighbors) != n_neighbors or not N_NEIGHBORS_MIN <= n_neighbors <= N_NEIGHBORS_MAX:
+        raise ValueError("n_neighbors must be an integer in %d..%d (the point itself and up to 127 others), got %r"
+                         % (N_NEIGHBORS_MIN, N_NEIGHBORS_MAX, n_neighbors))
+    if n < n_neighbors + 1:
+        raise ValueError("n_neighbors %d needs N >= n_neighbors + 1 = %d points, got %d" % (n_neighbors, n_neighbors + 1, n))
+
+
+def find_ab_params(min_dist, spread=1.0):
+    """umap-learn's curve: (a, b) of 1 / (1 + a x^(2b)) fitted on linspace(0, 3 spread, 300) to 1 below min_dist and
+    exp(-(x - min_dist) / spread) above.  Host plumbing; it needs scipy."""
+    try:
+        from scipy.optimize import curve_fit
+    except ImportError as e:
+        raise RuntimeError("UMAP fits its curve parameters (a, b) with scipy.optimize.curve_fit, and scipy does not import (%s)"
+                           % e) from None
+    x = np.linspace(0, spread * 3, 300)
+    y = np.where(x < min_dist, 1.0, np.exp(-(x - min_dist) / spread))
+    p, _ = curve_fit(lambda x, a, b: 1.0 / (1.0 + a * x ** (2 * b)), x, y)
+    return float(p[0]), float(p[1])
+
+
+class UMAP:
+    def __init__(self, n_neighbors, min_dist=0.5, seed=42, n_epochs=None, device="cuda"):
+        self.n_neighbors, self.min_dist, self.seed = n_neighbors, float(min_dist), int(seed)
+        self.n_epochs = None if n_epochs is None else int(n_epochs)
+        self.device = torch.device(device)
+        self.embedding_, self.n_epochs_, self.a_, self.b_ = None, None, None, None
+
+    find_ab_params = staticmethod(find_ab_params)
+    check_range = staticmethod(check_range)
+
+    def graph(self, x):
+        """(index (N, K) int32, dist (N, K) fp32 squared L2) of x on the device: the search for n_neighbors = K other points.
+        The map takes its first K - 1 columns."""
+        return H.knn_search(x, x, int(self.n_neighbors), metric="l2", exclude_self=True)
+
+    def fit_transform(self, x, graph=None):
+        """(N, 2) float32 numpy.  graph: (index, dist) of a search already made, with K or K - 1 columns."""
+        n = int(x.shape[0])
+        check_range(n, self.n_neighbors)
+        if self.n_epochs is not None and self.n_epochs < 1:
+            raise ValueError("n_epochs must be at least 1, got %d" % self.n_epochs)
+        if self.device.type != "cuda":
+            raise L.HipExtensionError("UMAP runs on the MI355X (cuda) device; there is no CPU path")
+        a, b = find_ab_params(self.min_dist)
+        with torch.cuda.device(self.device):
+            if graph is None:
+                if isinstance(x, np.ndarray):
+                    x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(n, -1)).to(self.device)
+                graph = self.graph(L.require_cuda(x, "x").contiguous())
+            index, dist = graph
+            k = int(self.n_neighbors) - 1
+            if index.shape[0] != n or index.shape[1] not in (k, k + 1) or tuple(dist.shape) != tuple(index.shape):
+                raise ValueError("graph must have N = %d rows and %d or %d columns, got %s" % (n, k, k + 1, tuple(index.shape)))
+            return self._fit(index[:, :k].contiguous(), dist[:, :k].contiguous(), a, b)
+
+    def setup(self, index, dist, n_epochs):
+        """(rev_ptr, rev_edge, mutual, eps) of the graph's K - 1 columns: what the epochs read."""
+        n, k = index.shape
+        mean_all = float(torch.sqrt(dist).sum(dtype=torch.float64).item()) / (n * (k + 1))
+        w = H.umap_smooth_knn(dist, mean_all)[2]
+        rev_ptr, rev_edge = reverse_graph(index)
+        out = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs)
+        wmax = out[0].max().reshape(1)                      # stays on the device
+        _, mutual, eps = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=wmax, out=out)
+        return rev_ptr, rev_edge, mutual, eps
+
+    def _fit(self, index, dist, a, b):
+        n = index.shape[0]
+        n_epochs = self.n_epochs or (EPOCHS_SMALL if n <= SMALL_N else EPOCHS_LARGE)
+        rev_ptr, rev_edge, mutual, eps = self.setup(index, dist, n_epochs)
+        y0 = np.random.RandomState(self.seed % 2 ** 32).uniform(-10, 10, (n, 2)).astype(np.float32)
+        y, y2 = torch.from_numpy(y0).to(index.device), torch.empty(n, 2, dtype=torch.float32, device=index.device)
+        for epoch in range(1, n_epochs + 1):
+            H.umap_epoch(y, y2, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epochs, a, b, self.seed)
+            y, y2 = y2, y
+        self.n_epochs_, self.a_, self.b_ = n_epochs, a, b
+        self.embedding_ = y.cpu().numpy()
+        return self.embedding_

@@ -822,6 +822,37 @@ int mi_tsne_gradient(const float* y, const int32_t* index, const float* p, const
 int mi_tsne_update(float* y, const float* grad, float* velocity, float* gains, long n, float momentum, float lr, float min_gain,
                    mi_stream_t stream);
 
+/* UMAP over a k-nearest-neighbour graph (reference plot_2d.py --mode umap: umap.UMAP, 2 components), in its epoch-synchronous
+ * form, DESIGN.md 4.14.  k is the number of COLUMNS of the graph, n_neighbors - 1 (UMAP counts the point itself).  1 <= k <= 127,
+ * n >= k + 2, n k < 2^31 (MI_E_UNSUPPORTED outside, nothing launched; mi_umap_check is that test alone, on the host).  Edge
+ * e = i k + c runs from row i to row index[e]; rev_ptr, rev_edge as mi_tsne_gradient takes them.
+ *   mi_umap_smooth_knn  dist2 (n, k) fp32 squared distances: d = sqrt as fp32; per row, in double, rho = the smallest positive d
+ *                       (0 where there is none) and sigma by bisection from 1 (doubling while unbounded, at most 64 steps) until
+ *                       |sum_c (d_c > rho ? exp(-(d_c - rho) / sigma) : 1) - log2(k + 1)| < 1e-5, then floored at 1e-3 times the
+ *                       row's mean distance sum_c d_c / (k + 1), or at 1e-3 mean_all where rho = 0.  out_rho, out_sigma (n)
+ *                       fp32; out_w (n, k) = exp(-max(0, d - rho) / sigma) at the double sigma.
+ *   mi_umap_union       per directed edge: out_wsym = a + b - a b with a = w[e] and b the weight of the opposite edge, 0 where
+ *                       there is none; out_mutual (n k bytes) = 1 where it exists.  With wmax (one DEVICE float, the largest
+ *                       wsym; NULL: out_eps is not written) out_eps (n k doubles) = wmax / wsym, +inf for an edge with
+ *                       wsym < wmax / n_epochs.  An edge that points outside [0, n) or at its own row gets 0, 0, +inf.
+ *   mi_umap_epoch       epoch `epoch` of n_epochs, 1-based, alpha = 1 - (epoch - 1) / n_epochs.  The incident pairs of vertex i
+ *                       are its forward edges (slot = column) and then the edges that end in it and have mutual = 0, in
+ *                       ascending edge id (slots k, k + 1, ...).  A pair with spacing eps fires iff floor(epoch / eps) >
+ *                       floor((epoch - 1) / eps); a firing adds 2 clip(c (y_i - y_j)), c = -2 a b d2^(b - 1) / (a d2^b + 1) (0 at
+ *                       d2 = 0), and for t = 0..4 the negative v = mulhi(word, n), word = philox4x32_10(i, slot, epoch, t / 4;
+ *                       seed)[t % 4]: nothing for v = i, +4 on both components at d2 = 0, else clip(2 b / ((0.001 + d2) (a d2^b
+ *                       + 1)) (y_i - y_v)); clip to [-4, 4] per component.  y_out_i = fp32(y_in_i + alpha sum), every term
+ *                       and the sum in double from y_in alone; y_out may not alias y_in.  No floating-point atomics: the same
+ *                       inputs give the same bytes.  Edge ids and destinations outside their range are passed over. */
+int mi_umap_check(long n, int k);
+int mi_umap_smooth_knn(const float* dist2, long n, int k, double mean_all, float* out_rho, float* out_sigma, float* out_w,
+                       mi_stream_t stream);
+int mi_umap_union(const int32_t* index, const float* w, const int32_t* rev_ptr, const int32_t* rev_edge, long n, int k,
+                  const float* wmax, int n_epochs, float* out_wsym, uint8_t* out_mutual, double* out_eps, mi_stream_t stream);
+int mi_umap_epoch(const float* y_in, float* y_out, const int32_t* index, const int32_t* rev_ptr, const int32_t* rev_edge,
+                  const uint8_t* mutual, const double* eps, long n, int k, int epoch, int n_epochs, double a, double b, uint64_t seed,
+                  mi_stream_t stream);
+
 /* 3-D visualisation of the exploration map (reference visualize_3dhm.py, and the colour step of plot_2d.py), DESIGN.md 4.13.
  * Volumes are (Z, R, C) row-major and addressed with 64-bit offsets; Z R C / 256 < 2^31 (MI_E_UNSUPPORTED above).
  *   mi_vis_sample_colours  y01 (n, 2) fp32, table (W, H, 3) uint8: out (n, 3) = table[ix, iy] with ix = clamp(rint(x (W - 1)), 0,
