@@ -196,6 +196,14 @@ SIGNATURES = {
     "mi_umap_smooth_knn": (_I, [_P, _L, _I, _D, _P, _P, _P, _P]),
     "mi_umap_union": (_I, [_P, _P, _P, _P, _L, _I, _P, _I, _P, _P, _P, _P]),
     "mi_umap_epoch": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _D, _D, _c.c_uint64, _P]),
+    # the spectral start of the UMAP map (csrc/spectral.hip)
+    "mi_graph_components": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P]),
+    "mi_spectral_degree": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
+    "mi_spectral_spmv": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _L, _L, _P]),
+    "mi_spectral_workspace_bytes": (_Z, [_I, _L]),
+    "mi_spectral_dots": (_I, [_P, _L, _I, _L, _P, _P, _P, _Z, _P]),
+    "mi_spectral_orth": (_I, [_P, _L, _I, _L, _P, _P, _P, _Z, _P]),
+    "mi_spectral_combine": (_I, [_P, _L, _I, _L, _P, _P, _D, _P]),
     # colours of the map, 8-bit Gaussian and disc painter of the 3-D visualisation (csrc/vis3d.hip)
     "mi_vis_sample_colours": (_I, [_P, _L, _P, _I, _I, _P, _P]),
     "mi_vis_slice_bytes": (_I, [_P, _L, _L, _P, _D, _D, _P, _P]),

@@ -2711,3 +2711,111 @@ def umap_epoch(y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epoc
                                   n, k, int(epoch), int(n_epochs), float(a), float(b), int(seed) & (2 ** 64 - 1), L.stream()),
             "mi_umap_epoch(N=%d, k=%d, epoch %d of %d)" % (n, k, epoch, n_epochs))
     return y_out
+
+
+# ---- the spectral start of the UMAP map (csrc/spectral.hip) ----------------------------------------------------------------
+
+def _sp_graph(index, eps, mutual, rev_ptr, rev_edge, wsym=None):
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2:
+        raise L.HipExtensionError("index must be (N, k), got %s" % (tuple(index.shape),))
+    n, k = index.shape
+    _ts_table(index, "index", (n, k), torch.int32)
+    _ts_table(eps, "eps", (n, k), torch.float64)
+    _ts_table(mutual, "mutual", (n, k), torch.uint8)
+    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
+    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    if wsym is not None:
+        _ts_table(wsym, "wsym", (n, k))
+    return n, k
+
+
+def graph_components(index, eps, mutual, rev_ptr, rev_edge):
+    """(label (N,) int32, sweeps): the smallest vertex id of every vertex's connected component in the graph the UMAP epochs walk
+    (forward edges and lone reverse edges, finite eps only).  One launch per sweep; the device flag is read between launches."""
+    n, k = _sp_graph(index, eps, mutual, rev_ptr, rev_edge)
+    a = torch.arange(n, dtype=torch.int32, device=index.device)
+    b, flag = torch.empty_like(a), torch.zeros(1, dtype=torch.int32, device=index.device)
+    sweeps = 0
+    while True:
+        flag.zero_()
+        L.check(L.lib().mi_graph_components(L.ptr(index), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, L.ptr(a),
+                                            L.ptr(b), L.ptr(flag), L.stream()), "mi_graph_components(N=%d, k=%d)" % (n, k))
+        a, b = b, a
+        sweeps += 1
+        if int(flag.item()) == 0:
+            return a, sweeps
+
+
+def spectral_degree(index, wsym, eps, mutual, rev_ptr, rev_edge):
+    """(deg (N,), dis (N,)) float64: the sum of every vertex's incident weights and 1 / sqrt of it (0 for an isolated vertex)."""
+    n, k = _sp_graph(index, eps, mutual, rev_ptr, rev_edge, wsym)
+    deg = torch.empty(n, dtype=torch.float64, device=index.device)
+    dis = torch.empty_like(deg)
+    L.check(L.lib().mi_spectral_degree(L.ptr(index), L.ptr(wsym), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k,
+                                       L.ptr(deg), L.ptr(dis), L.stream()), "mi_spectral_degree(N=%d, k=%d)" % (n, k))
+    return deg, dis
+
+
+def spectral_spmv(index, wsym, eps, mutual, rev_ptr, rev_edge, dis, x, y=None, row0=0):
+    """y = A x, A = D^-1/2 W D^-1/2 restricted to the rows [row0, row0 + len(x)); x, y float64 vectors of that range."""
+    n, k = _sp_graph(index, eps, mutual, rev_ptr, rev_edge, wsym)
+    _ts_table(dis, "dis", (n,), torch.float64)
+    L.require_cuda(x, "x", torch.float64)
+    if x.dim() != 1 or not x.is_contiguous():
+        raise L.HipExtensionError("x must be a contiguous vector, got %s" % (tuple(x.shape),))
+    nrows = x.shape[0]
+    if y is None:
+        y = torch.empty_like(x)
+    _ts_table(y, "y", (nrows,), torch.float64)
+    if y.data_ptr() == x.data_ptr():
+        raise L.HipExtensionError("y may not alias x")
+    L.check(L.lib().mi_spectral_spmv(L.ptr(index), L.ptr(wsym), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k,
+                                     L.ptr(dis), L.ptr(x), L.ptr(y), int(row0), nrows, L.stream()),
+            "mi_spectral_spmv(N=%d, k=%d, rows %d..%d)" % (n, k, row0, row0 + nrows))
+    return y
+
+
+def _sp_basis(Q, w, c):
+    L.require_cuda(Q, "Q", torch.float64)
+    if Q.dim() != 2 or Q.stride(1) != 1 or Q.shape[0] < 1 or (Q.shape[0] > 1 and Q.stride(0) < Q.shape[1]):
+        raise L.HipExtensionError("Q must be (m, n) float64 with contiguous rows, got %s" % (tuple(Q.shape),))
+    m, n = Q.shape
+    _ts_table(w, "w", (n,), torch.float64)
+    if c is None:
+        c = torch.empty(m, dtype=torch.float64, device=Q.device)
+    _ts_table(c, "c", (m,), torch.float64)
+    return m, n, (Q.stride(0) if m > 1 else n), c
+
+
+def _sp_ws(m, n, device):
+    nbytes = L.lib().mi_spectral_workspace_bytes(m, n)
+    if nbytes == 0:
+        L.check(-3, "mi_spectral_workspace_bytes(m=%d, n=%d)" % (m, n))
+    return L.workspace(nbytes, device, "spectral")
+
+
+def spectral_dots(Q, w, c=None):
+    """c = Q^T w (m,) float64 for the m rows of Q (m, n); a fixed summation order (a norm: Q = w[None])."""
+    m, n, ldq, c = _sp_basis(Q, w, c)
+    ws = _sp_ws(m, n, Q.device)
+    L.check(L.lib().mi_spectral_dots(L.ptr(Q), ldq, m, n, L.ptr(w), L.ptr(c), L.ptr(ws), ws.numel(), L.stream()),
+            "mi_spectral_dots(m=%d, n=%d)" % (m, n))
+    return c
+
+
+def spectral_orth(Q, w, c=None):
+    """c = Q^T w, then w -= Q c in place (one Gram-Schmidt pass against the rows of Q; two passes are `twice is enough`)."""
+    m, n, ldq, c = _sp_basis(Q, w, c)
+    ws = _sp_ws(m, n, Q.device)
+    L.check(L.lib().mi_spectral_orth(L.ptr(Q), ldq, m, n, L.ptr(w), L.ptr(c), L.ptr(ws), ws.numel(), L.stream()),
+            "mi_spectral_orth(m=%d, n=%d)" % (m, n))
+    return c
+
+
+def spectral_combine(Q, c, w, beta=0.0):
+    """w = beta w - Q c in place (beta = 0: w is only written), the rows of Q taken in order."""
+    m, n, ldq, c = _sp_basis(Q, w, c)
+    L.check(L.lib().mi_spectral_combine(L.ptr(Q), ldq, m, n, L.ptr(c), L.ptr(w), float(beta), L.stream()),
+            "mi_spectral_combine(m=%d, n=%d)" % (m, n))
+    return w

@@ -3,7 +3,7 @@ plot_2d.py without its plots):
 
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
                                    [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode umap | --mode tsne]
-                                   [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy]
+                                   [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy] [--umap_init random | spectral]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -26,6 +26,10 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
                                           constants in an epoch-synchronous form, its init="random" from --map_seed): y, y01,
                                           n_epochs, n_neighbors, min_dist, a, b, seed.  One search with K neighbours serves the
                                           graph and, by its first K - 1 columns (UMAP counts the pick itself), the map.
+                                          --umap_init spectral starts the map as umap-learn does by default, from the eigenvectors
+                                          of the graph's normalised Laplacian (utils/spectral.py, csrc/spectral.hip), and adds
+                                          init (the start that was used: "random" where the eigen-solver did not converge),
+                                          n_graph_components and eigenvalues (those of the largest component) to the file.
     OUT/all_colors.npy                    with the map: (N, 3) uint8, the colour of every pick at its y01 place on a 2-D colour
                                           table, in pick order (utils/vis3d.py, csrc/vis3d.hip: the reference's
                                           BaseColorMap2D._sample - round half to even, clamp) - the input of visualize_3dhm.
@@ -38,7 +42,7 @@ Only an explicit `--mode umap` makes the UMAP map.  The reference's default mode
 the files it does not write; the parser therefore tells the given value from the default one (DefaultMode), and making the bare
 default draw the map is a one-line change in main.
 
-Not made here: UMAP's spectral start, the WebP plots and PNG thumbnails, and the label-supervised second map.
+Not made here: the WebP plots and PNG thumbnails, and the label-supervised second map.
 """
 import argparse
 import os
@@ -68,6 +72,8 @@ def add_arguments(parser):
     parser.add_argument("--colormap", default=None, help="(W, H, 3) uint8 .npy colour table for all_colors.npy; the default is a "
                         "built-in 256 x 256 table, not one of the reference's")
     parser.add_argument("--min_dist_umap", type=float, default=0.5, help="min_dist of the UMAP map (the reference: 0.5)")
+    parser.add_argument("--umap_init", choices=("random", "spectral"), default="random", help="start of the UMAP map: random, or "
+                        "spectral as umap-learn's default (embeddings_2d.npz then also holds init, n_graph_components, eigenvalues)")
     # accepted for the reference's command lines; they only steer its plots
     parser.add_argument("--min_dist_vis", type=float, default=None)
     parser.add_argument("--save_out_img", type=int, default=1)
@@ -127,17 +133,18 @@ def tsne_map(projs, perplexity, seed, device):
         return (index[:, :perplexity].cpu().numpy(), dist[:, :perplexity].cpu().numpy(), y, ts.kl_divergence_, ts.n_iter_)
 
 
-def umap_map(projs, n_neighbors, min_dist, seed, device):
+def umap_map(projs, n_neighbors, min_dist, seed, device, init="random"):
     """One search with n_neighbors other picks, then the map from its first n_neighbors - 1 columns: index, dist, y (N, 2)
-    fp32, n_epochs and the curve parameters a, b."""
+    fp32, n_epochs and the curve parameters a, b; with init="spectral" also (init used, graph components, eigenvalues)."""
     import torch
     from .utils.umap import UMAP
     with torch.cuda.device(device):
-        um = UMAP(n_neighbors, min_dist=min_dist, seed=seed, device=device)
+        um = UMAP(n_neighbors, min_dist=min_dist, seed=seed, device=device, init=init)
         x = torch.from_numpy(projs).to(device)
         index, dist = um.graph(x)
         y = um.fit_transform(x, graph=(index, dist))
-        return index.cpu().numpy(), dist.cpu().numpy(), y, um.n_epochs_, um.a_, um.b_
+        out = index.cpu().numpy(), dist.cpu().numpy(), y, um.n_epochs_, um.a_, um.b_
+        return out if init == "random" else out + ((um.init_, um.n_components_, um.eigenvalues_),)
 
 
 def map_colours(y01, table, device):
@@ -212,7 +219,15 @@ def main(args):
           % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
     if args.num_neighbor is not None:
         if with_umap:
-            index, dist, y, n_epochs, a, b = umap_map(projs, args.num_neighbor, args.min_dist_umap, args.map_seed, torch.device("cuda", gpu))
+            if args.umap_init == "spectral":
+                index, dist, y, n_epochs, a, b, (init_used, n_comp, eigenvalues) = umap_map(
+                    projs, args.num_neighbor, args.min_dist_umap, args.map_seed, torch.device("cuda", gpu), init="spectral")
+                start = dict(init=np.array(init_used), n_graph_components=np.int32(n_comp),
+                             eigenvalues=np.asarray([] if eigenvalues is None else eigenvalues, np.float64))
+            else:
+                index, dist, y, n_epochs, a, b = umap_map(projs, args.num_neighbor, args.min_dist_umap, args.map_seed,
+                                                          torch.device("cuda", gpu))
+                start = {}
         elif with_tsne:
             index, dist, y, kl, n_iter = tsne_map(projs, args.num_neighbor, args.map_seed, torch.device("cuda", gpu))
         else:
@@ -226,7 +241,9 @@ def main(args):
         if with_umap:
             np.savez(os.path.join(args.path, "embeddings_2d.npz"), y=y, y01=y01, n_epochs=np.int32(n_epochs),
                      n_neighbors=np.int32(args.num_neighbor), min_dist=np.float32(args.min_dist_umap), a=np.float64(a),
-                     b=np.float64(b), seed=np.int32(args.map_seed))
+                     b=np.float64(b), seed=np.int32(args.map_seed), **start)
+            if start:
+                print("[cet_pick_amd] plot_2d: UMAP start %s (--umap_init spectral), %d graph components" % (init_used, n_comp))
             print("[cet_pick_amd] plot_2d: UMAP map of %d picks, n_neighbors %d, min_dist %g, %d epochs -> %s"
                   % (len(y), args.num_neighbor, args.min_dist_umap, n_epochs, os.path.join(args.path, "embeddings_2d.npz")))
         else:

@@ -14,8 +14,11 @@ Departures from umap-learn:
      every force of an epoch is evaluated from the positions at its start, summed per vertex in a fixed order in double and
      applied once.  The map is then a pure function of (graph, seed): repeated runs give identical bytes, and every term can be
      checked against a float64 restatement.
-  2. The start is umap-learn's init="random" (numpy.random.RandomState(seed).uniform(-10, 10, (N, 2))); its default, the
-     spectral start, is not built.
+  2. The start is umap-learn's init="random" (numpy.random.RandomState(seed).uniform(-10, 10, (N, 2))) unless init="spectral" is
+     asked for: umap-learn's default, the eigenvectors 1 and 2 of the graph's normalised Laplacian (utils/spectral.py,
+     csrc/spectral.hip), scaled to 10 / max|Y|, plus normal(scale=1e-4) noise, every axis then brought to [0, 10].
+     Where the eigen-solver does not converge one log line is printed and the random start is used, as umap-learn warns and falls
+     back; init_ says which start was used, n_components_ and eigenvalues_ what the solver found.
   3. Exactly 5 negatives per sample (umap-learn's floating-point bookkeeping gives 5, now and then 4 or 6), drawn by
      Philox-4x32-10 from (vertex, incident slot, epoch, seed).
 2 <= n_neighbors <= 128, N >= n_neighbors + 1.  There is no CPU path.
@@ -29,6 +32,7 @@ from .tsne import reverse_graph
 
 N_NEIGHBORS_MIN, N_NEIGHBORS_MAX = 2, 128       # K - 1 <= 127 columns, and the neighbour search's k <= 128
 EPOCHS_SMALL, EPOCHS_LARGE, SMALL_N = 500, 200, 10000
+INITS = ("random", "spectral")
 
 
 def check_range(n, n_neighbors):
@@ -55,8 +59,12 @@ def find_ab_params(min_dist, spread=1.0):
 
 
 class UMAP:
-    def __init__(self, n_neighbors, min_dist=0.5, seed=42, n_epochs=None, device="cuda"):
+    def __init__(self, n_neighbors, min_dist=0.5, seed=42, n_epochs=None, device="cuda", init="random", spectral_options=None):
+        if init not in INITS:
+            raise ValueError("init must be one of %s, got %r" % (", ".join(INITS), init))
         self.n_neighbors, self.min_dist, self.seed = n_neighbors, float(min_dist), int(seed)
+        self.init, self.spectral_options = init, dict(spectral_options or {})      # tol, max_basis, max_restarts of the solver
+        self.init_, self.n_components_, self.eigenvalues_ = None, None, None
         self.n_epochs = None if n_epochs is None else int(n_epochs)
         self.device = torch.device(device)
         self.embedding_, self.n_epochs_, self.a_, self.b_ = None, None, None, None
@@ -83,28 +91,49 @@ class UMAP:
                 if isinstance(x, np.ndarray):
                     x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(n, -1)).to(self.device)
                 graph = self.graph(L.require_cuda(x, "x").contiguous())
+            elif self.init == "spectral" and isinstance(x, np.ndarray):     # the centres of many components need the data
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(n, -1)).to(self.device)
             index, dist = graph
             k = int(self.n_neighbors) - 1
             if index.shape[0] != n or index.shape[1] not in (k, k + 1) or tuple(dist.shape) != tuple(index.shape):
                 raise ValueError("graph must have N = %d rows and %d or %d columns, got %s" % (n, k, k + 1, tuple(index.shape)))
-            return self._fit(index[:, :k].contiguous(), dist[:, :k].contiguous(), a, b)
+            return self._fit(index[:, :k].contiguous(), dist[:, :k].contiguous(), a, b, x)
 
-    def setup(self, index, dist, n_epochs):
-        """(rev_ptr, rev_edge, mutual, eps) of the graph's K - 1 columns: what the epochs read."""
+    def setup(self, index, dist, n_epochs, with_wsym=False):
+        """(rev_ptr, rev_edge, mutual, eps) of the graph's K - 1 columns: what the epochs read; with_wsym: and the weights."""
         n, k = index.shape
         mean_all = float(torch.sqrt(dist).sum(dtype=torch.float64).item()) / (n * (k + 1))
         w = H.umap_smooth_knn(dist, mean_all)[2]
         rev_ptr, rev_edge = reverse_graph(index)
         out = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs)
         wmax = out[0].max().reshape(1)                      # stays on the device
-        _, mutual, eps = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=wmax, out=out)
-        return rev_ptr, rev_edge, mutual, eps
+        wsym, mutual, eps = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=wmax, out=out)
+        return (rev_ptr, rev_edge, mutual, eps) + ((wsym,) if with_wsym else ())
 
-    def _fit(self, index, dist, a, b):
+    def spectral_start(self, index, wsym, eps, mutual, rev_ptr, rev_edge, x=None):
+        """umap-learn's start from the spectral layout, (N, 2) fp32 numpy, or None (and one log line) where the eigen-solver did
+        not converge.  Sets n_components_ and eigenvalues_."""
+        from .spectral import spectral_layout, umap_start
+        Y, info = spectral_layout(index, wsym, eps, mutual, rev_ptr, rev_edge, dim=2, seed=self.seed, x=x, **self.spectral_options)
+        self.n_components_, self.eigenvalues_ = info["n_components"], info["eigenvalues"]
+        if not info["converged"]:
+            print("[cet_pick_amd] UMAP: the spectral start did not converge (%d graph components, %d Lanczos steps, %d restarts); "
+                  "using the random start" % (info["n_components"], info["steps"], info["restarts"]))
+            return None
+        return umap_start(Y.cpu().numpy(), self.seed)
+
+    def _fit(self, index, dist, a, b, x=None):
         n = index.shape[0]
         n_epochs = self.n_epochs or (EPOCHS_SMALL if n <= SMALL_N else EPOCHS_LARGE)
-        rev_ptr, rev_edge, mutual, eps = self.setup(index, dist, n_epochs)
-        y0 = np.random.RandomState(self.seed % 2 ** 32).uniform(-10, 10, (n, 2)).astype(np.float32)
+        y0 = None
+        if self.init == "spectral":
+            rev_ptr, rev_edge, mutual, eps, wsym = self.setup(index, dist, n_epochs, with_wsym=True)
+            y0 = self.spectral_start(index, wsym, eps, mutual, rev_ptr, rev_edge, x if isinstance(x, torch.Tensor) else None)
+        else:
+            rev_ptr, rev_edge, mutual, eps = self.setup(index, dist, n_epochs)
+        self.init_ = "random" if y0 is None else "spectral"
+        if y0 is None:
+            y0 = np.random.RandomState(self.seed % 2 ** 32).uniform(-10, 10, (n, 2)).astype(np.float32)
         y, y2 = torch.from_numpy(y0).to(index.device), torch.empty(n, 2, dtype=torch.float32, device=index.device)
         for epoch in range(1, n_epochs + 1):
             H.umap_epoch(y, y2, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epochs, a, b, self.seed)

@@ -853,6 +853,37 @@ int mi_umap_epoch(const float* y_in, float* y_out, const int32_t* index, const i
                   const uint8_t* mutual, const double* eps, long n, int k, int epoch, int n_epochs, double a, double b, uint64_t seed,
                   mi_stream_t stream);
 
+/* The spectral start of the UMAP map (umap.UMAP's init="spectral"), DESIGN.md 4.15: the kernels of an eigen-solver over the graph
+ * mi_umap_epoch walks.  n, k, index, rev_ptr, rev_edge, mutual, eps as there (mi_umap_check's range; MI_E_UNSUPPORTED outside, nothing
+ * launched); wsym as mi_umap_union writes it.  The incident list of vertex i: its forward edges with finite eps, then the edges that
+ * end in it with mutual = 0 and finite eps; the weight of an entry is wsym of that directed edge.  Edge ids and destinations
+ * outside their range, and edges from a vertex to itself, are passed over.  All sums in double in a fixed order, no
+ * floating-point atomics: the same inputs give the same bytes.
+ *   mi_graph_components  one sweep of min-label propagation with pointer jumping: label_out_i = the smallest label_in among i and
+ *                        its incident vertices, followed through label_in down to a vertex that is its own label; *changed (one
+ *                        device int, zeroed by the caller) is set to 1 when a label moved.  Start from label_i = i and repeat, the
+ *                        two buffers swapped, until *changed stays 0: every vertex then holds the smallest id of its component.
+ *                        label_out may not alias label_in.
+ *   mi_spectral_degree   out_deg_i = the sum of the incident weights, out_dis_i = 1 / sqrt(deg_i) (0 where deg_i = 0), n doubles.
+ *   mi_spectral_spmv     y = A x over the rows [row0, row0 + nrows), A = D^-1/2 W D^-1/2 restricted to that range (entries that
+ *                        leave it are passed over): x and y hold nrows doubles, element 0 is row row0; y may not alias x.
+ *   mi_spectral_dots     c_v = sum_i Q[v ldq + i] w_i for v < m: 1 <= m <= 4096 vectors of 1 <= n < 2^31 doubles, ldq >= n.  Partial
+ *                        sums of 2048 elements, added in order; ws: mi_spectral_workspace_bytes(m, n) (0 = unsupported sizes).
+ *   mi_spectral_orth     c = Q^T w as mi_spectral_dots, then w = w - Q c with the vectors taken in order.  w outside Q.
+ *   mi_spectral_combine  w = beta w - Q c (beta = 0: w is not read).  w outside Q. */
+int mi_graph_components(const int32_t* index, const double* eps, const uint8_t* mutual, const int32_t* rev_ptr, const int32_t* rev_edge,
+                        long n, int k, const int32_t* label_in, int32_t* label_out, int32_t* changed, mi_stream_t stream);
+int mi_spectral_degree(const int32_t* index, const float* wsym, const double* eps, const uint8_t* mutual, const int32_t* rev_ptr,
+                       const int32_t* rev_edge, long n, int k, double* out_deg, double* out_dis, mi_stream_t stream);
+int mi_spectral_spmv(const int32_t* index, const float* wsym, const double* eps, const uint8_t* mutual, const int32_t* rev_ptr,
+                     const int32_t* rev_edge, long n, int k, const double* dis, const double* x, double* y, long row0, long nrows,
+                     mi_stream_t stream);
+size_t mi_spectral_workspace_bytes(int m, long n);
+int mi_spectral_dots(const double* Q, long ldq, int m, long n, const double* w, double* c, void* ws, size_t ws_bytes,
+                     mi_stream_t stream);
+int mi_spectral_orth(const double* Q, long ldq, int m, long n, double* w, double* c, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_spectral_combine(const double* Q, long ldq, int m, long n, const double* c, double* w, double beta, mi_stream_t stream);
+
 /* 3-D visualisation of the exploration map (reference visualize_3dhm.py, and the colour step of plot_2d.py), DESIGN.md 4.13.
  * Volumes are (Z, R, C) row-major and addressed with 64-bit offsets; Z R C / 256 < 2^31 (MI_E_UNSUPPORTED above).
  *   mi_vis_sample_colours  y01 (n, 2) fp32, table (W, H, 3) uint8: out (n, 3) = table[ix, iy] with ix = clamp(rint(x (W - 1)), 0,
