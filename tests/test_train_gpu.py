@@ -724,8 +724,9 @@ def test_fused_bn_relu_maxpool_matches_unfused(shape, train):
 @pytest.mark.parametrize("n,size", [(3, 32), (2, 48), (64, 32)])
 def test_stem_epilogue_statistics_match_statistics_pass(n, size):
     """mi_conv3d_stem_stats_f32: the output equals the plain stem convolution's bit for bit and the BatchNorm sums from
-    its epilogue equal float64 column sums of that output (to float32 rounding of the 16-voxel partial sums); the encoder's
-    trunk produces the same activations with and without them (MI_STEM_NO_STATS=1)."""
+    its epilogue equal float64 column sums of that output (to float32 rounding of the 16-voxel partial sums).  (The trunk's stem
+    block with and without them, MI_STEM_NO_STATS=1: test_stem_gpu.py::test_stem_block_with_and_without_epilogue_statistics;
+    the 8 x 4 x 4 tiling and non-cubic / odd shapes: test_stem_gpu.py::test_stem_statistics_epilogue.)"""
     import ctypes
     import numpy as np
     from cet_pick_amd import hipops as H, _lib as L
