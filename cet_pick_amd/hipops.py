@@ -9,7 +9,9 @@ the model was flattened by :class:`ParamArena`): a parameter whose ``.grad`` is 
 gradient assigned, otherwise it is accumulated - the same contract as torch's AccumulateGrad.
 PyTorch is the allocator / stream owner; all arithmetic happens in the HIP kernels.
 """
+import collections
 import ctypes
+import math
 import os
 import torch
 import torch.nn as nn
@@ -281,6 +283,10 @@ def _as5d(x):
     return x if x.dim() == 5 else x.unsqueeze(1)
 
 
+def _out_extent(extent, k3, stride, p3, d3):
+    return tuple((v + 2 * p - dl * (k - 1) - 1) // stride + 1 for v, k, p, dl in zip(extent, k3, p3, d3))
+
+
 class _Geom:
     """One convolution problem - (N, D, H, W, Ci) -> co channels, window k3, stride, padding p3, dilation d3 (None: none) - as the
     C-ABI takes it: the mi_conv_geom struct built once (`ref` is what the mi_conv_* entries get), the output extent, the tap count of
@@ -292,7 +298,7 @@ class _Geom:
         self.key = tuple(int(v) for v in shape5) + (int(co),) + tuple(k3) + (int(stride),) + tuple(p3) + d3
         self.c = L.ConvGeom(*self.key)
         self.ref = ctypes.byref(self.c)
-        self.out = tuple((v + 2 * p - dl * (k - 1) - 1) // stride + 1 for v, k, p, dl in zip(shape5[1:4], k3, p3, d3))
+        self.out = _out_extent(shape5[1:4], k3, stride, p3, d3)
         self.taps = k3[0] * k3[1] * k3[2]
 
     def workspace(self, device):
@@ -304,90 +310,67 @@ def _linear_geom(m, ci, co):
     return _Geom((m, 1, 1, 1, ci), co, (1, 1, 1), 1, (0, 0, 0))
 
 
-# Pre-cut weight images of the conv_direct3.hip / conv_s2.hip / conv_p2d.hip convolutions.  Outside a step engine an image is cut in
+# Pre-cut weight images of the conv_s2.hip / conv_direct3.hip / conv_p2d.hip convolutions.  Outside a step engine an image is cut in
 # front of its convolution (by the C side, or on the parameter: _kept_image); a step engine (trains/step_graph.py) knows when its weights
 # change, keeps them here and re-cuts a whole group in ONE launch per family.  The cache is only consulted while ACTIVE_IMAGES is set
 # (the engine sets it around its step), so a stale image can never reach a convolution issued from anywhere else.
 ACTIVE_IMAGES = None
 
+_ImageFamily = collections.namedtuple("_ImageFamily", ("nbytes", "prep"))      # image size (lib, weight, dgrad flag), prep entry
+# (in the order a refresh cuts them)
+_IMAGE_FAMILIES = {
+    # the stride-2 block fronts: image of (conv1.weight, downsample weight), forward or data gradient
+    "s2": _ImageFamily(lambda lib, w, dgrad: (lib.mi_conv3d_s2_dgrad_workspace_bytes if dgrad else lib.mi_conv3d_s2_fwd_workspace_bytes)(
+        int(w.shape[1]), int(w.shape[0])), "mi_conv3d_s2_prep"),
+    # the 3-D 3^3 / stride-1 C -> C layers
+    "direct": _ImageFamily(lambda lib, w, dgrad: lib.mi_conv3d_direct_wimg_bytes(int(w.shape[0])), "mi_conv3d_direct_prep"),
+    # the 2-D 3 x 3 / stride-1 C -> C layers
+    "p2d": _ImageFamily(lambda lib, w, dgrad: lib.mi_conv2d_p2d_wimg_bytes(int(w.shape[0])), "mi_conv2d_p2d_prep"),
+}
 
-def _prep_images(fn, items):
-    """items: [(weight, None, dgrad flag, image tensor)] - all cut by `fn` (mi_conv3d_direct_prep / mi_conv2d_p2d_prep: one launch per 16)
-    on the current stream."""
+
+def _prep_images(family, items):
+    """items: [(weight, shortcut weight of an "s2" front or None, dgrad flag, image tensor)] - all cut by the family's prep entry (one
+    launch for the s2 fronts, one per 16 images otherwise) on the current stream."""
     if not items:
         return
-    L.check(getattr(L.lib(), fn)(L.host_array([it[0].data_ptr() for it in items]), L.host_array([it[3].data_ptr() for it in items]),
-                                 L.host_array([it[2] for it in items], ctypes.c_int),
-                                 L.host_array([int(it[0].shape[0]) for it in items], ctypes.c_int), len(items), L.stream()), fn)
+    fn = _IMAGE_FAMILIES[family].prep
+    ints = lambda vals: L.host_array(vals, ctypes.c_int)
+    w, img = L.host_array([it[0].data_ptr() for it in items]), L.host_array([it[3].data_ptr() for it in items])
+    dgrad, co = ints([it[2] for it in items]), ints([int(it[0].shape[0]) for it in items])
+    if family == "s2":               # two more operand arrays: the shortcut weights and the input channels
+        args = (w, L.host_array([(it[1].data_ptr() if it[1] is not None else None) for it in items]), img,
+                ints([int(it[0].shape[1]) for it in items]), co, dgrad)
+    else:
+        args = (w, img, dgrad, co)
+    L.check(getattr(L.lib(), fn)(*args, len(items), L.stream()), fn)
 
 
 class WeightImages:
     def __init__(self):
         self._groups = {}            # group -> {family: [(weight, shortcut weight of an "s2" front or None, dgrad flag, image)]}
-        self._by_weight = {}         # (weight storage address, dgrad [+ 2: stride-2 front, + 4: p2d]) -> image tensor
-
-    def _family(self, group, fam):
-        return self._groups.setdefault(group, {"s2": [], "direct": [], "p2d": []})[fam]
+        self._by_weight = {}         # (family, weight storage address, dgrad flag) -> image tensor
 
     @staticmethod
     def eligible(w, k, stride, pad):
         return (w.is_cuda and tuple(w.shape[:2]) in ((64, 64), (128, 128)) and _k3(k, True) == (3, 3, 3) and stride == 1
                 and _p3(pad, True) == (1, 1, 1) and _phys_ok(w))
 
-    def add(self, group, w, dgrad):
-        nb = L.lib().mi_conv3d_direct_wimg_bytes(int(w.shape[0]))
-        img = torch.empty(nb, dtype=torch.uint8, device=w.device)
-        self._family(group, "direct").append((w, None, int(bool(dgrad)), img))
-        self._by_weight[(w.data_ptr(), int(bool(dgrad)))] = img
+    def add(self, group, family, w, dgrad, w_ds=None):
+        """Keep the `family` image of `w` (with the shortcut weight `w_ds` of an "s2" front) for the forward or data-gradient pass."""
+        dgrad = int(bool(dgrad))
+        img = torch.empty(int(_IMAGE_FAMILIES[family].nbytes(L.lib(), w, dgrad)), dtype=torch.uint8, device=w.device)
+        self._groups.setdefault(group, {f: [] for f in _IMAGE_FAMILIES})[family].append((w, w_ds, dgrad, img))
+        self._by_weight[(family, w.data_ptr(), dgrad)] = img
 
-    def get(self, w, dgrad, n, d, h, wd):
-        img = self._by_weight.get((w.data_ptr(), int(bool(dgrad))))
-        c = int(w.shape[0])
-        if img is None or not L.lib().mi_conv3d_direct_usable(n, d, h, wd, c, c, 3, 1, 1):
-            return None
-        return img
-
-    # ---- the stride-2 block fronts (csrc/conv_s2.hip): image of (conv1.weight, downsample weight), forward or data gradient ----
-    def add_s2(self, group, w, w_ds, dgrad):
-        lib = L.lib()
-        co, ci = int(w.shape[0]), int(w.shape[1])
-        nb = lib.mi_conv3d_s2_dgrad_workspace_bytes(ci, co) if dgrad else lib.mi_conv3d_s2_fwd_workspace_bytes(ci, co)
-        img = torch.empty(int(nb), dtype=torch.uint8, device=w.device)
-        self._family(group, "s2").append((w, w_ds, int(bool(dgrad)), img))
-        self._by_weight[(w.data_ptr(), 2 + int(bool(dgrad)))] = img
-
-    def get_s2(self, w, dgrad):
-        return self._by_weight.get((w.data_ptr(), 2 + int(bool(dgrad))))
-
-    # ---- the 2-D 3 x 3 / stride-1 C -> C layers (csrc/conv_p2d.hip): forward or data-gradient image ----
-    def add_p2d(self, group, w, dgrad):
-        img = torch.empty(int(L.lib().mi_conv2d_p2d_wimg_bytes(int(w.shape[0]))), dtype=torch.uint8, device=w.device)
-        self._family(group, "p2d").append((w, None, int(bool(dgrad)), img))
-        self._by_weight[(w.data_ptr(), 4 + int(bool(dgrad)))] = img
-
-    def get_p2d(self, w, dgrad):
-        return self._by_weight.get((w.data_ptr(), 4 + int(bool(dgrad))))
-
-    @staticmethod
-    def _refresh_s2(items):
-        if not items:
-            return
-        arr = L.host_array
-        L.check(L.lib().mi_conv3d_s2_prep(arr([it[0].data_ptr() for it in items]),
-                                          arr([(it[1].data_ptr() if it[1] is not None else None) for it in items]),
-                                          arr([it[3].data_ptr() for it in items]), arr([int(it[0].shape[1]) for it in items], ctypes.c_int),
-                                          arr([int(it[0].shape[0]) for it in items], ctypes.c_int),
-                                          arr([it[2] for it in items], ctypes.c_int), len(items), L.stream()), "mi_conv3d_s2_prep")
+    def get(self, family, w, dgrad):
+        return self._by_weight.get((family, w.data_ptr(), int(bool(dgrad))))
 
     def refresh(self, group):
         """Re-cut every image of `group` from the current weights on the current stream: one launch for the group's stride-2
         fronts, one (per 16 images) for its direct-kernel images, one for its p2d images."""
-        g = self._groups.get(group)
-        if g is None:
-            return
-        self._refresh_s2(g["s2"])
-        _prep_images("mi_conv3d_direct_prep", g["direct"])
-        _prep_images("mi_conv2d_p2d_prep", g["p2d"])
+        for family, items in self._groups.get(group, {}).items():
+            _prep_images(family, items)
 
     def refresh_all(self):
         for group in self._groups:              # (in registration order)
@@ -400,18 +383,25 @@ class WeightImages:
                    for g in self._groups.values() for items in g.values() for it in items)
 
 
+def _held_image(w, dgrad):
+    """(family, image) of the image the active step engine keeps of `w` for this pass; (None, None) without one."""
+    if ACTIVE_IMAGES is not None:
+        for family in _IMAGE_FAMILIES:
+            img = ACTIVE_IMAGES.get(family, w, dgrad)
+            if img is not None:
+                return family, img
+    return None, None
+
+
+def _switch(name):
+    """An environment switch of the routing, read per call (tests and A/B runs flip them between calls).  MI_CONV_ARITH (conv_igemm.hip
+    conv_arith_bf16x3) is on when it selects the f32 MFMA path: anything starting with 'f'; the others when set to anything."""
+    value = os.environ.get(name, "")
+    return value.startswith("f") if name == "MI_CONV_ARITH" else bool(value)
+
+
 def _arith_bf16x3():
-    """MI_CONV_ARITH (conv_igemm.hip conv_arith_bf16x3): anything starting with 'f' selects the f32 MFMA path."""
-    import os
-    return not os.environ.get("MI_CONV_ARITH", "").startswith("f")
-
-
-def _cached_image(w, dgrad, n, d, h, wd, k3, stride, p3):
-    if ACTIVE_IMAGES is None or PROFILE is not None or k3 != (3, 3, 3) or stride != 1 or p3 != (1, 1, 1):
-        return None
-    if not _arith_bf16x3():          # the direct kernels are bf16x3 only: an f32 A/B run keeps every conv on the f32 MFMA
-        return None
-    return ACTIVE_IMAGES.get(w, dgrad, n, d, h, wd)
+    return not _switch("MI_CONV_ARITH")
 
 
 SMALLK = os.environ.get("CETPICK_SMALLK", "1") != "0"
@@ -446,25 +436,6 @@ def inference_mode():
     return not torch.is_grad_enabled()
 
 
-def _smallk_taps(x, w, k3, stride, p3, dil, nd5, inference):
-    """1 / 3: this forward convolution can take the short-reduction inference kernel (conv_smallk.hip) as a 1 x 1 / (3, 1, 1)
-    convolution; 0: not.  `inference`: the caller's word that no gradient will be asked of this call (inference_mode())."""
-    if not SMALLK or not inference or not x.is_cuda or stride != 1:
-        return 0
-    if dil is not None and tuple(_k3(dil, nd5)) != (1, 1, 1):
-        return 0
-    ci, co = x.shape[-1], w.shape[0]
-    # at most 64 output channels: every wave streams the whole weight image of its columns, which beyond that outweighs the
-    # activations it reads (measured: the transposed convolutions' products to 128 - 512 columns are 20 % slower than on the implicit GEMM)
-    if ci % 16 or co % 32 or co > 64 or x.numel() * 4 >= 0x7fff0000:
-        return 0
-    if tuple(k3) == (1, 1, 1) and tuple(p3) == (0, 0, 0):
-        return 1
-    if nd5 and tuple(k3) == (3, 1, 1) and tuple(p3) == (1, 0, 0) and 3 * ci <= 512:
-        return 3
-    return 0
-
-
 def _smallk_image(w, owner, K, co):
     """The weight image of conv_smallk.hip for the kernel-layout weights `w` (a (K, co) matrix in memory), kept on `owner` (the
     parameter or folded-weight tensor that outlives the call) and rebuilt when the storage or its version changes."""
@@ -476,26 +447,36 @@ def _smallk_image(w, owner, K, co):
     return _kept_image(owner if owner is not None else w, "_mi_smallk", w, (K, co), cut)
 
 
-def _d32_kind(x5shape, ci, co, k3, stride, p3, d3, inference):
-    """0, or the kind (1: 3 x 3 per plane to 32 channels, 2: the dilated 3-D head, 3: 3 x 3 per plane to 64 channels) of conv_d32.hip's
-    direct inference kernel for this forward convolution (padding = dilation * (k - 1) / 2)."""
-    if not inference or stride != 1 or not (co == 32 or (co % 64 == 0 and 64 <= co <= 512)) or not _arith_bf16x3():
-        return 0
-    d3 = tuple(d3) if d3 is not None else (1, 1, 1)
-    if tuple(p3) != tuple(dl * (kk - 1) // 2 for dl, kk in zip(d3, k3)):
-        return 0
-    n, d, h, wd, _ = x5shape
-    return int(L.lib().mi_conv_d32_kind(n, d, h, wd, ci, co, *k3, *d3))
-
-
 POOL_FUSED = os.environ.get("CETPICK_POOL_FUSED", "1") != "0"
 
 
-def _d32_call(x, w, bias, relu, kind, owner=None, out=None, pool=False):
-    """y = act(conv(x, w) + bias) on conv_d32.hip; the pre-cut weight image is kept on `owner` (rebuilt when the weights change)."""
-    _f32c(x, "x")
+def _kernel_layout(w):
     if not _phys_ok(w):
         raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
+
+
+def _out_tensor(out, shape, x, sliced=False, who=""):
+    """(out, channel stride): `out` checked - or made, when None - as the fp32 result of `shape` on x's device.  Dense, or (sliced) a channel
+    slice of a wider contiguous tensor: the concatenation buffer of the up-convolution block that will consume it."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device), shape[-1]
+    ok = tuple(out.shape) == shape and out.dtype == torch.float32 and out.device == x.device
+    if not sliced:
+        if not (ok and out.is_contiguous()):
+            raise L.HipExtensionError(who + "`out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
+        return out, shape[-1]
+    cstride, want = int(out.stride(-2)), [1]
+    for v in reversed(shape[1:-1]):
+        want.insert(0, want[0] * v)
+    if (not ok or tuple(out.stride()) != tuple(cstride * v for v in want) + (1,) or cstride < shape[-1] or cstride % 4
+            or out.data_ptr() % 16):
+        raise L.HipExtensionError("`out` must be an fp32 %s tensor or a channel slice of a wider contiguous one" % (shape,))
+    return out, cstride
+
+
+def _d32_launch(route, x, w, bias, relu, owner=None, out=None, pool=False):
+    """y = act(conv(x, w) + bias) on conv_d32.hip; the pre-cut weight image is kept on `owner` (rebuilt when the weights change)."""
+    kind = route.param
     lib = L.lib()
     x5 = _as5d(x)
     n, d, h, wd, ci = x5.shape
@@ -510,37 +491,17 @@ def _d32_call(x, w, bias, relu, kind, owner=None, out=None, pool=False):
             L.check(lib.mi_conv_d32_prep(L.ptr(w), L.ptr(img), ci, ntap, L.stream()), "mi_conv_d32_prep")
         return img
     wimg = _kept_image(owner if owner is not None else w, "_mi_d32", w, (ci, ntap, co), cut)
-    shape = tuple(x.shape[:-1]) + (co,)
+    out, cstride = _out_tensor(out, tuple(x.shape[:-1]) + (co,), x, sliced=pool)
     if pool:                                          # kinds 1 / 3: the 2 x 2 max-pool of the result as a second output
-        cstride = co
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        else:
-            # a channel slice of a wider contiguous tensor (the concatenation buffer of the up-convolution block that will consume it)
-            cstride = int(out.stride(-2))
-            want = tuple(cstride * v for v in ([shape[-3] * shape[-2], shape[-2], 1] if len(shape) == 4 else
-                                               [shape[-4] * shape[-3] * shape[-2], shape[-3] * shape[-2], shape[-2], 1])) + (1,)
-            if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device or tuple(out.stride()) != want
-                    or cstride < co or cstride % 4 or out.data_ptr() % 16):
-                raise L.HipExtensionError("`out` must be an fp32 %s tensor or a channel slice of a wider contiguous one" % (shape,))
         pooled = torch.empty(tuple(x.shape[:-3]) + (h // 2, wd // 2, co), dtype=torch.float32, device=x.device)
         L.check(lib.mi_conv_d32_fwd_pool_strided_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), cstride, L.ptr(pooled),
                                                      int(relu), n, d, h, wd, ci, co, L.stream()), "mi_conv_d32_fwd_pool_strided_f32")
         return out, pooled
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise L.HipExtensionError("`out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
-
+    # kind 4: 1 x 1, tile-resident; 3: 3 x 3 per plane to 64-column blocks; 1 / 2: to 32 channels (2: the dilated 3-D head)
+    fn = {4: "mi_conv_d32_1x1_fwd_f32", 3: "mi_conv_d64_fwd_f32"}.get(kind, "mi_conv_d32_fwd_f32")
     def call():
-        if kind == 4:
-            return L.check(lib.mi_conv_d32_1x1_fwd_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, co,
-                                                       L.stream()), "mi_conv_d32_1x1_fwd_f32")
-        if kind == 3:
-            return L.check(lib.mi_conv_d64_fwd_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, co,
-                                                   L.stream()), "mi_conv_d64_fwd_f32")
-        return L.check(lib.mi_conv_d32_fwd_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci, kind,
-                                               L.stream()), "mi_conv_d32_fwd_f32")
+        return L.check(getattr(lib, fn)(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci,
+                                        co if kind in (3, 4) else kind, L.stream()), fn)
     _prof_run("fwd", 2.0 * n * d * h * wd * co * ci * ntap, call)
     return out
 
@@ -571,17 +532,12 @@ def detector_heads_fused(v, proj, hm):
     return y, yh
 
 
-def _smallk_call(x, w, bias, relu, ntaps, out=None, owner=None):
-    _f32c(x, "x")
-    if not _phys_ok(w):
-        raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
+def _smallk_launch(route, x, w, bias, relu, owner=None, out=None):
+    """The short-reduction inference kernel (conv_smallk.hip): a 1 x 1 / (3, 1, 1) convolution as route.param taps, no tile pipeline."""
+    ntaps = route.param
     ci, co = x.shape[-1], w.shape[0]
     m = x.numel() // ci
-    shape = tuple(x.shape[:-1]) + (co,)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise L.HipExtensionError("`out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
+    out, _ = _out_tensor(out, tuple(x.shape[:-1]) + (co,), x)
     img = _smallk_image(w, owner, ntaps * ci, co)
     plane, d = (x.shape[2] * x.shape[3], x.shape[1]) if ntaps == 3 else (1, 1)
     lib = L.lib()
@@ -603,31 +559,119 @@ def p2d_usable(x_shape, ci, co, k3, stride, p3, dil=None):
     return bool(L.lib().mi_conv2d_p2d_usable(int(n), int(h), int(w), int(ci)))
 
 
-def _stem3_ok(co):
-    """Conv2d(1, co, 3, padding=1) on its own kernels (conv_p2d.hip stem3_*): co a multiple of 4 that divides the block evenly."""
-    return 4 <= co <= 64 and co % 4 == 0 and 256 % (co // 4) == 0 and not os.environ.get("MI_NO_P2D")
+# Which kernel family a convolution takes: the family from a closed set and the family's parameter - the conv_d32.hip kind (1: 3 x 3 per
+# plane to 32 channels, 2: the dilated 3-D head, 3: 3 x 3 per plane to 64-column blocks, 4: 1 x 1), the conv_smallk.hip taps (1 / 3),
+# 1 where a "p2d" / "s2" launch reads the image the step engine keeps (0: it cuts its own), 1 where a "generic" weight gradient leaves
+# its split-K slabs with the parameter (the deferred form: _WgradJob).  family None: declined - the caller has another way.
+Route = collections.namedtuple("Route", ("family", "param"))
+ROUTE_FAMILIES = ("d32", "smallk", "stem3", "stem2d", "p2d", "direct", "cube2", "s2", "generic", None)
 
 
-def _p2d_image(w, dgrad):
+def conv_route(pass_, shape, ci, co, k3, stride, p3, d3=None, *, inference=False, has_res=False, has_bias=False, relu=False, pool=False,
+               image=None, profile=False, shortcut=False, phys_ok=True, accumulates=False, deferred=False, side=False):
+    """The Route of one convolution call, from integers and flags alone (the library's *_usable / *_kind predicates need no device): every
+    eligibility rule of conv_fwd, conv_bias_fwd, conv_dgrad, conv_wgrad_into and the stride-2 block fronts, each once, in their order
+    of precedence.
+    pass_: "fwd" / "dgrad" / "wgrad"; shape: the activation on the convolution's input side, (N, D, H, W, Ci) or (N, H, W, Ci); d3: the
+    dilation, None when the caller gave none.  inference: the caller's word that no gradient will be asked (inference_mode()); has_res /
+    has_bias / relu: the epilogue; pool: the 2 x 2 max-pool as a second output is asked for (declined unless conv_d32.hip makes it);
+    image: the family of the image ACTIVE_IMAGES holds for this weight and pass (_held_image); profile: bench.py's roofline pass is
+    on; shortcut: a block's stride-2 front with its 1 x 1 shortcut in one launch is asked for (declined unless conv_s2.hip takes it);
+    phys_ok: the weights are in kernel layout (where the caller does not insist on it); accumulates / deferred / side (weight gradient): the
+    gradient is added to an existing one, DEFERRED_WGRADS / SIDE_WGRADS are collecting."""
+    lib = L.lib()
+    nd5 = len(shape) == 5
+    n, d, h, wd = (shape[0], shape[1], shape[2], shape[3]) if nd5 else (shape[0], 1, shape[1], shape[2])
+    k3, p3 = tuple(k3), tuple(p3)
+    dd = tuple(d3) if d3 is not None else (1, 1, 1)
+    bf16x3 = _arith_bf16x3()
+    if shortcut:
+        # a BasicBlock's stride-2 front, cubic, one of the encoder's two shapes (csrc/conv_s2.hip)
+        usable = lib.mi_conv3d_s2_fwd_usable if pass_ == "fwd" else lib.mi_conv3d_s2_dgrad_usable
+        if nd5 and d == h == wd and phys_ok and usable(n, d, ci, co):
+            return Route("s2", int(image == "s2" and not profile))
+        return Route(None, 0)
+    if pass_ == "fwd" and inference and not has_res and stride == 1:
+        kind = 0                                      # conv_d32.hip's direct inference kernels: padding = dilation * (k - 1) / 2
+        if ((co == 32 or (co % 64 == 0 and 64 <= co <= 512)) and bf16x3
+                and p3 == tuple(dl * (k - 1) // 2 for dl, k in zip(dd, k3))):
+            kind = int(lib.mi_conv_d32_kind(n, d, h, wd, ci, co, *k3, *dd))
+        if pool:
+            # (y, maxpool2x2(y)) in one launch where the patch-resident 2-D kernel runs and nothing else asks for the result elsewhere
+            return Route("d32", kind) if (kind in (1, 3) and POOL_FUSED and not profile and not nd5) else Route(None, 0)
+        if kind == 4:                                 # 1 x 1 (the transposed convolutions' products): the tile-resident kernel
+            return Route("d32", 4)
+        # short reduction: no tile pipeline (conv_smallk.hip).  At most 64 output channels: every wave streams the whole weight image of its
+        # columns, which beyond that outweighs the activations it reads (measured: the transposed convolutions' products to 128 - 512
+        # columns are 20 % slower than on the implicit GEMM)
+        if (SMALLK and dd == (1, 1, 1) and not (ci % 16 or co % 32 or co > 64 or n * d * h * wd * ci * 4 >= 0x7fff0000)):
+            if k3 == (1, 1, 1) and p3 == (0, 0, 0):
+                return Route("smallk", 1)
+            if nd5 and k3 == (3, 1, 1) and p3 == (1, 0, 0) and 3 * ci <= 512:
+                return Route("smallk", 3)
+        if kind:                                      # 3 x 3: the patch-resident direct kernel
+            return Route("d32", kind)
+    if pool:
+        return Route(None, 0)
+    if has_bias:
+        # the detector's first layer: one input channel - a direct kernel instead of 49 single-float gathers per row
+        stem2d = (ci == 1 and co == 16 and d == 1 and k3 == (1, 7, 7) and stride == 2 and p3 == (0, 3, 3) and n <= 65535
+                  and not _switch("MI_NO_STEM2D"))
+        return Route("stem2d" if stem2d else "generic", 0)
+    # Conv2d(1, co, 3, padding=1) on its own kernels (conv_p2d.hip stem3_*): co a multiple of 4 that divides the block evenly
+    if (pass_ != "dgrad" and not nd5 and ci == 1 and k3 == (1, 3, 3) and stride == 1 and p3 == (0, 1, 1) and d3 is None
+            and not has_res and not relu and phys_ok
+            and 4 <= co <= 64 and co % 4 == 0 and 256 % (co // 4) == 0 and not _switch("MI_NO_P2D")):
+        return Route("stem3", 0)
+    if not nd5 and p2d_usable(shape, ci, co, k3, stride, p3, d3):
+        # the 2-D encoder's 3 x 3 / stride-1 layers; their weight gradient reads voxel-major operands through the transposing LDS read
+        if pass_ != "wgrad":
+            return Route("p2d", int(image == "p2d" and not profile))
+        if phys_ok and not _switch("MI_NO_P2D_WGRAD") and lib.mi_conv2d_p2d_wgrad_workspace_bytes(n, h, wd, ci):
+            return Route("p2d", 0)
+    if pass_ == "wgrad":
+        # the slab form (a _WgradJob that writes the gradient itself and leaves its split-K slabs to a batched reduce): always inside a step
+        # engine's backward pass, else where run_wgrad_jobs can batch the layer (conv_direct3.hip's shapes) at the end of the pass.  Under
+        # bench.py's roofline pass only the jobs the engine will queue take it - run_wgrad_jobs times them group by group -, everything else
+        # is timed call by call
+        rows = n * int(math.prod(_out_extent((d, h, wd), k3, stride, p3, dd)))
+        slab = (not accumulates and dd == (1, 1, 1) and (not profile or (deferred and side and rows <= SIDE_ROWS_MAX))
+                and (deferred or (WGRAD_BATCH and k3[0] == k3[1] == k3[2] and p3[0] == p3[1] == p3[2]
+                                  and lib.mi_conv3d_direct_usable(n, d, h, wd, ci, co, k3[0], stride, p3[0]) in (1, 2))))
+        return Route("generic", int(slab))
+    # (a forward call's all-ones dilation is none; a data gradient's counts as one: HipConvNd's layers stay on the generic entry there)
+    if nd5 and (d3 is None or (pass_ == "fwd" and dd == (1, 1, 1))) and k3 == (3, 3, 3) and p3 == (1, 1, 1) and bf16x3:
+        # the direct kernels are bf16x3 only: an f32 A/B run keeps every conv on the f32 MFMA
+        if image == "direct" and not profile and stride == 1 and lib.mi_conv3d_direct_usable(n, d, h, wd, co, co, 3, 1, 1):
+            return Route("direct", 0)
+        # 3^3 / padding 1 on a 2 x 2 x 2 volume (layer3, feature_3d): conv_cube2.hip, final in one launch (MI_CUBE2_REDUCE=1 keeps the
+        # partial sums + reduce launch of mi_conv_fwd_f32 / mi_conv_dgrad_f32)
+        if not _switch("MI_CUBE2_REDUCE") and lib.mi_conv3d_cube2_usable(n, d, h, wd, ci, co, 3, stride, 1):
+            return Route("cube2", 0)
+    return Route("generic", 0)
+
+
+def _p2d_image(w, dgrad, held):
+    """conv_p2d.hip's image of `w`: the one the step engine keeps (`held`), else cut on the parameter when the weights moved."""
+    if held is not None:
+        return held
+    _kernel_layout(w)
     dgrad = int(bool(dgrad))
-    if ACTIVE_IMAGES is not None and PROFILE is None:
-        img = ACTIVE_IMAGES.get_p2d(w, dgrad)
-        if img is not None:
-            return img
-    if not _phys_ok(w):
-        raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
     def cut(old):
         img = old if (old is not None and old.device == w.device) else torch.empty(
-            int(L.lib().mi_conv2d_p2d_wimg_bytes(int(w.shape[0]))), dtype=torch.uint8, device=w.device)
-        _prep_images("mi_conv2d_p2d_prep", [(w, None, dgrad, img)])
+            int(_IMAGE_FAMILIES["p2d"].nbytes(L.lib(), w, dgrad)), dtype=torch.uint8, device=w.device)
+        _prep_images("p2d", [(w, None, dgrad, img)])
         return img
     return _kept_image(w, ("_mi_p2d", "_mi_p2d_dgrad")[dgrad], w, (), cut)
 
 
-def _p2d_call(a, w, dgrad, res, mask, relu, tag):
+def _p2d_launch(route, a, w, dgrad, res, mask, relu, tag, held):
+    for t, name in ((res, "res"), (mask, "mask")):
+        if t is not None:
+            _f32c(t, name)
     n, h, wd, c = a.shape
     out = torch.empty_like(a)
-    img = _p2d_image(w, dgrad)
+    img = _p2d_image(w, dgrad, held if route.param else None)
     lib = L.lib()
     def call():
         return L.check(lib.mi_conv2d_p2d_f32(L.ptr(a), L.ptr(img), L.ptr(out), L.ptr(res), L.ptr(mask), int(relu), n, h, wd, c,
@@ -636,143 +680,128 @@ def _p2d_call(a, w, dgrad, res, mask, relu, tag):
     return out
 
 
+def _cube2_launch(lib, a, w, out, res, mask, relu, dgrad, n, c):
+    # arrival counters in front of the partial sums: zero at allocation, left zero by every call; one buffer per stream
+    ws = L.workspace(lib.mi_conv3d_cube2_workspace_bytes(n, c), a.device, "cube2", init=lambda b: b.zero_())
+    def call():
+        rc = lib.mi_conv3d_cube2_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), L.ptr(mask), relu, dgrad, n, c, L.ptr(ws),
+                                     ws.numel(), L.stream())
+        if rc:
+            L.drop_workspace(a.device, "cube2")         # its counters can no longer be trusted
+        return L.check(rc, "mi_conv3d_cube2_f32")
+    return call
+
+
+def _dense_launch(route, tag, g, a, w, out, res, mask, relu, held, flops, res_is_bias=0):
+    """The launch of a "direct" / "cube2" / "stem2d" / "generic" route of the forward (tag "fwd": out = act(conv(a, w) + res), res a bias row
+    when res_is_bias) or data-gradient pass (tag "dgrad": out = (conv_dgrad(a, w) + res) * (mask > 0)) of the geometry `g`."""
+    lib = L.lib()
+    n, d, h, wd, ci = g.key[:5]
+    dgrad = int(tag == "dgrad")
+    if route.family == "direct":                          # (the engine keeps the image current: no image build, never under PROFILE)
+        ws = _ws(lib.mi_conv3d_direct_workspace_bytes(n, ci), a.device, "conv")
+        L.check(lib.mi_conv3d_direct_f32(L.ptr(a), L.ptr(held), L.ptr(out), L.ptr(res), L.ptr(mask), relu, n, d, h, wd, ci,
+                                         L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_direct_f32")
+        return out
+    if route.family == "cube2":
+        call = _cube2_launch(lib, a, w, out, res, mask, relu, dgrad, n, ci)
+    elif route.family == "stem2d":
+        def call():
+            return L.check(lib.mi_stem2d_fwd_bias_f32(L.ptr(a), L.ptr(w), L.ptr(res), L.ptr(out), relu, n, h, wd, L.stream()),
+                           "mi_stem2d_fwd_bias_f32")
+    else:
+        ws = g.workspace(a.device)
+        if dgrad:
+            def call():
+                return L.check(lib.mi_conv_dgrad_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), L.ptr(mask), g.ref, L.ptr(ws), ws.numel(),
+                                                     L.stream()), "mi_conv_dgrad_f32")
+        else:
+            def call():
+                return L.check(lib.mi_conv_fwd_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), res_is_bias, relu, g.ref, L.ptr(ws),
+                                                   ws.numel(), L.stream()), "mi_conv_fwd_f32")
+    _prof_run(tag, flops, call)
+    return out
+
+
+def _conv_forward(x, w, k, stride, pad, res, bias, relu, dil, owner, inference, out, pool, who=""):
+    """conv_fwd (res) and conv_bias_fwd (bias, out, pool) on one route."""
+    _f32c(x, "x")
+    _kernel_layout(w)
+    nd5 = x.dim() == 5
+    k3, p3 = _k3(k, nd5), _p3(pad, nd5)
+    d3 = _k3(dil, nd5) if dil is not None else None
+    ci, co = int(x.shape[-1]), int(w.shape[0])
+    held_family, held = _held_image(w, False)
+    route = conv_route("fwd", tuple(x.shape), ci, co, k3, stride, p3, d3, inference=inference, has_res=res is not None,
+                       has_bias=bias is not None, relu=bool(relu), pool=pool, image=held_family, profile=PROFILE is not None)
+    if route.family is None:
+        return None
+    if bias is not None:
+        _f32c(bias, "bias")
+    if route.family == "d32":
+        return _d32_launch(route, x, w, bias, relu, owner, out, pool)
+    if route.family == "smallk":
+        return _smallk_launch(route, x, w, bias, relu, owner, out)
+    if route.family == "stem3":
+        n, h, wd, _ = x.shape
+        y = torch.empty((n, h, wd, co), dtype=torch.float32, device=x.device)
+        lib = L.lib()
+        def call():
+            return L.check(lib.mi_conv2d_stem3_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), n, h, wd, co, L.stream()), "mi_conv2d_stem3_fwd_f32")
+        _prof_run("fwd", 2.0 * y.numel() * 9, call)
+        return y
+    if route.family == "p2d":
+        return _p2d_launch(route, x, owner if owner is not None else w, False, res, None, relu, "fwd", held)
+    if d3 not in (None, (1, 1, 1)) and stride != 1:
+        raise L.HipExtensionError("dilated convolution needs stride 1")
+    g = _Geom(_as5d(x).shape, co, k3, stride, p3, d3)
+    y, _ = _out_tensor(out, (x.shape[0],) + (g.out if nd5 else g.out[1:]) + (co,), x, who=who)
+    return _dense_launch(route, "fwd", g, x, w, y, res if bias is None else bias, None, int(relu), held, 2.0 * y.numel() * ci * g.taps,
+                         int(bias is not None))
+
+
 def conv_fwd(x, w, k, stride, pad, res=None, relu=False, dil=None, owner=None, inference=False):
     """y = act(conv(x, w) + res).  x: (N,D,H,W,Ci) or (N,H,W,Ci) channels-last; w in kernel layout.
     dil: per-axis dilation (stride 1 only).  inference: the caller ran inference_mode() where the user's grad mode is visible
     (this function is also called from autograd.Function.forward, where grad mode is always off); `owner`: the tensor that
     outlives a temporary view `w` and keeps its cached weight image."""
-    _f32c(x, "x")
-    if not _phys_ok(w):
-        raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
-    nd5 = x.dim() == 5
-    k3, p3 = _k3(k, nd5), _p3(pad, nd5)
-    if res is None:
-        kind = _d32_kind(_as5d(x).shape, x.shape[-1], w.shape[0], k3, stride, p3, _k3(dil, nd5) if dil is not None else None, inference)
-        if kind == 4:                                 # inference, 1 x 1 (the transposed convolutions' products): tile-resident kernel
-            return _d32_call(x, w, None, relu, kind, owner=owner)
-        taps = _smallk_taps(x, w, k3, stride, p3, dil, nd5, inference)
-        if taps:                                      # inference, short reduction: no tile pipeline (conv_smallk.hip)
-            return _smallk_call(x, w, None, relu, taps, owner=owner)
-        if kind:                                      # inference, 3 x 3: patch-resident direct kernel (conv_d32.hip)
-            return _d32_call(x, w, None, relu, kind, owner=owner)
-    if (not nd5 and x.is_cuda and x.shape[-1] == 1 and tuple(k3) == (1, 3, 3) and stride == 1 and tuple(p3) == (0, 1, 1) and dil is None
-            and res is None and not relu and _stem3_ok(int(w.shape[0]))):
-        n, h, wd, _ = x.shape
-        y = torch.empty((n, h, wd, int(w.shape[0])), dtype=torch.float32, device=x.device)
-        lib = L.lib()
-        def call():
-            return L.check(lib.mi_conv2d_stem3_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), n, h, wd, int(w.shape[0]), L.stream()),
-                           "mi_conv2d_stem3_fwd_f32")
-        _prof_run("fwd", 2.0 * y.numel() * 9, call)
-        return y
-    if not nd5 and x.is_cuda and p2d_usable(x.shape, x.shape[-1], w.shape[0], k3, stride, p3, dil):
-        if res is not None:
-            _f32c(res, "res")
-        return _p2d_call(x, owner if owner is not None else w, False, res, None, relu, "fwd")
-    n, d, h, wd, ci = _as5d(x).shape
-    co = w.shape[0]
-    lib = L.lib()
-    dilated = dil is not None and tuple(dil) != (1, 1, 1)
-    if dilated and stride != 1:
-        raise L.HipExtensionError("dilated convolution needs stride 1")
-    g = _Geom((n, d, h, wd, ci), co, k3, stride, p3, _k3(dil, nd5) if dilated else None)
-    y = torch.empty((n,) + (g.out if nd5 else g.out[1:]) + (co,), dtype=torch.float32, device=x.device)
-    flops = 2.0 * y.numel() * ci * g.taps
-    img = _cached_image(w, False, n, d, h, wd, k3, stride, p3) if (nd5 and not dilated) else None
-    if img is not None:
-        ws = _ws(lib.mi_conv3d_direct_workspace_bytes(n, ci), x.device, "conv")
-        L.check(lib.mi_conv3d_direct_f32(L.ptr(x), L.ptr(img), L.ptr(y), L.ptr(res), None, int(relu), n, d, h, wd, ci,
-                                         L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_direct_f32")
-        return y
-    if nd5 and not dilated and _cube2_final(lib, n, d, h, wd, ci, co, k3, stride, p3):
-        ws = _cube2_ws(lib, n, ci, x.device)
-        def call():
-            return _cube2_call(lib, x, w, y, res, None, int(relu), 0, n, ci, ws)
-        _prof_run("fwd", flops, call)
-        return y
-    ws = g.workspace(x.device)
-    def call():
-        return L.check(lib.mi_conv_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(res), 0, int(relu), g.ref, L.ptr(ws), ws.numel(),
-                                           L.stream()), "mi_conv_fwd_f32")
-    _prof_run("fwd", flops, call)
-    return y
-
-
-def _cube2_final(lib, n, d, h, wd, ci, co, k3, stride, p3):
-    """3^3 / stride 1 / padding 1 on a 2 x 2 x 2 volume (layer3, feature_3d): conv_cube2.hip, final in one launch
-    (mi_conv3d_cube2_f32; MI_CUBE2_REDUCE=1 keeps the partial sums + reduce launch of mi_conv_fwd_f32 / mi_conv_dgrad_f32)."""
-    if os.environ.get("MI_CUBE2_REDUCE") or os.environ.get("MI_CONV_ARITH", "")[:1] == "f":
-        return False
-    return (tuple(k3) == (3, 3, 3) and tuple(p3) == (1, 1, 1) and
-            bool(lib.mi_conv3d_cube2_usable(n, d, h, wd, ci, co, 3, stride, 1)))
-
-
-def _cube2_ws(lib, n, c, device):
-    # arrival counters in front of the partial sums: zero at allocation, left zero by every call; one buffer per stream
-    return L.workspace(lib.mi_conv3d_cube2_workspace_bytes(n, c), device, "cube2", init=lambda b: b.zero_())
-
-
-def _cube2_call(lib, a, w, out, res, mask, relu, dgrad, n, c, ws):
-    rc = lib.mi_conv3d_cube2_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), L.ptr(mask), relu, dgrad, n, c, L.ptr(ws),
-                                 ws.numel(), L.stream())
-    if rc:
-        L.drop_workspace(a.device, "cube2")         # its counters can no longer be trusted
-    return L.check(rc, "mi_conv3d_cube2_f32")
+    return _conv_forward(x, w, k, stride, pad, res, None, relu, dil, owner, inference, None, False)
 
 
 def conv_dgrad(dy, w, in_shape, k, stride, pad, res=None, mask=None, dil=None):
     _f32c(dy, "dy")
+    in_shape = tuple(in_shape)
     nd5 = len(in_shape) == 5
     k3, p3 = _k3(k, nd5), _p3(pad, nd5)
-    shape5 = tuple(in_shape) if nd5 else (in_shape[0], 1) + tuple(in_shape[1:])
-    n, d, h, wd, ci = shape5
-    co = w.shape[0]
-    if not nd5 and dy.is_cuda and p2d_usable(tuple(in_shape), ci, co, k3, stride, p3, dil):
-        if res is not None:
-            _f32c(res, "res")
-        if mask is not None:
-            _f32c(mask, "mask")
-        return _p2d_call(dy, w, True, res, mask, False, "dgrad")
-    dx = torch.empty(tuple(in_shape), dtype=torch.float32, device=dy.device)
-    lib = L.lib()
-    d3 = _k3(dil, nd5) if dil is not None else (1, 1, 1)
-    g = _Geom(shape5, co, k3, stride, p3, d3)
-    flops = 2.0 * dy.numel() * ci * g.taps
-    img = _cached_image(w, True, n, d, h, wd, k3, stride, p3) if (nd5 and dil is None) else None
-    if img is not None:
-        ws = _ws(lib.mi_conv3d_direct_workspace_bytes(n, ci), dy.device, "conv")
-        L.check(lib.mi_conv3d_direct_f32(L.ptr(dy), L.ptr(img), L.ptr(dx), L.ptr(res), L.ptr(mask), 0, n, d, h, wd, ci,
-                                         L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_direct_f32")
-        return dx
-    if nd5 and dil is None and _cube2_final(lib, n, d, h, wd, ci, co, k3, stride, p3):
-        ws = _cube2_ws(lib, n, ci, dy.device)
-        def call():
-            return _cube2_call(lib, dy, w, dx, res, mask, 0, 1, n, ci, ws)
-        _prof_run("dgrad", flops, call)
-        return dx
-    ws = g.workspace(dy.device)
-    def call():
-        return L.check(lib.mi_conv_dgrad_f32(L.ptr(dy), L.ptr(w), L.ptr(dx), L.ptr(res), L.ptr(mask), g.ref, L.ptr(ws), ws.numel(),
-                                             L.stream()), "mi_conv_dgrad_f32")
-    _prof_run("dgrad", flops, call)
-    return dx
+    d3 = _k3(dil, nd5) if dil is not None else None
+    ci, co = int(in_shape[-1]), int(w.shape[0])
+    held_family, held = _held_image(w, True)
+    route = conv_route("dgrad", in_shape, ci, co, k3, stride, p3, d3, has_res=res is not None, image=held_family,
+                       profile=PROFILE is not None)
+    if route.family == "p2d":
+        return _p2d_launch(route, dy, w, True, res, mask, False, "dgrad", held)
+    dx = torch.empty(in_shape, dtype=torch.float32, device=dy.device)
+    g = _Geom(in_shape if nd5 else (in_shape[0], 1) + in_shape[1:], co, k3, stride, p3, d3)
+    return _dense_launch(route, "dgrad", g, dy, w, dx, res, mask, 0, held, 2.0 * dy.numel() * ci * g.taps)
 
 
 def conv_fwd_s2_block(x, w, w_ds):
     """Forward of a BasicBlock's stride-2 front in ONE launch (csrc/conv_s2.hip): (relu(conv(x; w, 3x3x3 stride 2 pad 1)),
     conv(x; w_ds, 1x1 stride 2)).  None when the shape is not one of the encoder's two (the caller runs the generic launches)."""
-    if x.dim() != 5 or w_ds is None:
+    if x.dim() != 5 or w_ds is None or not x.is_cuda:
         return None
-    n, g, g2, g3, ci = x.shape
-    co = w.shape[0]
-    lib = L.lib()
-    if not x.is_cuda or g != g2 or g != g3 or not lib.mi_conv3d_s2_fwd_usable(n, g, ci, co) or not (_phys_ok(w) and _phys_ok(w_ds)):
+    n, g, _, _, ci = x.shape
+    co = int(w.shape[0])
+    held_family, img = _held_image(w, False)
+    route = conv_route("fwd", tuple(x.shape), ci, co, (3, 3, 3), 2, (1, 1, 1), image=held_family, profile=PROFILE is not None,
+                       shortcut=True, phys_ok=_phys_ok(w) and _phys_ok(w_ds))
+    if route.family is None:
         return None
     _f32c(x, "x")
+    lib = L.lib()
     hmid = torch.empty((n, g // 2, g // 2, g // 2, co), dtype=torch.float32, device=x.device)
     r = torch.empty_like(hmid)
-    img = ACTIVE_IMAGES.get_s2(w, False) if (ACTIVE_IMAGES is not None and PROFILE is None) else None
-    if img is not None:                                   # the engine keeps the image current: no image build here
+    if route.param:                                       # the engine keeps the image current: no image build here
         L.check(lib.mi_conv3d_s2_fwd_img_f32(L.ptr(x), L.ptr(img), L.ptr(hmid), L.ptr(r), n, g, ci, co, L.stream()),
                 "mi_conv3d_s2_fwd_img_f32")
         return hmid, r
@@ -789,19 +818,21 @@ def conv_dgrad_s2_block(dh, d2, w, w_ds, in_shape, res=None, mask=None):
     """Data gradient of a BasicBlock's stride-2 front in ONE launch (csrc/conv_s2.hip): conv_dgrad(dh; w, 3x3x3 stride 2 pad 1)
     + conv_dgrad(d2; w_ds, 1x1 stride 2) (+ res), times (mask > 0).  Returns None when the shape is not one of the encoder's two
     (the caller then runs the two generic launches)."""
-    n, g, _, _, ci = in_shape
-    co = w.shape[0]
-    lib = L.lib()
-    if not dh.is_cuda or not lib.mi_conv3d_s2_dgrad_usable(n, g, ci, co):
+    if not dh.is_cuda:
         return None
-    if in_shape[1] != in_shape[2] or in_shape[2] != in_shape[3] or not (_phys_ok(w) and (w_ds is None or _phys_ok(w_ds))):
+    n, g, _, _, ci = in_shape
+    co = int(w.shape[0])
+    held_family, img = _held_image(w, True) if d2 is not None else (None, None)
+    route = conv_route("dgrad", tuple(in_shape), ci, co, (3, 3, 3), 2, (1, 1, 1), has_res=res is not None, image=held_family,
+                       profile=PROFILE is not None, shortcut=True, phys_ok=_phys_ok(w) and (w_ds is None or _phys_ok(w_ds)))
+    if route.family is None:
         return None
     _f32c(dh, "dh")
     if d2 is not None:
         _f32c(d2, "d2")
+    lib = L.lib()
     dx = torch.empty(tuple(in_shape), dtype=torch.float32, device=dh.device)
-    img = ACTIVE_IMAGES.get_s2(w, True) if (ACTIVE_IMAGES is not None and PROFILE is None and d2 is not None) else None
-    if img is not None:                                   # the engine keeps the images current: no image build here
+    if route.param:                                       # the engine keeps the images current: no image build here
         L.check(lib.mi_conv3d_s2_dgrad_img_f32(L.ptr(dh), L.ptr(d2), L.ptr(img), L.ptr(dx), L.ptr(res), L.ptr(mask), n, g, ci, co,
                                                L.stream()), "mi_conv3d_s2_dgrad_img_f32")
         return dx
@@ -992,8 +1023,9 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
     """dW for `param`, written (or accumulated) into param.grad."""
     nd5 = x.dim() == 5
     k3, p3 = _k3(k, nd5), _p3(pad, nd5)
+    d3 = _k3(dil, nd5) if dil is not None else None
     n, d, h, wd, ci = _as5d(x).shape
-    co = dy.shape[-1]
+    co = int(dy.shape[-1])
     lib = L.lib()
     if getattr(param, "_mi_wgrad_pending", False):
         # a module applied twice in one backward pass (the symmetric MoCo loss): the first contribution still waits for the end of
@@ -1005,37 +1037,12 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
     dest = _GradInto(param)
     tgt = dest.tgt
     flops = 2.0 * dy.numel() * ci * k3[0] * k3[1] * k3[2]
-    if (not nd5 and x.is_cuda and ci == 1 and tuple(k3) == (1, 3, 3) and stride == 1 and tuple(p3) == (0, 1, 1) and dil is None
-            and _stem3_ok(int(co)) and _phys_ok(param)):
+    route = conv_route("wgrad", tuple(x.shape), ci, co, k3, stride, p3, d3, profile=PROFILE is not None, phys_ok=_phys_ok(param),
+                       accumulates=dest.accumulates, deferred=DEFERRED_WGRADS is not None, side=SIDE_WGRADS is not None)
+    geom = _Geom((n, d, h, wd, ci), co, k3, stride, p3, d3) if route.family == "generic" else None
+    if route.family != "generic" or route.param:
         _f32c(x, "x"), _f32c(dy, "dy")
-        ws = _ws(lib.mi_conv2d_stem3_workspace_bytes(int(co)), x.device, "stem3")
-        def call():
-            return L.check(lib.mi_conv2d_stem3_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, int(co), L.ptr(ws), ws.numel(),
-                                                         L.stream()), "mi_conv2d_stem3_wgrad_f32")
-        with dest:
-            _prof_run("wgrad", flops, call)
-        return
-    # (under bench.py's roofline pass only the jobs the engine will queue take the job form - run_wgrad_jobs times them group by group -,
-    # everything else is timed right here, call by call)
-    p2d_ws = (int(lib.mi_conv2d_p2d_wgrad_workspace_bytes(n, h, wd, ci))
-              if (not nd5 and x.is_cuda and p2d_usable(tuple(x.shape), ci, int(co), k3, stride, p3, dil) and _phys_ok(param)
-                  and not os.environ.get("MI_NO_P2D_WGRAD")) else 0)
-    if p2d_ws:
-        # the 2-D encoder's 3 x 3 / stride-1 layers: voxel-major operands through the transposing LDS read (conv_p2d.hip p2d_wgrad_kernel)
-        _f32c(x, "x"), _f32c(dy, "dy")
-        ws = _ws(p2d_ws, x.device, "p2d_wgrad")
-        def call():
-            return L.check(lib.mi_conv2d_p2d_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, ci, L.ptr(ws), ws.numel(), L.stream()),
-                           "mi_conv2d_p2d_wgrad_f32")
-        with dest:
-            _prof_run("wgrad", flops, call)
-        return
-    d3 = _k3(dil, nd5) if dil is not None else (1, 1, 1)
-    geom = _Geom((n, d, h, wd, ci), co, k3, stride, p3, d3)
-    slab_form = (not dest.accumulates and d3 == (1, 1, 1) and x.is_cuda and
-                 (PROFILE is None or (DEFERRED_WGRADS is not None and SIDE_WGRADS is not None and dy.numel() // co <= SIDE_ROWS_MAX)))
-    if slab_form and (DEFERRED_WGRADS is not None or (WGRAD_BATCH and lib.mi_conv3d_direct_usable(n, d, h, wd, ci, co, k3[0], stride, p3[0]) in (1, 2)
-                                                      and k3[0] == k3[1] == k3[2] and p3[0] == p3[1] == p3[2])):
+    if route.param:                                        # the slab form
         nbytes = lib.mi_conv_workspace_bytes(geom.ref)
         slab = getattr(param, "_mi_slabs", None)
         if slab is None or slab.numel() < nbytes or slab.device != x.device:
@@ -1044,7 +1051,6 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
                 param._mi_slabs = slab
             # (pinned: a captured hipGraph writes and reads the old buffer on every replay - the step engines pin the slabs
             # when they capture; an eager call that needs more space gets a buffer of its own and the graph's stays alive)
-        _f32c(x, "x"), _f32c(dy, "dy")
         job = _WgradJob(x, dy, tgt, slab, geom, param, flops)    # (writes the gradient itself: no temporary to add behind it)
         if DEFERRED_WGRADS is not None:
             if _side_or_now(job, dy.numel() // co):
@@ -1052,10 +1058,21 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
             return
         if _defer_to_backward_end(job):                    # plain autograd: layer1's / layer2's weight gradients, batched at the end
             return
-    ws = geom.workspace(x.device)
-    def call():
-        return L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
-                       "mi_conv_wgrad_f32")
+    if route.family == "stem3":
+        ws = _ws(lib.mi_conv2d_stem3_workspace_bytes(co), x.device, "stem3")
+        def call():
+            return L.check(lib.mi_conv2d_stem3_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, co, L.ptr(ws), ws.numel(),
+                                                         L.stream()), "mi_conv2d_stem3_wgrad_f32")
+    elif route.family == "p2d":
+        ws = _ws(int(lib.mi_conv2d_p2d_wgrad_workspace_bytes(n, h, wd, ci)), x.device, "p2d_wgrad")
+        def call():
+            return L.check(lib.mi_conv2d_p2d_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, ci, L.ptr(ws), ws.numel(), L.stream()),
+                           "mi_conv2d_p2d_wgrad_f32")
+    else:
+        ws = geom.workspace(x.device)
+        def call():
+            return L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
+                           "mi_conv_wgrad_f32")
     with dest:
         _prof_run("wgrad", flops, call)
 
@@ -1158,52 +1175,11 @@ class _ConvFn(torch.autograd.Function):
 
 def conv_bias_fwd(x, w, bias, k, stride, pad, relu=False, out=None, pool=False):
     """y = act(conv(x, w) + bias[co]) in one launch (mi_conv_fwd_f32 with the residual read as a bias row), inference only: no
-    autograd node.  `out`: a contiguous (N, [D,] Ho, Wo, Co) tensor (or a leading-axis slice of one) that receives the result."""
-    _f32c(x, "x")
-    if not _phys_ok(w):
-        raise L.HipExtensionError("conv weight is not in kernel layout [tap][Cin][Cout]")
-    nd5 = x.dim() == 5
-    k3, p3 = _k3(k, nd5), _p3(pad, nd5)
+    autograd node.  `out`: a contiguous (N, [D,] Ho, Wo, Co) tensor (or a leading-axis slice of one) that receives the result.
+    pool: (y, maxpool2x2(y)) in one launch, with `out` possibly a channel slice of a wider tensor - or None: the caller pools by itself."""
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         raise L.HipExtensionError("conv_bias_fwd is inference only (no autograd node)")
-    kind = _d32_kind(_as5d(x).shape, x.shape[-1], w.shape[0], k3, stride, p3, None, True)
-    if pool:
-        # (y, maxpool2x2(y)) in one launch where the patch-resident 2-D kernel runs and nothing else asks for the result elsewhere;
-        # None: the caller pools by itself
-        if kind in (1, 3) and POOL_FUSED and PROFILE is None and x.dim() == 4:
-            return _d32_call(x, w, _f32c(bias, "bias"), relu, kind, pool=True, out=out)
-        return None
-    if kind == 4:                                     # 1 x 1: the tile-resident kernel (in front of the short-reduction one)
-        return _d32_call(x, w, _f32c(bias, "bias"), relu, kind, out=out)
-    taps = _smallk_taps(x, w, k3, stride, p3, None, nd5, True)
-    if taps:
-        return _smallk_call(x, w, _f32c(bias, "bias"), relu, taps, out=out)
-    if kind:
-        return _d32_call(x, w, _f32c(bias, "bias"), relu, kind, out=out)
-    n, d, h, wd, ci = _as5d(x).shape
-    co = w.shape[0]
-    g = _Geom((n, d, h, wd, ci), co, k3, stride, p3)
-    do, ho, wo = g.out
-    shape = (n, do, ho, wo, co) if nd5 else (n, ho, wo, co)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise L.HipExtensionError("conv_bias_fwd: `out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
-    lib = L.lib()
-    if (ci == 1 and co == 16 and d == 1 and tuple(k3) == (1, 7, 7) and stride == 2 and tuple(p3) == (0, 3, 3) and n <= 65535
-            and not os.environ.get("MI_NO_STEM2D")):
-        # the detector's first layer: one input channel - a direct kernel instead of 49 single-float gathers per row
-        def call():
-            return L.check(lib.mi_stem2d_fwd_bias_f32(L.ptr(x), L.ptr(w), L.ptr(_f32c(bias, "bias")), L.ptr(out), int(relu), n, h, wd,
-                                                      L.stream()), "mi_stem2d_fwd_bias_f32")
-        _prof_run("fwd", 2.0 * n * do * ho * wo * co * 49, call)
-        return out
-    ws = g.workspace(x.device)
-    def call():
-        return L.check(lib.mi_conv_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(out), L.ptr(_f32c(bias, "bias")), 1, int(relu), g.ref, L.ptr(ws),
-                                           ws.numel(), L.stream()), "mi_conv_fwd_f32")
-    _prof_run("fwd", 2.0 * n * do * ho * wo * co * ci * g.taps, call)
-    return out
+    return _conv_forward(x, w, k, stride, pad, None, bias, relu, None, None, True, out, pool, who="conv_bias_fwd: ")
 
 
 CONCAT_DIRECT = os.environ.get("CETPICK_CONCAT_DIRECT", "1") != "0"
@@ -1229,8 +1205,10 @@ def skip_into_concat_ok(conv, bn, x, co_up, up=None, up_bn=None):
         return False
     if up is not None and not _phys_ok(up.gemm_view()):
         return False
-    k3, p3 = _k3(conv.k, False), _p3(conv.pad, False)
-    return _d32_kind((n, 1, h, w, ci), ci, co, k3, conv.stride, p3, None, True) in (1, 3)
+    # ... and this layer on the patch-resident kernel that makes the pooled second output (conv_d32.hip kinds 1 / 3)
+    route = conv_route("fwd", (n, h, w, ci), ci, co, _k3(conv.k, False), conv.stride, _p3(conv.pad, False), inference=True, has_bias=True,
+                       relu=True, pool=True)
+    return route.family == "d32"
 
 
 def conv_bn(conv, bn, x, relu=False, pool=False, out=None):

@@ -51,9 +51,9 @@ class MocoStepEngine(StepGraph):
         for enc, group in ((self.moco.encoder_q, "q"), (self.moco.encoder_k, "k")):
             for m in enc.modules():
                 if isinstance(m, H.HipConv3d) and H.WeightImages.eligible(m.weight, m.k, m.stride, m.pad):
-                    imgs.add(group, m.weight, False)
+                    imgs.add(group, "direct", m.weight, False)
                     if group == "q":
-                        imgs.add(group, m.weight, True)
+                        imgs.add(group, "direct", m.weight, True)
             # the stride-2 block fronts (conv_s2.hip): forward image per encoder, data-gradient image for encoder_q
             for blk in enc.modules():
                 ds = getattr(blk, "downsample", None)
@@ -63,9 +63,9 @@ class MocoStepEngine(StepGraph):
                 co, ci = int(w.shape[0]), int(w.shape[1])
                 if (co, ci) not in ((128, 64), (256, 128)) or not (H._phys_ok(w) and H._phys_ok(wds)):
                     continue
-                imgs.add_s2(group, w, wds, False)
+                imgs.add(group, "s2", w, False, wds)
                 if group == "q":
-                    imgs.add_s2(group, w, wds, True)
+                    imgs.add(group, "s2", w, True, wds)
         self.moco.weight_images = imgs                 # MoCo re-cuts group "k" right behind its momentum update
         return imgs
 

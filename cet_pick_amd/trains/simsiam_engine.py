@@ -53,8 +53,8 @@ class SimSiamStepEngine(StepGraph):
         for m in self.model.modules():
             if isinstance(m, H.HipConv2d) and m.ci == m.co and m.k == 3 and m.stride == 1 and m.pad == 1 and m.co in (64, 128, 256) \
                     and H._phys_ok(m.weight):
-                imgs.add_p2d("p2d", m.weight, False)
-                imgs.add_p2d("p2d", m.weight, True)
+                imgs.add("p2d", "p2d", m.weight, False)
+                imgs.add("p2d", "p2d", m.weight, True)
         return imgs
 
     # ---- the step ------------------------------------------------------------------------------------------------

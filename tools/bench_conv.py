@@ -14,8 +14,8 @@ LAYERS = {
     "ds2":  (64, 8, 8, 8, 64, 128, 1, 2, 0),
 }
 def kernels_table(crop, batch):
-    """Which kernel family every convolution of the MoCo-3D encoder takes at a crop size, forward / data gradient / weight
-    gradient, with its time (us per call, hipGraph replay of 4 calls):  python tools/bench_conv.py --kernels [crop] [batch]"""
+    """Which route (hipops.conv_route: family[:parameter]) and which kernel family of the library every convolution of the MoCo-3D
+    encoder takes at a crop size, forward / data gradient / weight gradient, with its time (us per call, hipGraph replay of 4 calls):  python tools/bench_conv.py --kernels [crop] [batch]"""
     from cet_pick_amd import _lib as L
     lib = L.lib()
     def timeit(fn, n=20):
@@ -39,7 +39,7 @@ def kernels_table(crop, batch):
               ("layer3.0 front", (g2,) * 3, 128, 256, 3, 2, 1, "ds"),
               ("layer3 x3 + feature_3d", (g3,) * 3, 256, 256, 3, 1, 1, None)]
     print("crop %d^3, batch %d" % (crop, batch))
-    print("%-24s %-6s %-26s %9s" % ("layer", "pass", "kernel", "us"))
+    print("%-24s %-6s %-10s %-26s %9s" % ("layer", "pass", "route", "kernel", "us"))
     for name, (d, h, w), ci, co, k, st, pd, ds in layers:
         x = torch.randn(batch, d, h, w, ci, device="cuda")
         wt = H.conv_weight_param(co, ci, k); wt.data = wt.data.cuda(); wt.data.normal_()
@@ -50,28 +50,31 @@ def kernels_table(crop, batch):
         dy = torch.randn_like(y)
         def last():
             return lib.mi_debug_last_conv_kernel().decode()
+        def route(ps, kk=k, pp=pd, **kw):
+            r = H.conv_route(ps, tuple(x.shape), ci, co, (kk,) * 3, st, (pp,) * 3, **kw)
+            return "%s:%d" % r if r.param else str(r.family)
         rows = []
         if ds and H.conv_fwd_s2_block(x, wt, wd) is not None:
-            rows.append(("fwd", "s2_fwd (conv + shortcut)", timeit(lambda: H.conv_fwd_s2_block(x, wt, wd))))
+            rows.append(("fwd", route("fwd", shortcut=True), "s2_fwd (conv + shortcut)", timeit(lambda: H.conv_fwd_s2_block(x, wt, wd))))
         else:
             H.conv_fwd(x, wt, k, st, pd); kn = last()
-            rows.append(("fwd", kn, timeit(lambda: H.conv_fwd(x, wt, k, st, pd))))
+            rows.append(("fwd", route("fwd"), kn, timeit(lambda: H.conv_fwd(x, wt, k, st, pd))))
             if ds:
                 H.conv_fwd(x, wd, 1, st, 0); kn = last()
-                rows.append(("fwd", "shortcut: " + kn, timeit(lambda: H.conv_fwd(x, wd, 1, st, 0))))
+                rows.append(("fwd", route("fwd", 1, 0), "shortcut: " + kn, timeit(lambda: H.conv_fwd(x, wd, 1, st, 0))))
         if ci > 1:
             if ds and H.conv_dgrad_s2_block(dy, dy, wt, wd, x.shape) is not None:
-                rows.append(("dgrad", "s2_dgrad (conv + shortcut)", timeit(lambda: H.conv_dgrad_s2_block(dy, dy, wt, wd, x.shape))))
+                rows.append(("dgrad", route("dgrad", shortcut=True), "s2_dgrad (conv + shortcut)", timeit(lambda: H.conv_dgrad_s2_block(dy, dy, wt, wd, x.shape))))
             else:
                 H.conv_dgrad(dy, wt, x.shape, k, st, pd); kn = last()
-                rows.append(("dgrad", kn, timeit(lambda: H.conv_dgrad(dy, wt, x.shape, k, st, pd))))
+                rows.append(("dgrad", route("dgrad"), kn, timeit(lambda: H.conv_dgrad(dy, wt, x.shape, k, st, pd))))
         def wg():
             wt.grad = None
             H.conv_wgrad_into(x, dy, wt, k, st, pd)
         wg(); kn = last()
-        rows.append(("wgrad", kn, timeit(wg)))
-        for ps, kn, us in rows:
-            print("%-24s %-6s %-26s %9.1f" % (name, ps, kn, us), flush=True)
+        rows.append(("wgrad", route("wgrad"), kn, timeit(wg)))
+        for ps, rt, kn, us in rows:
+            print("%-24s %-6s %-10s %-26s %9.1f" % (name, ps, rt, kn, us), flush=True)
 
 
 def main():
