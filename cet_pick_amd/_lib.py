@@ -195,6 +195,8 @@ SIGNATURES = {
     "mi_umap_check": (_I, [_L, _I]),
     "mi_umap_smooth_knn": (_I, [_P, _L, _I, _D, _P, _P, _P, _P]),
     "mi_umap_union": (_I, [_P, _P, _P, _P, _L, _I, _P, _I, _P, _P, _P, _P]),
+    "mi_umap_rowmax": (_I, [_P, _P, _P, _P, _P, _L, _I, _D, _D, _P, _P]),
+    "mi_umap_supervise": (_I, [_P, _P, _P, _P, _L, _I, _D, _D, _P, _I, _P, _P, _P]),
     "mi_umap_epoch": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _D, _D, _c.c_uint64, _P]),
     # the spectral start of the UMAP map (csrc/spectral.hip)
     "mi_graph_components": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P]),

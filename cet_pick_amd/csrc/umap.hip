@@ -7,6 +7,9 @@
 //   union       one thread per directed edge: wsym = a + b - a b with b the weight of the opposite edge (found by binary search
 //               in the reverse list) or 0, whether that edge exists, and the edge's spacing eps = wmax / wsym in double (+inf
 //               for an edge pruned at wsym < wmax / n_epochs).
+//   rowmax,     the label-supervised map (fit_transform(x, y=labels)): s = wsym f(labels of the two ends), m_i the
+//   supervise   largest s over the pairs of vertex i (one wave per vertex), wsup = p + q - p q with p = s / m_i, q = s / m_j (one
+//               thread per directed edge), and the spacing of wsup as the union writes it.
 //   epoch       one wave (one workgroup) per vertex.  The lanes stride over the vertex's incident pairs - its forward edges, then
 //               the reverse edges without an opposite edge - 64 at a time; the pairs that fire this epoch are listed in LDS, and
 //               the lanes then stride over (firing, term): term 0 the attraction, terms 1..5 the negatives, drawn by Philox from
@@ -106,6 +109,62 @@ __global__ __launch_bounds__(256) void um_union_kernel(const int* index, const f
     }
     out_wsym[e] = ws;
     out_mutual[e] = mu;
+    if (wmax) {
+        const double wm = (double)wmax[0], v = (double)ws;
+        out_eps[e] = (!(v > 0.0) || v < wm / (double)n_epochs) ? (double)INFINITY : wm / v;
+    }
+}
+
+// ---- label supervision -----------------------------------------------------------------------------------------------------
+// umap-learn's categorical intersection: the factor on the weight of a pair by the labels of its ends (any negative label: unknown)
+__device__ __forceinline__ double um_factor(int la, int lb, double f_far, double f_unknown) {
+    return (la < 0 || lb < 0) ? f_unknown : (la != lb ? f_far : 1.0);
+}
+
+// m_i = the largest wsym f over the pairs of vertex i: its k forward edges, then every edge of its reverse list (a mutual pair
+// is met twice with the same value).  One wave per vertex; a maximum does not depend on the order.
+__global__ __launch_bounds__(256) void um_rowmax_kernel(const int* index, const float* wsym, const int* label, const int* rev_ptr,
+                                                        const int* rev_edge, int n, int k, double f_far, double f_unknown,
+                                                        double* out_m) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;                                  // (wave-uniform)
+    const long ne = (long)n * k;
+    const int i = (int)row, li = label[i];
+    double m = 0.0;
+    for (int c = lane; c < k; c += 64) {
+        const size_t e = (size_t)i * k + c;
+        const int j = index[e];
+        if (j >= 0 && j < n && j != i) m = fmax(m, (double)wsym[e] * um_factor(li, label[j], f_far, f_unknown));
+    }
+    int r0 = rev_ptr[i], r1 = rev_ptr[i + 1];
+    r0 = r0 < 0 ? 0 : r0;
+    r1 = r1 > ne ? (int)ne : r1;
+    for (long r = (long)r0 + lane; r < r1; r += 64) {
+        const int e2 = rev_edge[r];
+        if (e2 >= 0 && e2 < ne && e2 / k != i) m = fmax(m, (double)wsym[e2] * um_factor(label[e2 / k], li, f_far, f_unknown));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    if (lane == 0) out_m[i] = m;
+}
+
+// An edge that points outside [0, n) or at its own row gets wsup 0 and (with wmax) eps +inf, as in the union.
+__global__ __launch_bounds__(256) void um_supervise_kernel(const int* index, const float* wsym, const int* label, const double* rowmax,
+                                                           int n, int k, double f_far, double f_unknown, const float* wmax, int n_epochs,
+                                                           float* out_wsup, double* out_eps) {
+    const long ne = (long)n * k;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ne) return;
+    const int i = (int)(e / k), j = index[e];
+    float ws = 0.f;
+    if (j >= 0 && j < n && j != i) {
+        const double s = (double)wsym[e] * um_factor(label[i], label[j], f_far, f_unknown);
+        const double mi = rowmax[i], mj = rowmax[j];
+        const double p = s / (mi > 0.0 ? mi : 1.0), q = s / (mj > 0.0 ? mj : 1.0);
+        ws = (float)(p + q - p * q);
+    }
+    out_wsup[e] = ws;
     if (wmax) {
         const double wm = (double)wmax[0], v = (double)ws;
         out_eps[e] = (!(v > 0.0) || v < wm / (double)n_epochs) ? (double)INFINITY : wm / v;
@@ -235,6 +294,31 @@ extern "C" int mi_umap_union(const int32_t* index, const float* w, const int32_t
     if (n_epochs < 1) return MI_E_UNSUPPORTED;
     hipLaunchKernelGGL(um_union_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream, index, w, rev_ptr, rev_edge,
                        (int)n, k, wmax, n_epochs, out_wsym, out_mutual, out_eps);
+    MI_RETURN_IF_LAUNCH_FAILED();
+    return MI_OK;
+}
+
+extern "C" int mi_umap_rowmax(const int32_t* index, const float* wsym, const int32_t* label, const int32_t* rev_ptr,
+                              const int32_t* rev_edge, long n, int k, double f_far, double f_unknown, double* out_rowmax,
+                              mi_stream_t stream) {
+    if (!index || !wsym || !label || !rev_ptr || !rev_edge || !out_rowmax) return MI_E_ARG;
+    const int rc = um_check(n, k);
+    if (rc != MI_OK) return rc;
+    hipLaunchKernelGGL(um_rowmax_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, index, wsym, label, rev_ptr,
+                       rev_edge, (int)n, k, f_far, f_unknown, out_rowmax);
+    MI_RETURN_IF_LAUNCH_FAILED();
+    return MI_OK;
+}
+
+extern "C" int mi_umap_supervise(const int32_t* index, const float* wsym, const int32_t* label, const double* rowmax, long n, int k,
+                                 double f_far, double f_unknown, const float* wmax, int n_epochs, float* out_wsup, double* out_eps,
+                                 mi_stream_t stream) {
+    if (!index || !wsym || !label || !rowmax || !out_wsup || (wmax && !out_eps)) return MI_E_ARG;
+    const int rc = um_check(n, k);
+    if (rc != MI_OK) return rc;
+    if (n_epochs < 1) return MI_E_UNSUPPORTED;
+    hipLaunchKernelGGL(um_supervise_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream, index, wsym, label,
+                       rowmax, (int)n, k, f_far, f_unknown, wmax, n_epochs, out_wsup, out_eps);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }

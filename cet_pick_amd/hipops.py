@@ -2666,6 +2666,46 @@ def umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=None, out=None):
     return wsym, mutual, eps
 
 
+def _um_labelled(index, wsym, label):
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2:
+        raise L.HipExtensionError("index must be (N, k), got %s" % (tuple(index.shape),))
+    n, k = index.shape
+    _ts_table(index, "index", (n, k), torch.int32)
+    _ts_table(wsym, "wsym", (n, k))
+    _ts_table(label, "label", (n,), torch.int32)
+    return n, k
+
+
+def umap_rowmax(index, wsym, label, rev_ptr, rev_edge, f_far, f_unknown):
+    """rowmax (N,) float64 of the label-supervised map: the largest wsym f over the pairs of every vertex (its forward edges and
+    its reverse list), f = f_unknown where an end has a negative label (N,) int32, f_far where the labels differ, else 1."""
+    n, k = _um_labelled(index, wsym, label)
+    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
+    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    rowmax = torch.empty(n, dtype=torch.float64, device=wsym.device)
+    L.check(L.lib().mi_umap_rowmax(L.ptr(index), L.ptr(wsym), L.ptr(label), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, float(f_far),
+                                   float(f_unknown), L.ptr(rowmax), L.stream()), "mi_umap_rowmax(N=%d, k=%d)" % (n, k))
+    return rowmax
+
+
+def umap_supervise(index, wsym, label, rowmax, f_far, f_unknown, n_epochs, wmax=None, out=None):
+    """(wsup (N, k) fp32, eps (N, k) float64): umap-learn's categorical intersection and reset_local_connectivity per directed
+    edge, wsup = p + q - p q with p = wsym f / rowmax_i, q = wsym f / rowmax_j, and the spacings of wsup.  wmax: a (1,) fp32
+    device tensor holding the largest wsup; without it eps is not written (the two launches of umap_union)."""
+    n, k = _um_labelled(index, wsym, label)
+    _ts_table(rowmax, "rowmax", (n,), torch.float64)
+    if wmax is not None:
+        _ts_table(wmax, "wmax", (1,))
+    if out is None:
+        out = (torch.empty(n, k, dtype=torch.float32, device=wsym.device), torch.empty(n, k, dtype=torch.float64, device=wsym.device))
+    wsup, eps = _ts_table(out[0], "out[0]", (n, k)), _ts_table(out[1], "out[1]", (n, k), torch.float64)
+    L.check(L.lib().mi_umap_supervise(L.ptr(index), L.ptr(wsym), L.ptr(label), L.ptr(rowmax), n, k, float(f_far), float(f_unknown),
+                                      L.ptr(wmax), int(n_epochs), L.ptr(wsup), L.ptr(eps), L.stream()),
+            "mi_umap_supervise(N=%d, k=%d)" % (n, k))
+    return wsup, eps
+
+
 def umap_epoch(y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epochs, a, b, seed):
     """y_out = y_in + alpha (the attractions and negatives of the incident pairs that fire at `epoch` of n_epochs), every vertex
     from y_in alone (the epoch-synchronous form of umap-learn's loop); y_in, y_out (N, 2) fp32, two different buffers."""

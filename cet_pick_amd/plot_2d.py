@@ -4,6 +4,7 @@ plot_2d.py without its plots):
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
                                    [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode umap | --mode tsne]
                                    [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy] [--umap_init random | spectral]
+                                   [--label_map] [--target_weight 0.5]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -30,6 +31,13 @@ reference's arguments; --n_cluster 0 keeps the k-means assignment as the class),
                                           of the graph's normalised Laplacian (utils/spectral.py, csrc/spectral.hip), and adds
                                           init (the start that was used: "random" where the eigen-solver did not converge),
                                           n_graph_components and eigenvalues (those of the largest component) to the file.
+    OUT/embeddings_2d_labels.npz          with --label_map --num_neighbor K only, under any --mode: the label-supervised UMAP map,
+                                          the reference's umap.UMAP(K, min_dist, random_state).fit_transform(projs, y=final_lbs)
+                                          (DESIGN.md 4.16): the UMAP map steered by `label` of kmeans_labels.npz, from the first
+                                          K - 1 columns of the search already made (no second search), with --min_dist_umap,
+                                          --map_seed, --umap_init and --target_weight (umap-learn's 0.5): y, y01, label,
+                                          n_epochs, n_neighbors, min_dist, a, b, seed, target_weight, far_dist, and with
+                                          --umap_init spectral init, n_graph_components, eigenvalues of the supervised graph.
     OUT/all_colors.npy                    with the map: (N, 3) uint8, the colour of every pick at its y01 place on a 2-D colour
                                           table, in pick order (utils/vis3d.py, csrc/vis3d.hip: the reference's
                                           BaseColorMap2D._sample - round half to even, clamp) - the input of visualize_3dhm.
@@ -42,7 +50,8 @@ Only an explicit `--mode umap` makes the UMAP map.  The reference's default mode
 the files it does not write; the parser therefore tells the given value from the default one (DefaultMode), and making the bare
 default draw the map is a one-line change in main.
 
-Not made here: the WebP plots and PNG thumbnails, and the label-supervised second map.
+Not made here: the WebP plots and PNG thumbnails (the picture 2d_visualization_labels is drawn from
+embeddings_2d_labels.npz by the reader's own plotting).
 """
 import argparse
 import os
@@ -74,6 +83,10 @@ def add_arguments(parser):
     parser.add_argument("--min_dist_umap", type=float, default=0.5, help="min_dist of the UMAP map (the reference: 0.5)")
     parser.add_argument("--umap_init", choices=("random", "spectral"), default="random", help="start of the UMAP map: random, or "
                         "spectral as umap-learn's default (embeddings_2d.npz then also holds init, n_graph_components, eigenvalues)")
+    parser.add_argument("--label_map", action="store_true", help="with --num_neighbor K, under any --mode: also write "
+                        "embeddings_2d_labels.npz, the UMAP map steered by the class of every pick (the reference's second map)")
+    parser.add_argument("--target_weight", type=float, default=0.5, help="weight of the classes in the label-supervised map, 0..1 "
+                        "(umap-learn's default: 0.5)")
     # accepted for the reference's command lines; they only steer its plots
     parser.add_argument("--min_dist_vis", type=float, default=None)
     parser.add_argument("--save_out_img", type=int, default=1)
@@ -147,6 +160,22 @@ def umap_map(projs, n_neighbors, min_dist, seed, device, init="random"):
         return out if init == "random" else out + ((um.init_, um.n_components_, um.eigenvalues_),)
 
 
+def umap_label_map(projs, index, dist, label, n_neighbors, min_dist, seed, device, init="random", target_weight=0.5):
+    """The label-supervised UMAP map (the reference's fit_transform(projs, y=final_lbs)) from the first n_neighbors - 1 columns
+    of a search already made, index and dist (N, >= n_neighbors - 1) numpy: y (N, 2) fp32, n_epochs, a, b, far_dist and
+    (init used, graph components, eigenvalues) - the last one None for init="random"."""
+    import torch
+    from .utils.umap import UMAP
+    k = n_neighbors - 1
+    with torch.cuda.device(device):
+        um = UMAP(n_neighbors, min_dist=min_dist, seed=seed, device=device, init=init, target_weight=target_weight)
+        graph = (torch.from_numpy(np.ascontiguousarray(index[:, :k], dtype=np.int32)).to(device),
+                 torch.from_numpy(np.ascontiguousarray(dist[:, :k], dtype=np.float32)).to(device))
+        y = um.fit_transform(torch.from_numpy(projs).to(device), graph=graph, y=label)
+        return y, um.n_epochs_, um.a_, um.b_, um.far_dist_, \
+            None if init == "random" else (um.init_, um.n_components_, um.eigenvalues_)
+
+
 def map_colours(y01, table, device):
     """(N, 3) uint8: the colour of every row of y01 (N, 2) on the (W, H, 3) uint8 table, sampled on the device."""
     import torch
@@ -184,6 +213,12 @@ def main(args):
             from .utils.tsne import check_range
         check_range(len(projs), args.num_neighbor)
         table = load_colormap(args.colormap)
+    if args.label_map:
+        if args.num_neighbor is None:
+            raise ValueError("--label_map needs --num_neighbor K: the label-supervised map is a UMAP map with n_neighbors K")
+        from .utils.umap import check_range as check_umap_range, check_target_weight
+        check_umap_range(len(projs), args.num_neighbor)
+        check_target_weight(args.target_weight)
     if with_umap:
         print("[cet_pick_amd] plot_2d: the plots and thumbnails are not made here (--min_dist_vis, --save_out_img are ignored); "
               "--mode umap --num_neighbor %d writes the neighbour graph knn_graph.npz, the UMAP map embeddings_2d.npz (min_dist "
@@ -235,6 +270,22 @@ def main(args):
         np.savez(os.path.join(args.path, "knn_graph.npz"), index=index, dist=dist, k=np.int32(args.num_neighbor))
         print("[cet_pick_amd] plot_2d: %d nearest neighbours of %d picks (squared L2, self excluded) -> %s"
               % (args.num_neighbor, len(index), os.path.join(args.path, "knn_graph.npz")))
+    if args.label_map:
+        ys, n_epochs_s, a_s, b_s, far, start_s = umap_label_map(
+            projs, index, dist, label, args.num_neighbor, args.min_dist_umap, args.map_seed, torch.device("cuda", gpu),
+            init=args.umap_init, target_weight=args.target_weight)
+        ys = np.asarray(ys, np.float32)
+        start_s = {} if start_s is None else dict(
+            init=np.array(start_s[0]), n_graph_components=np.int32(start_s[1]),
+            eigenvalues=np.asarray([] if start_s[2] is None else start_s[2], np.float64))
+        np.savez(os.path.join(args.path, "embeddings_2d_labels.npz"), y=ys, y01=unit_square(ys), label=label,
+                 n_epochs=np.int32(n_epochs_s), n_neighbors=np.int32(args.num_neighbor), min_dist=np.float32(args.min_dist_umap),
+                 a=np.float64(a_s), b=np.float64(b_s), seed=np.int32(args.map_seed), target_weight=np.float64(args.target_weight),
+                 far_dist=np.float64(far), **start_s)
+        print("[cet_pick_amd] plot_2d: label-supervised UMAP map of %d picks in %d classes, n_neighbors %d, min_dist %g, "
+              "target_weight %g, %d epochs%s -> %s"
+              % (len(ys), len(set(label.tolist())), args.num_neighbor, args.min_dist_umap, args.target_weight, n_epochs_s,
+                 ", start %s" % start_s["init"] if start_s else "", os.path.join(args.path, "embeddings_2d_labels.npz")))
     if with_map:
         y = np.asarray(y, np.float32)
         y01 = unit_square(y)

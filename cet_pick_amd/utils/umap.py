@@ -21,8 +21,15 @@ Departures from umap-learn:
      back; init_ says which start was used, n_components_ and eigenvalues_ what the solver found.
   3. Exactly 5 negatives per sample (umap-learn's floating-point bookkeeping gives 5, now and then 4 or 6), drawn by
      Philox-4x32-10 from (vertex, incident slot, epoch, seed).
+The label-supervised map, `fit_transform(x, y=labels)`, is umap-learn's fit with a categorical target at its
+defaults (target_weight 0.5, -1 an unknown label): the weight of a pair is multiplied by exp(-2.5 / (1 - target_weight)) where the
+labels of its ends differ (by 0 at target_weight 1) and by exp(-1) where one is unknown, the local connectivity is reset (every
+row divided by its largest entry, then the fuzzy union with the transpose), and the spacings, the pruning and the spectral start
+are taken from that graph.  Everything after the graph is the plain fit.
 2 <= n_neighbors <= 128, N >= n_neighbors + 1.  There is no CPU path.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -33,6 +40,7 @@ from .tsne import reverse_graph
 N_NEIGHBORS_MIN, N_NEIGHBORS_MAX = 2, 128       # K - 1 <= 127 columns, and the neighbour search's k <= 128
 EPOCHS_SMALL, EPOCHS_LARGE, SMALL_N = 500, 200, 10000
 INITS = ("random", "spectral")
+UNKNOWN_DIST, FAR_DIST_AT_ONE = 1.0, 1.0e12     # umap-learn's categorical intersection: an unknown label, target_weight = 1
 
 
 def check_range(n, n_neighbors):
@@ -42,6 +50,33 @@ def check_range(n, n_neighbors):
                          % (N_NEIGHBORS_MIN, N_NEIGHBORS_MAX, n_neighbors))
     if n < n_neighbors + 1:
         raise ValueError("n_neighbors %d needs N >= n_neighbors + 1 = %d points, got %d" % (n_neighbors, n_neighbors + 1, n))
+
+
+def check_target_weight(target_weight):
+    """ValueError unless 0 <= target_weight <= 1 (a NaN is outside)."""
+    if not 0.0 <= float(target_weight) <= 1.0:
+        raise ValueError("target_weight must be in [0, 1], got %r" % (target_weight,))
+    return float(target_weight)
+
+
+def far_dist(target_weight):
+    """umap-learn's distance between two different classes: 2.5 / (1 - target_weight), 1e12 at target_weight 1."""
+    return 2.5 / (1.0 - target_weight) if target_weight < 1.0 else FAR_DIST_AT_ONE
+
+
+def check_labels(y, n):
+    """y as a contiguous (N,) int32 numpy array: ValueError for a wrong length, a non-integer dtype or a value below -1 (-1 is
+    the unknown label), before anything is launched."""
+    if isinstance(y, torch.Tensor):
+        y = y.detach().cpu().numpy()
+    y = np.asarray(y)
+    if y.dtype.kind not in "iu":
+        raise ValueError("y must hold integer class labels (-1: unknown), got dtype %s" % y.dtype)
+    if y.shape != (n,):
+        raise ValueError("y must have shape (%d,), one label per point, got %s" % (n, y.shape))
+    if y.size and (int(y.min()) < -1 or int(y.max()) > 2 ** 31 - 1):
+        raise ValueError("labels must be in -1..2^31 - 1 (-1: unknown), got %d..%d" % (int(y.min()), int(y.max())))
+    return np.ascontiguousarray(y, dtype=np.int32)
 
 
 def find_ab_params(min_dist, spread=1.0):
@@ -59,9 +94,12 @@ def find_ab_params(min_dist, spread=1.0):
 
 
 class UMAP:
-    def __init__(self, n_neighbors, min_dist=0.5, seed=42, n_epochs=None, device="cuda", init="random", spectral_options=None):
+    def __init__(self, n_neighbors, min_dist=0.5, seed=42, n_epochs=None, device="cuda", init="random", spectral_options=None,
+                 target_weight=0.5):
         if init not in INITS:
             raise ValueError("init must be one of %s, got %r" % (", ".join(INITS), init))
+        self.target_weight = target_weight                  # checked by fit_transform, where y is given
+        self.supervised_, self.far_dist_ = False, None
         self.n_neighbors, self.min_dist, self.seed = n_neighbors, float(min_dist), int(seed)
         self.init, self.spectral_options = init, dict(spectral_options or {})      # tol, max_basis, max_restarts of the solver
         self.init_, self.n_components_, self.eigenvalues_ = None, None, None
@@ -77,10 +115,15 @@ class UMAP:
         The map takes its first K - 1 columns."""
         return H.knn_search(x, x, int(self.n_neighbors), metric="l2", exclude_self=True)
 
-    def fit_transform(self, x, graph=None):
-        """(N, 2) float32 numpy.  graph: (index, dist) of a search already made, with K or K - 1 columns."""
+    def fit_transform(self, x, graph=None, y=None):
+        """(N, 2) float32 numpy.  graph: (index, dist) of a search already made, with K or K - 1 columns.  y: (N,) integer class
+        labels, -1 for an unknown one: the label-supervised map."""
         n = int(x.shape[0])
         check_range(n, self.n_neighbors)
+        self.supervised_, self.far_dist_ = y is not None, None
+        if y is not None:
+            self.far_dist_ = far_dist(check_target_weight(self.target_weight))
+            y = check_labels(y, n)
         if self.n_epochs is not None and self.n_epochs < 1:
             raise ValueError("n_epochs must be at least 1, got %d" % self.n_epochs)
         if self.device.type != "cuda":
@@ -97,10 +140,12 @@ class UMAP:
             k = int(self.n_neighbors) - 1
             if index.shape[0] != n or index.shape[1] not in (k, k + 1) or tuple(dist.shape) != tuple(index.shape):
                 raise ValueError("graph must have N = %d rows and %d or %d columns, got %s" % (n, k, k + 1, tuple(index.shape)))
-            return self._fit(index[:, :k].contiguous(), dist[:, :k].contiguous(), a, b, x)
+            label = None if y is None else torch.from_numpy(y).to(index.device)
+            return self._fit(index[:, :k].contiguous(), dist[:, :k].contiguous(), a, b, x, label)
 
-    def setup(self, index, dist, n_epochs, with_wsym=False):
-        """(rev_ptr, rev_edge, mutual, eps) of the graph's K - 1 columns: what the epochs read; with_wsym: and the weights."""
+    def setup(self, index, dist, n_epochs, with_wsym=False, label=None):
+        """(rev_ptr, rev_edge, mutual, eps) of the graph's K - 1 columns: what the epochs read; with_wsym: and the weights.
+        label (N,) int32 on the device: the weights and spacings of the label-supervised graph in their place."""
         n, k = index.shape
         mean_all = float(torch.sqrt(dist).sum(dtype=torch.float64).item()) / (n * (k + 1))
         w = H.umap_smooth_knn(dist, mean_all)[2]
@@ -108,6 +153,12 @@ class UMAP:
         out = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs)
         wmax = out[0].max().reshape(1)                      # stays on the device
         wsym, mutual, eps = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=wmax, out=out)
+        if label is not None:
+            f_far, f_unknown = math.exp(-far_dist(float(self.target_weight))), math.exp(-UNKNOWN_DIST)     # exp(-1e12) = 0.0
+            rowmax = H.umap_rowmax(index, wsym, label, rev_ptr, rev_edge, f_far, f_unknown)
+            sup = H.umap_supervise(index, wsym, label, rowmax, f_far, f_unknown, n_epochs)
+            wmax = sup[0].max().reshape(1)                  # 1.0 wherever an edge is left; taken from the device all the same
+            wsym, eps = H.umap_supervise(index, wsym, label, rowmax, f_far, f_unknown, n_epochs, wmax=wmax, out=sup)
         return (rev_ptr, rev_edge, mutual, eps) + ((wsym,) if with_wsym else ())
 
     def spectral_start(self, index, wsym, eps, mutual, rev_ptr, rev_edge, x=None):
@@ -122,15 +173,15 @@ class UMAP:
             return None
         return umap_start(Y.cpu().numpy(), self.seed)
 
-    def _fit(self, index, dist, a, b, x=None):
+    def _fit(self, index, dist, a, b, x=None, label=None):
         n = index.shape[0]
         n_epochs = self.n_epochs or (EPOCHS_SMALL if n <= SMALL_N else EPOCHS_LARGE)
         y0 = None
         if self.init == "spectral":
-            rev_ptr, rev_edge, mutual, eps, wsym = self.setup(index, dist, n_epochs, with_wsym=True)
+            rev_ptr, rev_edge, mutual, eps, wsym = self.setup(index, dist, n_epochs, with_wsym=True, label=label)
             y0 = self.spectral_start(index, wsym, eps, mutual, rev_ptr, rev_edge, x if isinstance(x, torch.Tensor) else None)
         else:
-            rev_ptr, rev_edge, mutual, eps = self.setup(index, dist, n_epochs)
+            rev_ptr, rev_edge, mutual, eps = self.setup(index, dist, n_epochs, label=label)
         self.init_ = "random" if y0 is None else "spectral"
         if y0 is None:
             y0 = np.random.RandomState(self.seed % 2 ** 32).uniform(-10, 10, (n, 2)).astype(np.float32)

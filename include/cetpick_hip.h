@@ -843,12 +843,27 @@ int mi_tsne_update(float* y, const float* grad, float* velocity, float* gains, l
  *                       seed)[t % 4]: nothing for v = i, +4 on both components at d2 = 0, else clip(2 b / ((0.001 + d2) (a d2^b
  *                       + 1)) (y_i - y_v)); clip to [-4, 4] per component.  y_out_i = fp32(y_in_i + alpha sum), every term
  *                       and the sum in double from y_in alone; y_out may not alias y_in.  No floating-point atomics: the same
- *                       inputs give the same bytes.  Edge ids and destinations outside their range are passed over. */
+ *                       inputs give the same bytes.  Edge ids and destinations outside their range are passed over.
+ * The label-supervised map (umap.UMAP.fit_transform(x, y) with a categorical target), DESIGN.md 4.16.  label (n) int32, any
+ * negative value: unknown.  s(e) = wsym[e] f, f = f_unknown where an end of the edge is unknown, f_far where the labels of its
+ * ends differ, 1 where they are equal; both factors are computed by the caller (exp(-1), exp(-2.5 / (1 - target_weight))).
+ *   mi_umap_rowmax      out_rowmax (n doubles): m_i = the largest s over the k forward edges of row i and the edges
+ *                       rev_edge[rev_ptr[i] .. rev_ptr[i + 1]) that end in it; 0 where there is none.  An edge that points
+ *                       outside [0, n) or at its own row contributes 0.
+ *   mi_umap_supervise   per directed edge i -> j: out_wsup = p + q - p q in double, stored as fp32, p = s / (m_i or 1),
+ *                       q = s / (m_j or 1) with rowmax as mi_umap_rowmax wrote it; wmax, n_epochs, out_eps as in mi_umap_union,
+ *                       on out_wsup.  An edge that points outside [0, n) or at its own row gets 0, +inf.  n_epochs < 1:
+ *                       MI_E_UNSUPPORTED. */
 int mi_umap_check(long n, int k);
 int mi_umap_smooth_knn(const float* dist2, long n, int k, double mean_all, float* out_rho, float* out_sigma, float* out_w,
                        mi_stream_t stream);
 int mi_umap_union(const int32_t* index, const float* w, const int32_t* rev_ptr, const int32_t* rev_edge, long n, int k,
                   const float* wmax, int n_epochs, float* out_wsym, uint8_t* out_mutual, double* out_eps, mi_stream_t stream);
+int mi_umap_rowmax(const int32_t* index, const float* wsym, const int32_t* label, const int32_t* rev_ptr, const int32_t* rev_edge,
+                   long n, int k, double f_far, double f_unknown, double* out_rowmax, mi_stream_t stream);
+int mi_umap_supervise(const int32_t* index, const float* wsym, const int32_t* label, const double* rowmax, long n, int k,
+                      double f_far, double f_unknown, const float* wmax, int n_epochs, float* out_wsup, double* out_eps,
+                      mi_stream_t stream);
 int mi_umap_epoch(const float* y_in, float* y_out, const int32_t* index, const int32_t* rev_ptr, const int32_t* rev_edge,
                   const uint8_t* mutual, const double* eps, long n, int k, int epoch, int n_epochs, double a, double b, uint64_t seed,
                   mi_stream_t stream);
