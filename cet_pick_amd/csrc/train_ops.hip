@@ -46,6 +46,10 @@ __global__ __launch_bounds__(256) void colreduce_kernel(ColReduceParams p) {
     const int tcol = threadIdx.x % CV, trow = threadIdx.x / CV;
     const int RS = 256 / CV;
     float s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    // STATS adds in double from the first row on (as bn_small_fwd_kernel does): var = E[x^2] - mean^2 cancels, and a sum of x^2
+    // rounded to fp32 leaves eps32 * mean^2 in it - against eps = 1e-5 that is 0.6 % of invstd for ONE row of |x| ~ 1.4, and it
+    // grows with mean^2 / var.  (The backward sums cancel nothing: they stay fp32 per thread.)
+    double w0[4] = {0, 0, 0, 0}, w1[4] = {0, 0, 0, 0};
     float mean[4] = {0, 0, 0, 0}, inv[4] = {1, 1, 1, 1};
     if (MODE == CR_BNBWD || MODE == CR_BNBWD_X) {
         float4 m = ld4(p.save + 4 * tcol), iv = ld4(p.save + p.C + 4 * tcol);
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(256) void colreduce_kernel(ColReduceParams p) {
         a[0] = a4.x; a[1] = a4.y; a[2] = a4.z; a[3] = a4.w;
         if (MODE == CR_STATS) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { s0[i] += a[i]; s1[i] = fmaf(a[i], a[i], s1[i]); }
+            for (int i = 0; i < 4; ++i) { w0[i] += (double)a[i]; w1[i] = fma((double)a[i], (double)a[i], w1[i]); }
         } else if (MODE == CR_BNBWD) {
             float4 x4 = ld4(p.x + o);
             float x[4] = {x4.x, x4.y, x4.z, x4.w};
@@ -94,7 +98,10 @@ __global__ __launch_bounds__(256) void colreduce_kernel(ColReduceParams p) {
     }
     __shared__ double red[2][256][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { red[0][threadIdx.x][i] = (double)s0[i]; red[1][threadIdx.x][i] = (double)s1[i]; }
+    for (int i = 0; i < 4; ++i) {
+        red[0][threadIdx.x][i] = MODE == CR_STATS ? w0[i] : (double)s0[i];
+        red[1][threadIdx.x][i] = MODE == CR_STATS ? w1[i] : (double)s1[i];
+    }
     __syncthreads();
     if (trow == 0) {
         double a0[4] = {0, 0, 0, 0}, a1[4] = {0, 0, 0, 0};
@@ -1067,6 +1074,8 @@ extern "C" int mi_bn_apply_fwd(const float* x, float* y, long M, int C, const do
 
 static bool pool_geom(int N, int Di, int Hi, int Wi, int k, int stride, int pad, PoolGeom* g) {
     if (N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || k <= 0 || k > 6 || stride <= 0 || pad < 0) return false;
+    // (a window larger than the padded volume: C++ rounds (Di + 2 pad - k) / stride towards zero, which would leave one voxel)
+    if (Di + 2 * pad < k || Hi + 2 * pad < k || Wi + 2 * pad < k) return false;
     const int Do = (Di + 2 * pad - k) / stride + 1, Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
     if (Do <= 0 || Ho <= 0 || Wo <= 0) return false;
     *g = PoolGeom{N, Di, Hi, Wi, Do, Ho, Wo, k, stride, pad};
@@ -1249,9 +1258,9 @@ extern "C" int mi_colsum(const float* dy, long M, int C, float* out, double* sum
 
 extern "C" int mi_maxpool3d_fwd(const float* x, float* y, uint8_t* argmax, int N, int Di, int Hi,
                                 int Wi, int C, int k, int stride, int pad, mi_stream_t stream) {
-    if (!x || !y || C % 4 || k <= 0 || k > 6 || stride <= 0 || pad < 0) return MI_E_ARG;
-    int Do = (Di + 2 * pad - k) / stride + 1, Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-    if (Do <= 0 || Ho <= 0 || Wo <= 0) return MI_E_ARG;
+    PoolGeom g;
+    if (!x || !y || C <= 0 || C % 4 || !pool_geom(N, Di, Hi, Wi, k, stride, pad, &g)) return MI_E_ARG;
+    const int Do = g.Do, Ho = g.Ho, Wo = g.Wo;
     long total = (long)N * Do * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y,
                        argmax, N, Di, Hi, Wi, C, Do, Ho, Wo, k, stride, pad);
@@ -1335,8 +1344,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k3s2_kernel(const float* dy, 
 // themselves: 8 us faster alone, 30 us slower inside the captured step, profiles/r05_experiments.txt item 6; removed in round 6.)
 extern "C" int mi_maxpool3d_bwd(const float* dy, const uint8_t* argmax, float* dx, int N, int Di,
                                 int Hi, int Wi, int C, int k, int stride, int pad, mi_stream_t stream) {
-    if (!dy || !argmax || !dx || C % 4 || k <= 0 || k > 6 || stride <= 0 || pad < 0) return MI_E_ARG;
-    int Do = (Di + 2 * pad - k) / stride + 1, Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
+    PoolGeom g;
+    if (!dy || !argmax || !dx || C <= 0 || C % 4 || !pool_geom(N, Di, Hi, Wi, k, stride, pad, &g)) return MI_E_ARG;
+    const int Do = g.Do, Ho = g.Ho, Wo = g.Wo;
     const long rows = (long)N * Di * Hi;
     if (rows >= (1l << 31)) return MI_E_UNSUPPORTED;
     // bands of rows per plane: 4 rows each by default (MI_MAXPOOL_BWD_BAND: tuning), the staged pooled rows of a band in LDS
