@@ -30,6 +30,15 @@ class Aug2d3dRanges(ctypes.Structure):
 
 _R = _c.POINTER(Aug2d3dRanges)
 
+
+class Aug3dRanges(ctypes.Structure):
+    """mi_aug3d_ranges of include/cetpick_hip.h, fields in header order"""
+    _fields_ = [(f, _F) for f in ("blur_p sigma_lo sigma_hi noise_p noise_lo noise_hi rot_p angle_lo angle_hi flip_z_below "
+                                  "flip_y_above drop_below centre_below swap_below").split()]
+
+
+_R3 = _c.POINTER(Aug3dRanges)
+
 # name -> (restype, argtypes); kept in step with include/cetpick_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "mi_abi_version": (_I, []),
@@ -58,6 +67,9 @@ SIGNATURES = {
     "mi_aug2d_apply": (_I, [_P, _c.c_int64, _I, _P, _P, _c.c_int64, _I, _F, _F, _P, _P]),
     "mi_aug2d3d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _R, _R, _P, _P]),
     "mi_aug2d3d_apply": (_I, [_P, _P, _c.c_int64, _I, _P, _P, _P, _P, _c.c_int64, _I, _F, _F, _F, _F, _P, _P]),
+    "mi_aug3d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _I, _I, _R3, _P, _P]),
+    "mi_aug3d_workspace_bytes": (_Z, [_c.c_int64, _I, _I]),
+    "mi_aug3d_apply": (_I, [_P, _P, _P, _c.c_int64, _P, _P, _c.c_int64, _I, _I, _P, _P, _Z, _P]),
     "mi_tilt_patches": (_I, [_P, _I, _P, _P, _c.c_int64, _I, _I, _D, _D, _P, _P, _P]),
     "mi_semi_labels": (_I, [_P, _I, _I, _I, _P, _c.c_int64, _P, _I, _I, _P]),
     "mi_semi_pairs": (_I, [_P, _P, _I, _P, _P, _c.c_int64, _I, _I, _P, _P, _P, _P]),

@@ -10,6 +10,7 @@
 //   simsiam_test_hm_3d.py:45-51  ToPILImage -> ToTensor -> Normalize(mean, std)   (mi_u8_roundtrip_normalize)
 // HBM-bound gather: rows of the crop are contiguous along x, so lanes read consecutive floats.
 #include "common.h"
+#include "znorm_chain.h"
 #include <algorithm>
 
 namespace {
@@ -18,26 +19,7 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 
 enum { CROP_RAW = 0, CROP_SUMZ_MINMAX = 1, CROP_ZNORM = 2, CROP_ZNORM_RESCALE_ZNORM = 3 };
 
-// block-wide (sum, sum of squares) in fp64 and (min, max) of per-thread partials; every thread gets the result
-__device__ __forceinline__ void block_stats(double s, double ss, float mn, float mx, double* out_s, double* out_ss,
-                                            float* out_mn, float* out_mx) {
-    __shared__ double rs[2][4];
-    __shared__ float rm[2][4];
-    s = wave_sum(s); ss = wave_sum(ss);
-    mn = -wave_max(-mn); mx = wave_max(mx);
-    __syncthreads();                                  // (the buffers may still be read from the previous round)
-    if ((threadIdx.x & 63) == 0) {
-        rs[0][threadIdx.x >> 6] = s; rs[1][threadIdx.x >> 6] = ss;
-        rm[0][threadIdx.x >> 6] = mn; rm[1][threadIdx.x >> 6] = mx;
-    }
-    __syncthreads();
-    *out_s = rs[0][0] + rs[0][1] + rs[0][2] + rs[0][3];
-    *out_ss = rs[1][0] + rs[1][1] + rs[1][2] + rs[1][3];
-    *out_mn = fminf(fminf(rm[0][0], rm[0][1]), fminf(rm[0][2], rm[0][3]));
-    *out_mx = fmaxf(fmaxf(rm[1][0], rm[1][1]), fmaxf(rm[1][2], rm[1][3]));
-}
-
-// mode 3: the crop sits in LDS; three in-place passes, statistics of each pass in fp64
+// mode 3: the crop sits in LDS; the chain's arithmetic is znorm_chain.h's
 __global__ __launch_bounds__(256) void crop_chain_kernel(const float* __restrict__ vol, int D, int H, int W,
                                                         const int* __restrict__ centres, int cz, int cy, int cx,
                                                         int flip_x, float* __restrict__ out) {
@@ -46,38 +28,14 @@ __global__ __launch_bounds__(256) void crop_chain_kernel(const float* __restrict
     const int x0 = centres[3 * n + 0] - cx / 2, y0 = centres[3 * n + 1] - cy / 2, z0 = centres[3 * n + 2] - cz / 2;
     const long HW = (long)H * W;
     const int vox = cz * cy * cx, pix = cy * cx;
-    double s = 0, ss = 0, S, SS;
-    float mn = INFINITY, mx = -INFINITY, MN, MX;
     for (int i = tid; i < vox; i += 256) {
         const int z = i / pix, y = (i / cx) % cy, x = i % cx;
         const int sx = flip_x ? (cx - 1 - x) : x;
-        const float v = vol[(long)clampi(z0 + z, 0, D - 1) * HW + (long)clampi(y0 + y, 0, H - 1) * W + clampi(x0 + sx, 0, W - 1)];
-        buf[i] = v;
-        s += v; ss += (double)v * v;
+        buf[i] = vol[(long)clampi(z0 + z, 0, D - 1) * HW + (long)clampi(y0 + y, 0, H - 1) * W + clampi(x0 + sx, 0, W - 1)];
     }
-    block_stats(s, ss, 0.f, 0.f, &S, &SS, &MN, &MX);
-    // ZNormalization: (x - mean) / std, unbiased
-    double mean = S / vox, var = (SS - vox * mean * mean) / (vox - 1);
-    float m = (float)mean, inv = (float)(1.0 / sqrt(var > 0 ? var : 0.0));
-    for (int i = tid; i < vox; i += 256) {
-        const float v = (buf[i] - m) * inv;
-        buf[i] = v;
-        mn = fminf(mn, v); mx = fmaxf(mx, v);
-    }
-    block_stats(0, 0, mn, mx, &S, &SS, &MN, &MX);
-    // RescaleIntensity(out_min_max = (-3, 3)): (x - min) / (max - min) * 6 - 3
-    const float sc = 6.0f / (MX - MN);
-    s = 0; ss = 0;
-    for (int i = tid; i < vox; i += 256) {
-        const float v = (buf[i] - MN) * sc - 3.0f;
-        buf[i] = v;
-        s += v; ss += (double)v * v;
-    }
-    block_stats(s, ss, 0.f, 0.f, &S, &SS, &MN, &MX);
-    mean = S / vox; var = (SS - vox * mean * mean) / (vox - 1);
-    m = (float)mean; inv = (float)(1.0 / sqrt(var > 0 ? var : 0.0));
+    const ZnormTail t = znorm_rescale_in_lds(buf, vox);
     float* o = out + (long)n * vox;
-    for (int i = tid; i < vox; i += 256) o[i] = (buf[i] - m) * inv;
+    for (int i = tid; i < vox; i += 256) o[i] = znorm_tail_value(buf[i], t);
 }
 
 __global__ void u8_roundtrip_normalize_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n, float mean,

@@ -12,6 +12,13 @@ parameters (csrc/augment2d3d.hip); both views and both channels of a batch are t
     table = draw_params_2d3d(sample_ids, seed, epoch, bbox)         # mi_aug2d3d_params: (2 views, B, 16)
     four = apply_2d3d(patches_2d, patches_3d, sample_ids, variants, table, means, stds)     # mi_aug2d3d_apply: (4, B, 1, bbox, bbox)
 
+The 3-D views of the MoCo training (datasets/tomo_pre.py:53-62, datasets/particle_pre.py:48-87: blur, noise, in-plane
+rotation, margin crop, ZNorm / Rescale(-3, 3) / ZNorm, a flip, one of three erasures) are made from the tomograms of a
+`CropTable` (csrc/augment3d.hip); both views of a batch are three launches:
+
+    table = draw_params_3d(sample_ids, seed, epoch, view, crop)     # mi_aug3d_params: (B, 16)
+    views = apply_3d(crop_table, sample_ids, table, crop)           # mi_aug3d_apply:  (B, 1, crop, crop, crop)
+
 A record is a pure function of (seed, epoch, sample id, view) - counter-based Philox-4x32-10 - so a sample is augmented
 the same way whatever batch, rank or world size it is served in, and nothing carries over between launches.
 """
@@ -172,3 +179,104 @@ class PairViewAugmenter:
         view is made of variant `variants[t]` (both int64, on the device)"""
         table = draw_params_2d3d(sample_ids, self.seed, epoch, self.bbox, self.strong, self.weak)
         return apply_2d3d(self.patches_2d, self.patches_3d, sample_ids, variants, table, self.means, self.stds).unbind(0)
+
+
+# ---- the 3-D views of the MoCo training --------------------------------------------------------------------------------------
+RECORD_WORDS_3D = 16
+# RandomBlur(p 0.15, std (0, 1)), RandomNoise(p 0.5, std (0, 0.25)), RandomAffine(p 0.75, degrees (0, 60) about the depth
+# axis); flip: u < 0.33 reverses z, u > 0.66 reverses y; erase: u < 0.25 drop_out, < 0.5 center_out, < 0.75 swap_out
+RANGES_3D = dict(blur_p=0.15, sigma=(0.0, 1.0), noise_p=0.5, noise=(0.0, 0.25), rot_p=0.75, angle=(0.0, 60.0),
+                 flip=(0.33, 0.66), erase=(0.25, 0.5, 0.75))
+MIN_CROP_3D, MAX_CROP_3D = 6, 32
+
+
+def geometry_3d(crop):
+    """-> (m, S, e, q) of a served edge `crop`: the margin the chain's Crop removes per side, the edge of the source box,
+    the edge of an erased box, half the edge of center_out's window.  ValueError for a crop the chain cannot serve."""
+    c = int(crop)
+    if c < MIN_CROP_3D or c > MAX_CROP_3D or c % 2:
+        raise ValueError("the 3-D views need an even crop in %d..%d (the crop sits in LDS), got %d" % (MIN_CROP_3D, MAX_CROP_3D, c))
+    m = c // 6
+    S = c + 2 * m
+    assert S // 8 == m
+    return m, S, S // 8, S // 4
+
+
+def erase_corners_3d(crop):
+    """The corners an erased box may take along an axis: [0, c/2 - 2e) U [c/2 + e, c - e), ascending (utils/image.py:484-486).
+    ValueError when fewer than two are left (swap_out draws two of them) or the box is empty."""
+    _, _, e, _ = geometry_3d(crop)
+    c = int(crop)
+    corners = list(range(0, c // 2 - 2 * e)) + list(range(c // 2 + e, c - e))
+    if e < 1 or len(corners) < 2:
+        raise ValueError("a crop of %d leaves %d erasure corners per axis; swap_out needs two" % (c, len(corners)))
+    return corners
+
+
+def _ranges_3d(rg):
+    return L.Aug3dRanges(float(rg["blur_p"]), float(rg["sigma"][0]), float(rg["sigma"][1]), float(rg["noise_p"]),
+                         float(rg["noise"][0]), float(rg["noise"][1]), float(rg["rot_p"]), float(rg["angle"][0]),
+                         float(rg["angle"][1]), float(rg["flip"][0]), float(rg["flip"][1]), float(rg["erase"][0]),
+                         float(rg["erase"][1]), float(rg["erase"][2]))
+
+
+def _draw_3d(sample_ids, seed, epoch, view, n_views, crop, ranges):
+    ids = _ids(sample_ids)
+    erase_corners_3d(crop)
+    table = torch.empty((n_views, ids.numel(), RECORD_WORDS_3D), dtype=torch.int32, device=ids.device)
+    L.check(L.lib().mi_aug3d_params(L.ptr(ids), ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(view), int(n_views),
+                                    int(crop), _ranges_3d(RANGES_3D if ranges is None else ranges), L.ptr(table), L.stream()),
+            "mi_aug3d_params")
+    return table
+
+
+def draw_params_3d(sample_ids, seed, epoch, view, crop, ranges=None):
+    """The records of `sample_ids` (int64, on the device) for `view` -> (n, 16) int32 table (layout: include/cetpick_hip.h)."""
+    return _draw_3d(sample_ids, seed, epoch, view, 1, crop, ranges)[0]
+
+
+def apply_3d(crop_table, sample_ids, table, crop):
+    """The chain on the boxes around the centres `sample_ids` of `crop_table` (datasets/subvols.py CropTable) with the records
+    of `table` -> (B, 1, crop, crop, crop) float32; a table (V, B, 16) of V views gives (V, B, 1, crop, crop, crop).  ValueError
+    when a source box (edge crop + 2 (crop // 6)) would leave its tomogram."""
+    _, S, _, _ = geometry_3d(crop)
+    erase_corners_3d(crop)
+    c = int(crop)
+    ids = _ids(sample_ids)
+    L.require_cuda(table, "table", torch.int32)
+    B = ids.numel()
+    stacked = table.dim() == 3
+    V = int(table.shape[0]) if stacked else 1
+    if tuple(table.shape[-2:]) != (B, RECORD_WORDS_3D) or table.dim() not in (2, 3) or not table.is_contiguous() or table.data_ptr() % 16:
+        raise L.HipExtensionError("table must be a contiguous ([V,] %d, %d) tensor, 16-byte aligned (the kernel loads whole "
+                                  "records), got %s" % (B, RECORD_WORDS_3D, tuple(table.shape)))
+    if not crop_table.boxes_inside(S):
+        raise ValueError("a %d^3 source box (crop %d + 2 x %d) leaves its tomogram: keep the centres %d voxels from the edges"
+                         % (S, c, c // 6, S // 2))
+    dev = crop_table.desc.device
+    out = torch.empty((V, B, 1, c, c, c), dtype=torch.float32, device=dev)
+    lib = L.lib()
+    # (scratch of this call alone, from the allocator of the current stream: a loader cuts on a stream of its own)
+    ws = torch.empty(max(int(lib.mi_aug3d_workspace_bytes(B, V, c)), 16), dtype=torch.uint8, device=dev)
+    L.check(lib.mi_aug3d_apply(L.ptr(crop_table.desc), L.ptr(crop_table.owner), L.ptr(crop_table.centres), crop_table.n,
+                               L.ptr(ids), L.ptr(table), B, V, c, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
+            "mi_aug3d_apply")
+    return out if stacked else out[0]
+
+
+class VolumeAugmenter:
+    """The two views of the reference's 3-D contrastive dataset: two independent draws of the chain on the same box
+    (datasets/particle_pre.py:55-87).  Holds the crop table, the ranges and the seed; a batch is three launches on the
+    current stream."""
+
+    def __init__(self, crop_table, crop, seed, ranges=RANGES_3D):
+        _, S, _, _ = geometry_3d(crop)
+        erase_corners_3d(crop)
+        if not crop_table.boxes_inside(S):
+            raise ValueError("a %d^3 source box (crop %d + 2 x %d) leaves its tomogram" % (S, int(crop), int(crop) // 6))
+        self.table, self.crop, self.seed, self.ranges = crop_table, int(crop), int(seed), dict(ranges)
+
+    def views(self, sample_ids, epoch):
+        """-> (input, input_aug) of the samples `sample_ids` (int64, on the device) in epoch `epoch`"""
+        records = _draw_3d(sample_ids, self.seed, epoch, 0, 2, self.crop, self.ranges)
+        return apply_3d(self.table, sample_ids, records, self.crop).unbind(0)

@@ -59,6 +59,19 @@ class CropTable:
         if int(self.owner.numel()) != self.n or (self.shift is not None and tuple(self.shift.shape) != tuple(self.centres.shape)):
             raise L.HipExtensionError("CropTable: owner / centres / shift disagree in length")
 
+        self._inside = {}
+
+    def boxes_inside(self, size):
+        """True when the even size^3 box around every centre (placed as `cut` places an even crop: it starts at centre -
+        size // 2) lies inside its tomogram.  One read-back per size, then remembered."""
+        size = int(size)
+        if size not in self._inside:
+            ext = torch.tensor([[v.shape[2], v.shape[1], v.shape[0]] for v in self.vols], dtype=torch.int32,
+                               device=self.desc.device)[self.owner.long()]                # (n, 3) extents along x, y, z
+            lo = self.centres - size // 2
+            self._inside[size] = bool(((lo >= 0) & (lo + size <= ext)).all())
+        return self._inside[size]
+
     def epoch_order(self, order):
         """the epoch's sample order (any int array) as the device array `cut` indexes"""
         return torch.as_tensor(np.ascontiguousarray(order, dtype=np.int64)).to(self.desc.device)

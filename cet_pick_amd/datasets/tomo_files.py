@@ -10,8 +10,9 @@ Semantics kept from the reference: the list format, `--order` / `--compress` / `
 crop geometry and the border rule of `load_data` (:196), the dataset mean / std (:238-239), the attributes
 simsiam_test_hm_3d.py reads.  The second view is the mirrored crop (2-D) / the crop shifted by <= 1 voxel and mirrored (3-D), as
 in the synthetic datasets; with `--augment reference` the 2-D train split serves the reference's random views instead (the
-strong chain on the crop, the weak chain on a neighbouring centre's crop: datasets/augment.py, on the device).  The torchio
-augmentations of the 3-D loader stay out of scope.
+strong chain on the crop, the weak chain on a neighbouring centre's crop: datasets/augment.py, on the device), and the 3-D
+loader serves two independent draws of the reference's torchio / numpy chain on the box around each pick (blur, noise, in-plane
+rotation, margin crop, ZNorm / Rescale / ZNorm, flip, erasure: csrc/augment3d.hip).
 """
 import os
 
@@ -22,7 +23,7 @@ from ..utils import image as Im
 from ..utils import loader as Ld
 from . import subvols as S
 from .synthetic_datasets import SyntheticSimSiamDataset
-from .synthetic_moco import SyntheticMocoLoader
+from .synthetic_moco import SyntheticMocoLoader, centre_border
 
 
 def read_image_list(path):
@@ -138,16 +139,18 @@ class TomoFileSimSiamDataset(SyntheticSimSiamDataset):
 class TomoFileMocoLoader(SyntheticMocoLoader):
     """3-D sub-tomogram pairs for moco_main from listed tomograms: crop centres = the DoG picks that keep a whole crop^3 box
     inside the volume; views = the z-normalised crop and the crop shifted by <= 1 voxel, mirrored along x (what
-    SyntheticMocoLoader serves).  A batch may mix tomograms: every tomogram's share is cut in one launch."""
+    SyntheticMocoLoader serves), or with `augment="reference"` the reference's two random views of the pick's box, whose
+    centres keep the larger source box inside the volume.  A batch may mix tomograms: every tomogram's share is cut in one
+    launch."""
 
-    def __init__(self, opt, crop=32, device="cuda", rank=0, world=1, split="train"):
+    def __init__(self, opt, crop=32, device="cuda", rank=0, world=1, split="train", augment="mirror"):
         self.vols, cents, owner = [], [], []
-        hc = crop // 2
+        bd = centre_border(crop, augment)
         for name, rec in load_listed_tomos(opt, split).items():
             d, h, w = rec.shape
             _, c = Im.get_potential_coords_pyramid(rec, sigmas=list(opt.dog), border_z=min(10, max(d // 4, 1)))
-            keep = ((c[:, 0] >= hc + 1) & (c[:, 0] < w - hc - 1) & (c[:, 1] >= hc + 1) & (c[:, 1] < h - hc - 1) &
-                    (c[:, 2] >= hc + 1) & (c[:, 2] < d - hc - 1))
+            keep = ((c[:, 0] >= bd) & (c[:, 0] < w - bd) & (c[:, 1] >= bd) & (c[:, 1] < h - bd) &
+                    (c[:, 2] >= bd) & (c[:, 2] < d - bd))
             c = c[keep]
             if len(c):
                 owner += [len(self.vols)] * len(c)
@@ -164,6 +167,7 @@ class TomoFileMocoLoader(SyntheticMocoLoader):
         self.rank, self.world = rank, world
         # the bookkeeping of every batch, on the device once: tomogram descriptors, owner / centre / shift per sample
         self.table = S.CropTable(self.vols, self.owner, self.centres, self.shift)
+        self._set_augment(augment)
         self.prefetch = os.environ.get("CETPICK_LOADER_PREFETCH", "1") != "0"
         self._stream = None
         print("Loaded {} {} samples".format(split, len(self.centres)))
@@ -191,14 +195,12 @@ class TomoFileMocoLoader(SyntheticMocoLoader):
         # one upload per EPOCH (the permutation); a batch is two launches that index it - no numpy slice, no np.unique, no
         # host-to-device copy, no scatter per tomogram (moco_main.py:122-156's DataLoader, minus its workers)
         order = self.table.epoch_order(self.epoch_order())
-        c, B = (self.crop,) * 3, self.batch_size
         dev = self.vols[0].device
         if dev.type != "cuda" or not self.prefetch:
             for b in range(len(self)):
-                yield {"input": self.table.cut(order, b * B, B, c),
-                       "input_aug": self.table.cut(order, b * B, B, c, shifted=True, flip_x=True)}
+                yield self._batch(order, b)
             return
-        # One batch ahead on a stream of the loader's own (what the reference's DataLoader workers are for): the two crop launches of
+        # One batch ahead on a stream of the loader's own (what the reference's DataLoader workers are for): the view launches of
         # batch b + 1 run next to training step b instead of in front of step b + 1.  The consumer's stream waits for the batch's
         # event; the tensors are handed over with record_stream (the allocator must not recycle them for the loader's stream early).
         if self._stream is None:
@@ -209,8 +211,7 @@ class TomoFileMocoLoader(SyntheticMocoLoader):
             if b == 0:
                 side.wait_stream(torch.cuda.current_stream(dev))    # (the epoch's order upload; the table has been there since __init__)
             with torch.cuda.stream(side):
-                batch = {"input": self.table.cut(order, b * B, B, c),
-                         "input_aug": self.table.cut(order, b * B, B, c, shifted=True, flip_x=True)}
+                batch = self._batch(order, b)
                 ev = torch.cuda.Event()
                 ev.record(side)
             return batch, ev

@@ -6,7 +6,9 @@ the ranks exchange gradients / keys / SyncBN sums over RCCL.
 
 Data: `--dataset synthetic` trains on a synthetic tomogram; any other `--dataset` value reads the reference's
 `<cwd>/data/<--train_img_txt>` list of MRC reconstructions (datasets/tomo_files.py: device loader -> DoG picks -> crop
-kernel, same batch contract; the random augmentations of the reference's datasets are out of scope).
+kernel, same batch contract).  The second view is the crop shifted by <= 1 voxel and mirrored by default; `--augment reference`
+serves the reference's two random 3-D views of every sub-volume (blur, noise, in-plane rotation, margin crop, ZNorm / Rescale /
+ZNorm, flip, one of three erasures), drawn and applied on the device (datasets/augment.py, csrc/augment3d.hip).
 """
 import os
 import random
@@ -68,10 +70,10 @@ def build(opt):
     from .datasets.tomo_files import use_files
     if not use_files(opt):
         loader = SyntheticMocoLoader(batch_size=opt.batch_size, seed=opt.seed, device=opt.device, rank=rank, world=world,
-                                     n_crops=max(opt.batch_size * 8, 256))
+                                     n_crops=max(opt.batch_size * 8, 256), augment=opt.augment)
     else:
         from .datasets.tomo_files import TomoFileMocoLoader
-        loader = TomoFileMocoLoader(opt, crop=opt.bbox, device=opt.device, rank=rank, world=world)
+        loader = TomoFileMocoLoader(opt, crop=opt.bbox, device=opt.device, rank=rank, world=world, augment=opt.augment)
     return opt, model, optimizer, trainer, loader, start_epoch, rank, world
 
 

@@ -70,7 +70,9 @@ _FLAGS = [
     ("--no_hipgraph", dict(dest="hipgraph", action="store_false")),
     # MI355X build only: the two views of the simsiam3d train split - the crop and its mirror image (default), or the reference's
     # random chains on the crop and on a neighbouring centre's crop, drawn and applied on the device (datasets/augment.py); for
-    # the simsiam2d3d train split the unaugmented pairs (default) or the reference's chains on both channels of a pair
+    # the simsiam2d3d train split the unaugmented pairs (default) or the reference's chains on both channels of a pair; for the
+    # moco loaders the crop and its shifted mirror image (default) or two draws of the reference's 3-D chain on the box around
+    # the crop (blur, noise, rotation, margin crop, normalisation, flip, erasure: csrc/augment3d.hip)
     ("--augment", dict(default="mirror", choices=["mirror", "reference"])),
 ]
 

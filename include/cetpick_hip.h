@@ -242,6 +242,61 @@ int mi_aug2d3d_apply(const float* patches_2d, const float* patches_3d, int64_t n
                      const int32_t* table_weak, int64_t n, int bbox, float mean_2d, float std_2d, float mean_3d, float std_3d,
                      float* out, mi_stream_t stream);
 
+/* Random 3-D views of the MoCo training (datasets/tomo_pre.py:53-62: RandomBlur(p 0.15), RandomNoise(p 0.5), RandomAffine(
+ * degrees (0, 60, 0, 0, 0, 0), p 0.75), Crop(size // 8), ZNormalization, RescaleIntensity(-3, 3), ZNormalization;
+ * datasets/particle_pre.py:48-87: a flip, then drop_out / center_out / swap_out of utils/image.py:481-536).  c = `crop` is the
+ * served edge (even, 6..32); m = c / 6, S = c + 2 m (S / 8 == m), e = S / 8, q = S / 4.  The source of sample s is the S^3 box
+ * of tomogram vols[owner[s]] that starts at centre - S / 2 per axis (so its inner c^3 is the crop mi_crop_normalize cuts
+ * around the same centre); a box that leaves the tomogram repeats the edge.
+ *
+ * mi_aug3d_params draws table[v][t] = the record of sample sample_ids[t] for view `view` + v, v < n_views; table is
+ * (n_views, n, 16) int32.  A record, 16 x 32 bit:
+ *     word 0       bit 0 blur, bit 1 noise, bit 2 rotation act; bits 4-5 flip (0 none, 1 reverse z, 2 reverse y); bits 8-9
+ *                  erasure (0 none, 1 drop_out, 2 center_out, 3 swap_out); other bits reserved, 0
+ *     word 1..3    sigma z, y, x of the blur (float32 bits), each lo + (hi - lo) u, not contracted; drawn whether or not bit 0 is set
+ *     word 4       sigma of the noise (float32 bits)
+ *     word 5       the rotation angle in degrees (float32 bits)
+ *     word 6, 7    (float) cos, (float) sin of the angle, from word 5 in fp64: t = (double) degrees * (pi / 180)
+ *     word 8..10   z, y, x corner of erasure box 0 (drop_out's box, swap_out's first)
+ *     word 11..13  z, y, x corner of erasure box 1 (swap_out's second); per axis distinct from box 0's
+ *     word 14, 15  k0, k1: the key of the view's noise (below)
+ * Draws: Philox-4x32-10 with key (seed low, seed high) and counter (sample id low, sample id high, epoch,
+ * view | j << 8 | 0x3D3D0000), j = 0..4, of which words w0..w3; u(w) = (w >> 8) / 2^24:
+ *     j = 0   w0: blur iff u < blur_p; w1..w3: sigma z, y, x        j = 1   w0: noise iff u < noise_p; w1: noise sigma;
+ *     w2: rotation iff u < rot_p; w3: angle                          j = 2   w0: flip z iff u < flip_z_below, y iff u >
+ *     flip_y_above; w1: drop_out iff u < drop_below, else center_out iff u < centre_below, else swap_out iff u < swap_below;
+ *     w2, w3: k0, k1         j = 3   w0..w2: index i0 = mulhi(w, N) of box 0's z, y, x corner in the corner set
+ *     j = 4   w0..w2: i = mulhi(w, N - 1), box 1's index i1 = i + (i >= i0)
+ * The corner set of an axis is [0, c/2 - 2e) U [c/2 + e, c - e) in ascending order, N entries.  A record is a pure function
+ * of (seed, epoch, sample id, view) and the ranges; its counters are disjoint from mi_aug2d_params' and mi_aug2d3d_params'.
+ *
+ * mi_aug3d_apply: out[v][t] (c^3; out is (n_views, n, c, c, c)) = the chain on the box of sample sample_ids[t] with
+ * table[v][t]:
+ *     blur:     scipy.ndimage.gaussian_filter(box, (sz, sy, sx)): per axis radius r = int(4 sigma + 0.5) (fp64; at most 4), taps
+ *               exp(-k^2 / (2 sigma^2)) normalised, edge mode `reflect` at the box's edges, axes z, y, x in turn; r = 0 leaves the axis
+ *     noise:    + sigma_n * N(0, 1) per voxel; the deviate of voxel i = (z S + y) S + x of the box is sqrt(-2 ln u1) cos(2 pi u2)
+ *               with u1 = ((w0 >> 8) + 1) / 2^24, u2 = (w1 >> 8) / 2^24 of Philox(counter (i, 0, 0, 0x3D3E0000), key (k0, k1))
+ *     rotation: output (z, y, x) = plane z sampled at (a + cos (y - a) - sin (x - a), a + sin (y - a) + cos (x - a)), a =
+ *               (S - 1) / 2, bilinear; a coordinate outside [0, S - 1] gives the minimum of the blurred, noised box
+ *     crop m per side; ZNormalization (unbiased std), RescaleIntensity(-3, 3), ZNormalization: mode 3 of mi_crop_normalize
+ *     flip; erasure: drop_out zeroes the e^3 box 0; center_out zeroes all but y, x in [c/2 - q, c/2 + q); swap_out writes box
+ *     1's old content to box 0, then box 0's old content to box 1.
+ * A step that does not act leaves the values untouched, so a record with only flip / erasure bits gives the mode-3 crop of
+ * the same centre, flipped / erased, bit for bit.  Corners are clamped into [0, c - e]; a sample id outside [0, n_samples)
+ * gives a NaN view and no read.  table and workspace must be 16-byte aligned; workspace (mi_aug3d_workspace_bytes) holds the
+ * blurred, noised boxes and their minima.  Three launches with mi_aug3d_params; no atomics: bit-reproducible.
+ * MI_E_ARG: sigma_hi > 1, thresholds outside [0, 1] or out of order; MI_E_UNSUPPORTED: crop odd, outside 6..32. */
+typedef struct mi_aug3d_ranges {
+    float blur_p, sigma_lo, sigma_hi, noise_p, noise_lo, noise_hi, rot_p, angle_lo, angle_hi, flip_z_below, flip_y_above,
+        drop_below, centre_below, swap_below;
+} mi_aug3d_ranges;
+int mi_aug3d_params(const int64_t* sample_ids, int64_t n, uint64_t seed, int epoch, int view, int n_views, int crop,
+                    const mi_aug3d_ranges* ranges, int32_t* table, mi_stream_t stream);
+size_t mi_aug3d_workspace_bytes(int64_t n, int n_views, int crop);
+int mi_aug3d_apply(const mi_vol_desc* vols, const int32_t* owner, const int32_t* centres_xyz, int64_t n_samples,
+                   const int64_t* sample_ids, const int32_t* table, int64_t n, int n_views, int crop, float* out,
+                   void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
 /* Tilt-series patches of the 2d3d exploration mode (datasets/tomo_pre_proj_angle_select_new2d3d.py:91-133
  * `convert_tomo_to_tilt` + `extract_patches`), one per centre.  Centre i = (x, y, z_full) of stack owner[i]
  * (owner == NULL: stack 0).  For every tilt t of that stack, in order:
