@@ -46,6 +46,7 @@ SIGNATURES = {
     "mi_debug_stamp": (_I, [_P, _P]),
     "mi_linear_stats_fwd_f32": (_I, [_P] * 5 + [_I] * 3 + [_P]),
     "mi_debug_last_conv_kernel": (_c.c_char_p, []),
+    "mi_debug_last_conv_plan": (_I, [_P, _I]),
     "mi_linear_bn_fwd_f32": (_I, [_P] * 5 + [_I] * 3 + [_P, _P, _F, _F] + [_P] * 4 + [_I, _P]),
     "mi_conv3d_stem_stats_workspace_bytes": (_Z, [_I] * 5),
     "mi_conv3d_stem_stats_f32": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _P, _Z, _P]),

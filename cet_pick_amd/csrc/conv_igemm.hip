@@ -923,6 +923,14 @@ Plan make_plan(int mode, bool stem, long M, int Ncols, long red_len, int red_ch,
     return pl;
 }
 
+// true: launch_mode runs this plan on the bf16x3 instantiations (64 x 64 x 32 / 16, forward also 128 x 32 x 32); every other tile
+// - the tuning overrides, the stem - is an f32-MFMA instantiation under either MI_CONV_ARITH
+bool plan_bf16x3(int mode, bool stem, const Plan& pl) {
+    if (stem || !conv_arith_bf16x3()) return false;
+    if (mode == MODE_FWD && pl.bm == 128 && pl.bn == 32 && pl.bk == 32) return true;
+    return pl.bm == 64 && pl.bn == 64 && (pl.bk == 32 || pl.bk == 16);
+}
+
 template <int MODE, bool STEM>
 int launch_mode(const ConvParams& p, const Plan& pl, hipStream_t s) {
     dim3 grid((unsigned)(pl.tiles_x * ((p.Ncols + pl.bn - 1) / pl.bn) * pl.splits), (unsigned)std::max(1, p.nbatch));    // x: decoded in the kernel
@@ -930,14 +938,15 @@ int launch_mode(const ConvParams& p, const Plan& pl, hipStream_t s) {
         // (a 128 x 64 bf16x3 tile was built and measured in round 2: layer-1 forward 100.6 us against 52.8 us, layer-2
         // 43.4 against 33.4, layer-3 25.0 against 23.7 - a batch-64 step does not have the rows for it: 32,768 im2col
         // rows are 256 tiles of 128, one per CU)
+        const bool bf3 = plan_bf16x3(MODE, STEM, pl);
         if constexpr (MODE == MODE_FWD) {
-            if (conv_arith_bf16x3() && pl.bm == 128 && pl.bn == 32 && pl.bk == 32) {
+            if (bf3 && pl.bn == 32) {
                 hipLaunchKernelGGL((conv_igemm_kernel<MODE, 128, 32, 32, false, true>), grid, dim3(NTHREADS), 0, s, p);
                 MI_RETURN_IF_LAUNCH_FAILED();
                 return MI_OK;
             }
         }
-        if (conv_arith_bf16x3() && pl.bm == 64 && pl.bn == 64 && (pl.bk == 32 || pl.bk == 16)) {
+        if (bf3) {
             if (pl.bk == 32) hipLaunchKernelGGL((conv_igemm_kernel<MODE, 64, 64, 32, false, true>), grid, dim3(NTHREADS), 0, s, p);
             else hipLaunchKernelGGL((conv_igemm_kernel<MODE, 64, 64, 16, false, true>), grid, dim3(NTHREADS), 0, s, p);
             MI_RETURN_IF_LAUNCH_FAILED();
@@ -1201,6 +1210,9 @@ size_t conv_ws_bytes(const Geom& g) {
 // which reduces by itself) reports 1 and `out` is final.
 // measurement aid (tools/bench_conv.py --kernels): the kernel family the last convolution call of this thread dispatched to
 thread_local const char* g_last_conv_kernel = "none";
+// test aid (tests/test_igemm_gpu.py): the schedule of this thread's last generic launch - mi_debug_last_conv_plan
+constexpr int PLAN_FIELDS = 11;
+thread_local int g_last_conv_plan[PLAN_FIELDS] = {0};
 
 int run_conv(int mode, const Geom& g, const float* a_src, const float* b_src, float* out,
              const float* res, const float* mask, int relu, void* ws, size_t ws_bytes, hipStream_t s,
@@ -1345,6 +1357,13 @@ int run_conv(int mode, const Geom& g, const float* a_src, const float* b_src, fl
     p.splits = pl.splits;
     if (pl.splits > 1) { p.out = (float*)ws; p.slab_stride = out_elems; }
     else { p.out = out; p.slab_stride = 0; }
+    {
+        // (wbox as the kernel applies it: only where a row tile lies inside one tap)
+        const int plan[PLAN_FIELDS] = {pl.bm, pl.bn, pl.bk, pl.splits, p.n_classes, p.border, p.fold,
+                                       (p.wbox && g.Ci % pl.bm == 0) ? 1 : 0, (int)(pl.tiles_x * p.ny_tiles * pl.splits),
+                                       plan_bf16x3(mode, stem, pl) ? 1 : 0, stem ? 1 : 0};
+        std::copy(plan, plan + PLAN_FIELDS, g_last_conv_plan);
+    }
     if (mode == MODE_FWD) rc = stem ? launch_mode<MODE_FWD, true>(p, pl, s) : launch_mode<MODE_FWD, false>(p, pl, s);
     else if (mode == MODE_DGRAD) rc = launch_mode<MODE_DGRAD, false>(p, pl, s);
     else rc = stem ? launch_mode<MODE_WGRAD, true>(p, pl, s) : launch_mode<MODE_WGRAD, false>(p, pl, s);
@@ -1402,6 +1421,14 @@ extern "C" int mi_conv_wgrad_f32(const float* x, const float* dy, float* dw, con
 
 /* measurement aid: the kernel family the last mi_conv* call of the calling thread ran ("direct3", "cube2 + reduce", ...) */
 extern "C" const char* mi_debug_last_conv_kernel(void) { return g_last_conv_kernel; }
+/* test aid: the schedule of the calling thread's last implicit-GEMM launch through mi_conv_{fwd,dgrad,wgrad}_f32 - bm, bn, bk, splits
+ * used, row classes, border, fold, wbox, grid blocks, bf16x3 kernel, stem - into out[0 .. n); returns the values written */
+extern "C" int mi_debug_last_conv_plan(int* out, int n) {
+    if (!out || n <= 0) return 0;
+    const int m = std::min(n, PLAN_FIELDS);
+    std::copy(g_last_conv_plan, g_last_conv_plan + m, out);
+    return m;
+}
 void mi_note_conv_kernel(const char* name) { g_last_conv_kernel = name; }       // (entry points outside run_conv: conv_cube2.hip)
 
 /* nn.Linear (+ bias) followed by training-mode nn.BatchNorm1d (+ ReLU) in ONE launch - the projection MLP of the MoCo-3D

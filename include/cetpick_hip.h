@@ -42,6 +42,10 @@ int mi_graph_node_counts(void* graph, int* counts);
 int mi_debug_stamp(void* slot, mi_stream_t stream);
 /* measurement aid: the kernel family the last mi_conv* call of the calling thread dispatched to (tools/bench_conv.py) */
 const char* mi_debug_last_conv_kernel(void);
+/* test aid: the schedule of the calling thread's last implicit-GEMM launch ("implicit GEMM ..." above), read-only.  Writes up to n of
+ * bm, bn, bk, splits actually used, row classes, border (0/1), fold (0/1), wbox (0/1, as the kernel applies it), grid blocks (x),
+ * bf16x3 kernel (0/1), stem (0/1) into out, in this order; returns the number of values written */
+int mi_debug_last_conv_plan(int* out, int n);
 /* gfx target the code objects were built for, e.g. "gfx950". */
 const char* mi_build_arch(void);
 

@@ -1,4 +1,5 @@
-"""A/B check of the border-class schedules against the plain schedule (MI_CONV_NO_BORDER=1) on random shapes."""
+"""A/B check of the border-class schedules against the plain schedule (MI_CONV_NO_BORDER=1) on random shapes.
+(The suite now pins this, with the plan that ran and against float64: tests/test_igemm_gpu.py, test_border_classes.)"""
 import os, sys, itertools
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
