@@ -39,6 +39,14 @@ class Aug3dRanges(ctypes.Structure):
 
 _R3 = _c.POINTER(Aug3dRanges)
 
+
+class PlotLayout(ctypes.Structure):
+    """mi_plot_layout of include/cetpick_hip.h, fields in header order"""
+    _fields_ = [(f, _I) for f in "P M R T label_dx label_dy glyph_px glyph_gap box_pad box_border".split()]
+
+
+_PL = _c.POINTER(PlotLayout)
+
 # name -> (restype, argtypes); kept in step with include/cetpick_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "mi_abi_version": (_I, []),
@@ -225,6 +233,13 @@ SIGNATURES = {
     "mi_vis_gauss_workspace_bytes": (_Z, [_L, _L, _L]),
     "mi_vis_gauss_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "mi_vis_paint": (_I, [_P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    # thumbnail selection, thumbnails, grey patch bytes and the map pictures (csrc/plot2d.hip)
+    "mi_plot_select_workspace_bytes": (_Z, [_L, _F]),
+    "mi_plot_select": (_I, [_P, _L, _F, _P, _P, _P, _Z, _P]),
+    "mi_plot_thumbs": (_I, [_P, _L, _I, _I, _P, _L, _I, _P, _P, _P]),
+    "mi_plot_patch_bytes": (_I, [_P, _L, _I, _I, _P, _P, _P]),
+    "mi_plot_raster_workspace_bytes": (_Z, [_I]),
+    "mi_plot_raster": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _PL, _I, _P, _P, _Z, _P]),
 }
 
 _lib = None

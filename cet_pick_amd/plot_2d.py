@@ -1,10 +1,11 @@
 """Cluster the exploration embeddings, write the per-pick class table and the 2-D UMAP or t-SNE map (the reference's
-plot_2d.py without its plots):
+plot_2d.py; its pictures and thumbnails with --min_dist_vis):
 
     python -m cet_pick_amd.plot_2d --input exp/.../all_output_info.npz --path OUT --n_cluster 48 [--k 256] [--niter 300]
                                    [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode umap | --mode tsne]
                                    [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy] [--umap_init random | spectral]
-                                   [--label_map] [--target_weight 0.5]
+                                   [--label_map] [--target_weight 0.5] [--min_dist_vis 1.3e-3] [--save_out_img 1]
+                                   [--plot_size 1500]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -50,8 +51,28 @@ Only an explicit `--mode umap` makes the UMAP map.  The reference's default mode
 the files it does not write; the parser therefore tells the given value from the default one (DefaultMode), and making the bare
 default draw the map is a one-line change in main.
 
-Not made here: the WebP plots and PNG thumbnails (the picture 2d_visualization_labels is drawn from
-embeddings_2d_labels.npz by the reader's own plotting).
+With --min_dist_vis D, GIVEN (the reference's documented value is 1.3e-3; without it nothing below is written), the input must
+also hold `subvol` (N, C, b, b), and utils/plot2d.py with csrc/plot2d.hip make on the MI355X:
+
+    OUT/imgs/{i}.png                      with --save_out_img 1 (the default): channel 0 of every pick's patch as the reference's
+                                          plt.imsave(cmap='gray') writes it (RGBA, R = G = B, A = 255) - the files the `image`
+                                          column of the parquet table points to.  The bytes come from the device; the PNG
+                                          encoding is host work on OMP_NUM_THREADS threads (4 where it is not set).
+    OUT/2d_visualization_out.png          with a map: --plot_size P (1500) pixels square.  The reference's filter picks the
+                                          thumbnails (in input order, a pick is shown unless one shown before it, or pick 0, lies
+                                          at a float32 squared y01 distance below D); every shown pick gets a disc of radius 0.03
+                                          map units in its colour of all_colors.npy and over it its 32 x 32 thumbnail (z-score,
+                                          quantize(-3, 3), torchvision's resize), later picks over earlier ones.
+    OUT/2d_visualization_labels.png       with --label_map: the same selection on the y01 of embeddings_2d_labels.npz, every
+                                          thumbnail tagged with its class number in a blue-framed box.
+    OUT/plot_2d_shown.npz                 shown_idx and / or shown_idx_labels (int32, ascending), min_dist_vis (f32), plot_size,
+                                          thumb: enough to rebuild or restyle a picture from the embeddings files.
+    OUT/2d_visualization_*.webp           the same pictures, lossless, under the reference's own file names, where PIL with WebP
+                                          support imports (one log line otherwise).
+
+Without a map --min_dist_vis writes the imgs/ only.  Not made here: the Phoenix interactive session, and
+matplotlib's own figure layout - the pictures have no axes, ticks, fonts or tight bounding box; their layout is fixed in
+utils/plot2d.py.
 """
 import argparse
 import os
@@ -87,9 +108,13 @@ def add_arguments(parser):
                         "embeddings_2d_labels.npz, the UMAP map steered by the class of every pick (the reference's second map)")
     parser.add_argument("--target_weight", type=float, default=0.5, help="weight of the classes in the label-supervised map, 0..1 "
                         "(umap-learn's default: 0.5)")
-    # accepted for the reference's command lines; they only steer its plots
-    parser.add_argument("--min_dist_vis", type=float, default=None)
-    parser.add_argument("--save_out_img", type=int, default=1)
+    parser.add_argument("--min_dist_vis", type=float, default=None, help="when given: write imgs/{i}.png and, with a map, the "
+                        "pictures; a pick gets a thumbnail unless one shown before it lies at a SQUARED map distance below this "
+                        "(the reference's documented value: 1.3e-3)")
+    parser.add_argument("--save_out_img", type=int, default=1, help="with --min_dist_vis: 1 writes imgs/{i}.png, anything else "
+                        "leaves them out")
+    parser.add_argument("--plot_size", type=int, default=1500, help="side of the pictures in pixels, at least 128 (the "
+                        "reference: 15 in at 100 dpi)")
     return parser
 
 
@@ -184,6 +209,66 @@ def map_colours(y01, table, device):
         return sample_colours(torch.from_numpy(np.ascontiguousarray(y01, dtype=np.float32)).to(device), table).cpu().numpy()
 
 
+def encoder_threads():
+    """Threads of the host-side PNG encoding: OMP_NUM_THREADS where it is set (16 at most), 4 otherwise."""
+    try:
+        return max(1, min(16, int(os.environ["OMP_NUM_THREADS"])))
+    except (KeyError, ValueError):
+        return 4
+
+
+def write_patch_images(subvol, out_dir, device):
+    """imgs/{i}.png of every pick as the reference's plt.imsave(patch[0], cmap='gray') writes them: RGBA, R = G = B = the
+    grey byte made on the device (utils/plot2d.patch_bytes), A = 255.  The encoding is host work, on a small thread pool."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .utils import plot2d as P2
+    grey = P2.patch_bytes(subvol, device=device)
+    os.makedirs(out_dir, exist_ok=True)
+
+    def one(i):
+        rgba = np.repeat(grey[i][:, :, None], 4, 2)
+        rgba[:, :, 3] = 255
+        P2.write_png(os.path.join(out_dir, "%d.png" % i), rgba)
+
+    with ThreadPoolExecutor(max_workers=encoder_threads()) as ex:
+        list(ex.map(one, range(len(grey))))
+    return len(grey)
+
+
+def map_picture(y01, subvol, thr, plot_size, device, colours=None, labels=None):
+    """The thumbnail selection on the map y01 and its picture, on the device: (shown_idx (n_shown,) int32, picture
+    (plot_size, plot_size, 3) uint8), both numpy.  With `colours` (N, 3) the picture is 2d_visualization_out (discs under
+    thumbnails), with `labels` (N,) it is 2d_visualization_labels (every thumbnail tagged with its class)."""
+    import torch
+    from .utils import plot2d as P2
+    with torch.cuda.device(device):
+        y = torch.from_numpy(np.ascontiguousarray(y01, dtype=np.float32)).to(device)
+        idx = P2.select(y, thr)
+        shown = idx.cpu().numpy()
+        patches = torch.from_numpy(np.ascontiguousarray(subvol[shown], dtype=np.float32)).to(device)
+        thumbs = P2.thumbnails(patches, torch.arange(len(shown), dtype=torch.int32, device=device))
+        if colours is not None:
+            pic = P2.draw_out(y, idx, thumbs, colours, plot_size)
+        else:
+            pic = P2.draw_labels(y, idx, thumbs, labels, plot_size)
+        return shown, pic.cpu().numpy()
+
+
+def write_picture(stem, pic):
+    """stem.png always; stem.webp (lossless: the reference's own file name) where PIL with WebP support imports."""
+    from .utils.plot2d import write_png
+    write_png(stem + ".png", pic)
+    try:
+        from PIL import Image, features
+        if not features.check("webp"):
+            raise ImportError("PIL without WebP support")
+        Image.fromarray(pic).save(stem + ".webp", lossless=True)
+        return True
+    except Exception as e:                                 # nothing may fail for lack of PIL: the PNG is written
+        print("[cet_pick_amd] plot_2d: %s.webp left out (%s); %s.png holds the same picture" % (stem, e, stem))
+        return False
+
+
 def unit_square(y):
     """(y - min) / (max - min) per axis, as the reference normalises its map (an axis of one value maps to 0)."""
     lo, hi = y.min(0), y.max(0)
@@ -219,7 +304,26 @@ def main(args):
         from .utils.umap import check_range as check_umap_range, check_target_weight
         check_umap_range(len(projs), args.num_neighbor)
         check_target_weight(args.target_weight)
-    if with_umap:
+    with_vis = args.min_dist_vis is not None
+    if with_vis:
+        if args.plot_size < 128:
+            raise ValueError("--plot_size is at least 128, got %d" % args.plot_size)
+        if "subvol" not in data.files:
+            raise ValueError("--min_dist_vis draws the picks' patches: %s holds no 'subvol' (it has %s)"
+                             % (args.input, ", ".join(data.files)))
+        subvol = np.asarray(data["subvol"], dtype=np.float32)
+        if subvol.ndim != 4 or len(subvol) != len(projs) or subvol.shape[2] != subvol.shape[3]:
+            raise ValueError("'subvol' of %s must be (%d, C, b, b), got %s" % (args.input, len(projs), subvol.shape))
+        thr = np.float32(args.min_dist_vis)
+        pictures = (["2d_visualization_out.png"] if with_map else []) + (
+            ["2d_visualization_labels.png"] if args.label_map and args.num_neighbor is not None else [])
+        print("[cet_pick_amd] plot_2d: --min_dist_vis %g writes %s%s" % (
+            args.min_dist_vis, "imgs/{i}.png of %d picks" % len(projs) if args.save_out_img == 1 else "no imgs/ (--save_out_img "
+            "%d)" % args.save_out_img, (", " + ", ".join(pictures) + " (%d x %d) and plot_2d_shown.npz" % (args.plot_size,
+            args.plot_size)) if pictures else " only: without a map (--mode umap | tsne with --num_neighbor K) there is no picture"))
+    if with_vis:
+        pass                                               # the line above says what is written
+    elif with_umap:
         print("[cet_pick_amd] plot_2d: the plots and thumbnails are not made here (--min_dist_vis, --save_out_img are ignored); "
               "--mode umap --num_neighbor %d writes the neighbour graph knn_graph.npz, the UMAP map embeddings_2d.npz (min_dist "
               "%g) and its colours all_colors.npy" % (args.num_neighbor, args.min_dist_umap))
@@ -250,6 +354,9 @@ def main(args):
     np.savez(os.path.join(args.path, "kmeans_labels.npz"), centroids=centroids, assign=assign, dist=D[:, 0].astype(np.float32),
              label=label, obj=km.obj.astype(np.float32), name=names, coords=coords)
     write_parquet(os.path.join(args.path, "interactive_info_parquet.gzip"), names, coords, projs, label, args.host)
+    if with_vis and args.save_out_img == 1:
+        n_img = write_patch_images(subvol, os.path.join(args.path, "imgs"), torch.device("cuda", gpu))
+        print("[cet_pick_amd] plot_2d: %d grey PNGs -> %s" % (n_img, os.path.join(args.path, "imgs")))
     print("[cet_pick_amd] plot_2d: %d picks, %d centroids, %d classes, objective %.6g -> %s"
           % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
     if args.num_neighbor is not None:
@@ -270,6 +377,7 @@ def main(args):
         np.savez(os.path.join(args.path, "knn_graph.npz"), index=index, dist=dist, k=np.int32(args.num_neighbor))
         print("[cet_pick_amd] plot_2d: %d nearest neighbours of %d picks (squared L2, self excluded) -> %s"
               % (args.num_neighbor, len(index), os.path.join(args.path, "knn_graph.npz")))
+    shown_sets = {}
     if args.label_map:
         ys, n_epochs_s, a_s, b_s, far, start_s = umap_label_map(
             projs, index, dist, label, args.num_neighbor, args.min_dist_umap, args.map_seed, torch.device("cuda", gpu),
@@ -286,6 +394,12 @@ def main(args):
               "target_weight %g, %d epochs%s -> %s"
               % (len(ys), len(set(label.tolist())), args.num_neighbor, args.min_dist_umap, args.target_weight, n_epochs_s,
                  ", start %s" % start_s["init"] if start_s else "", os.path.join(args.path, "embeddings_2d_labels.npz")))
+        if with_vis:
+            shown_l, pic = map_picture(unit_square(ys), subvol, thr, args.plot_size, torch.device("cuda", gpu), labels=label)
+            write_picture(os.path.join(args.path, "2d_visualization_labels"), pic)
+            shown_sets["shown_idx_labels"] = shown_l
+            print("[cet_pick_amd] plot_2d: %d of %d picks shown with their class -> %s"
+                  % (len(shown_l), len(ys), os.path.join(args.path, "2d_visualization_labels.png")))
     if with_map:
         y = np.asarray(y, np.float32)
         y01 = unit_square(y)
@@ -307,10 +421,21 @@ def main(args):
             # stubs for the clustering, the search and the map): the sampler is a kernel, and there is no host form of it
             print("[cet_pick_amd] plot_2d: all_colors.npy left out: no MI355X (cuda) device for the colour sampler")
             return
-        np.save(os.path.join(args.path, "all_colors.npy"), map_colours(y01, table, torch.device("cuda", gpu)))
+        colours = map_colours(y01, table, torch.device("cuda", gpu))
+        np.save(os.path.join(args.path, "all_colors.npy"), colours)
         print("[cet_pick_amd] plot_2d: colours of %d picks on the %d x %d table%s -> %s"
               % (len(y), table.shape[0], table.shape[1], "" if args.colormap else " (built in, not the reference's)",
                  os.path.join(args.path, "all_colors.npy")))
+        if with_vis:
+            shown, pic = map_picture(y01, subvol, thr, args.plot_size, torch.device("cuda", gpu), colours=colours)
+            write_picture(os.path.join(args.path, "2d_visualization_out"), pic)
+            shown_sets["shown_idx"] = shown
+            print("[cet_pick_amd] plot_2d: %d of %d picks shown over their colours -> %s"
+                  % (len(shown), len(y), os.path.join(args.path, "2d_visualization_out.png")))
+    if shown_sets:
+        from .utils.plot2d import THUMB
+        np.savez(os.path.join(args.path, "plot_2d_shown.npz"), min_dist_vis=thr, plot_size=np.int32(args.plot_size),
+                 thumb=np.int32(THUMB), **shown_sets)
 
 
 if __name__ == "__main__":

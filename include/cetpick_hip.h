@@ -986,6 +986,46 @@ int mi_vis_gauss_u8(const uint8_t* in, int Z, int R, int C, const double* weight
 int mi_vis_paint(const int32_t* picks_xyz, const uint8_t* colours, long n, const int32_t* slot_of_slice, int n_slots, int Z,
                  int R, int C, int z0, int nz, int32_t* index, uint8_t* out, mi_stream_t stream);
 
+/* The pictures of the 2-D map and the thumbnails of the picks (reference plot_2d.py:96-103, :121-218), DESIGN.md 4.18.
+ *   mi_plot_select       y01 (n, 2) fp32, finite.  The reference's filter in input order: `shown` starts as [y01[0]]; pick i
+ *                        is skipped when min over shown of fl(fl(dx dx) + fl(dy dy)) < thr (float32, dx = fl(x_i - x_j)),
+ *                        and is appended to shown and to shown_idx otherwise.  thr is a SQUARED distance; a distance equal
+ *                        to thr does not block; with thr > 0 pick 0 is never emitted, with thr <= 0 every pick is.
+ *                        shown_idx (room for n) int32 ascending, *count (device int32) their number, or -1 if the kernel
+ *                        found its own lists corrupted.  n <= 2^24 (MI_E_UNSUPPORTED above).
+ *   mi_plot_thumbs       patches (N, C, b, b) fp32, idx (n_shown) int32.  Per pick of idx: mean and population deviation
+ *                        over all C b b values in double, q = rint(clip(255 ((x - mean) / std + 3) / 6, 0, 255)) in double
+ *                        for every value (written to pre (n_shown, C, b, b) where pre is not null), then channel 0 of q
+ *                        resized to T x T as torch's bilinear interpolation without align_corners and without antialias
+ *                        does in float32, rounded half to even: out (n_shown, T, T) uint8.  A patch whose deviation is not
+ *                        > 0, or an index outside [0, N), gives bytes 0.  b <= 192.
+ *   mi_plot_patch_bytes  matplotlib's imsave(patch[0], cmap='gray'): per pick over channel 0, t = fl(fl(x - min) /
+ *                        fl(max - min)) in float32, k = min(floor(256 t), 255), out (N, b, b) = lut256[k]; max == min
+ *                        gives lut256[0].
+ *   mi_plot_raster       a white (P, P, 3) uint8 canvas.  The map point (u, v) of shown pick k = y01[idx[k]] sits at column
+ *                        M + rint(u S), row M + rint((1 - v) S), S = P - 1 - 2 M, in double.  mode 0: the discs
+ *                        dx^2 + dy^2 <= R^2 of all shown picks in order, each in colours[idx[k]] (colours (N, 3)), then
+ *                        all thumbnails (thumbs (n_shown, T, T) as grey, top-left at (column - T / 2, row - T / 2), inside a
+ *                        1-pixel black frame) in order.  mode 1: thumbnail k, then the class box of labels[idx[k]]
+ *                        (labels (N) int32 >= 0), for k in order; the box holds the decimal digits from glyphs (10, 7)
+ *                        uint8 (7 rows of 5 bits, bit 4 the left pixel), each cell glyph_px square, glyph_gap between
+ *                        digits, box_pad of white inside a box_border of (0, 0, 255) as the digits are; its bottom-left
+ *                        pixel is (column - label_dx, row - label_dy).  Later primitives cover earlier ones; everything is
+ *                        clipped at the canvas.  ws: mi_plot_raster_workspace_bytes(P), the priority image. */
+typedef struct mi_plot_layout {
+    int P, M, R, T, label_dx, label_dy, glyph_px, glyph_gap, box_pad, box_border;
+} mi_plot_layout;
+size_t mi_plot_select_workspace_bytes(long n, float thr);
+int mi_plot_select(const float* y01, long n, float thr, int32_t* shown_idx, int32_t* count, void* ws, size_t ws_bytes,
+                   mi_stream_t stream);
+int mi_plot_thumbs(const float* patches, long N, int C, int b, const int32_t* idx, long n_shown, int T, uint8_t* out, uint8_t* pre,
+                   mi_stream_t stream);
+int mi_plot_patch_bytes(const float* patches, long N, int C, int b, const uint8_t* lut256, uint8_t* out, mi_stream_t stream);
+size_t mi_plot_raster_workspace_bytes(int P);
+int mi_plot_raster(const float* y01, long N, const int32_t* idx, long n_shown, const uint8_t* thumbs, const uint8_t* colours,
+                   const int32_t* labels, const uint8_t* glyphs, const mi_plot_layout* layout, int mode, uint8_t* out, void* ws,
+                   size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
