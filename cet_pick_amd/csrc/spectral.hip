@@ -1,6 +1,6 @@
 // The spectral start of the UMAP map (umap.UMAP's init="spectral"), DESIGN.md 4.15: the eigen-solver's kernels over the graph the
-// epochs use.  The incident list of vertex i is what um_epoch_kernel walks - its forward edges, then the edges that end in it and
-// have mutual = 0 - without the edges the schedule pruned (eps = +inf); the weight of an entry is wsym of that directed edge.
+// epochs use.  The incident list of vertex i is the one of knn_graph.h, walked by the walker um_epoch_kernel uses, without the
+// edges the schedule pruned (eps = +inf); the weight of an entry is wsym of that directed edge.
 //   components  one wave per vertex, one launch = one sweep from label_in to label_out: the smallest label among the vertex and its
 //               incident vertices, then pointer jumping through label_in down to a vertex that is its own label.  `changed` is set
 //               to 1 by every vertex whose label moved.  Labels are vertex ids and never grow, so the fixed point - every vertex
@@ -15,6 +15,7 @@
 // Every sum is taken in double in a fixed order: lanes stride, a fixed butterfly, waves and chunks in index order.  No
 // floating-point atomics: the same inputs give the same bytes.
 #include "common.h"
+#include "knn_graph.h"
 #include "../../include/cetpick_hip.h"
 
 namespace {
@@ -28,37 +29,21 @@ inline int sp_vec_check(int m, long n, long ldq) {
     return MI_OK;
 }
 
-// f(j, e) for every entry of vertex i's incident list that this lane owns: other end j, directed edge e.
+// f(j, e) for every entry of vertex i's incident list that this lane owns and the schedule kept: other end j, directed edge e.
 template <typename F>
-__device__ __forceinline__ void sp_for_incident(const int* index, const double* eps, const uint8_t* mutual, const int* rev_ptr,
-                                                const int* rev_edge, int n, int k, int i, int lane, F&& f) {
-    const long ne = (long)n * k;
-    for (int c = lane; c < k; c += 64) {
-        const size_t e = (size_t)i * k + c;
-        const int j = index[e];
-        if (j >= 0 && j < n && j != i && eps[e] < (double)INFINITY) f(j, e);
-    }
-    int r0 = rev_ptr[i], r1 = rev_ptr[i + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > ne ? (int)ne : r1;
-    for (int r = r0 + lane; r < r1; r += 64) {
-        const int e2 = rev_edge[r];
-        if (e2 >= 0 && e2 < ne && !mutual[e2]) {
-            const int j = e2 / k;
-            if (j != i && eps[e2] < (double)INFINITY) f(j, (size_t)e2);
-        }
-    }
+__device__ __forceinline__ void sp_for_incident(const KnnEpochGraph& g, int i, int lane, F&& f) {
+    g.for_incident(i, lane, [&](const KnnEpochGraph::Entry& t) __attribute__((always_inline)) {
+        if (t.has && g.eps[t.e] < (double)INFINITY) f(t.j, t.e);
+    });
 }
 
-__global__ __launch_bounds__(256) void sp_components_kernel(const int* index, const double* eps, const uint8_t* mutual, const int* rev_ptr,
-                                                            const int* rev_edge, int n, int k, const int* label_in, int* label_out,
-                                                            int* changed) {
+__global__ __launch_bounds__(256) void sp_components_kernel(KnnEpochGraph g, const int* label_in, int* label_out, int* changed) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= n) return;                                  // (wave-uniform)
+    if (row >= g.n) return;                                // (wave-uniform)
     const int i = (int)row, was = label_in[i];
-    int best = (was < 0 || was >= n) ? i : was;
-    sp_for_incident(index, eps, mutual, rev_ptr, rev_edge, n, k, i, lane, [&](int j, size_t) {
+    int best = (was < 0 || was >= g.n) ? i : was;
+    sp_for_incident(g, i, lane, [&](int j, long) {
         const int l = label_in[j];
         if (l >= 0 && l < best) best = l;
     });
@@ -75,13 +60,12 @@ __global__ __launch_bounds__(256) void sp_components_kernel(const int* index, co
     }
 }
 
-__global__ __launch_bounds__(256) void sp_degree_kernel(const int* index, const float* wsym, const double* eps, const uint8_t* mutual,
-                                                        const int* rev_ptr, const int* rev_edge, int n, int k, double* deg, double* dis) {
+__global__ __launch_bounds__(256) void sp_degree_kernel(KnnEpochGraph g, const float* wsym, double* deg, double* dis) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= n) return;
+    if (row >= g.n) return;
     double acc = 0.0;
-    sp_for_incident(index, eps, mutual, rev_ptr, rev_edge, n, k, (int)row, lane, [&](int, size_t e) { acc += (double)wsym[e]; });
+    sp_for_incident(g, (int)row, lane, [&](int, long e) { acc += (double)wsym[e]; });
     acc = wave_sum(acc);
     if (lane == 0) {
         deg[row] = acc;
@@ -89,15 +73,14 @@ __global__ __launch_bounds__(256) void sp_degree_kernel(const int* index, const 
     }
 }
 
-__global__ __launch_bounds__(256) void sp_spmv_kernel(const int* index, const float* wsym, const double* eps, const uint8_t* mutual,
-                                                      const int* rev_ptr, const int* rev_edge, int n, int k, const double* dis,
-                                                      const double* __restrict__ x, double* __restrict__ y, int row0, int nrows) {
+__global__ __launch_bounds__(256) void sp_spmv_kernel(KnnEpochGraph g, const float* wsym, const double* dis, const double* __restrict__ x,
+                                                      double* __restrict__ y, int row0, int nrows) {
     const long local = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (local >= nrows) return;
     const int i = row0 + (int)local, row1 = row0 + nrows;
     double acc = 0.0;
-    sp_for_incident(index, eps, mutual, rev_ptr, rev_edge, n, k, i, lane, [&](int j, size_t e) {
+    sp_for_incident(g, i, lane, [&](int j, long e) {
         if (j >= row0 && j < row1) acc += (double)wsym[e] * (dis[j] * x[j - row0]);
     });
     acc = wave_sum(acc);
@@ -153,22 +136,23 @@ inline bool sp_inside(const double* p, const double* Q, long ldq, int m) { retur
 extern "C" int mi_graph_components(const int32_t* index, const double* eps, const uint8_t* mutual, const int32_t* rev_ptr,
                                    const int32_t* rev_edge, long n, int k, const int32_t* label_in, int32_t* label_out, int32_t* changed,
                                    mi_stream_t stream) {
-    if (!index || !eps || !mutual || !rev_ptr || !rev_edge || !label_in || !label_out || label_in == label_out || !changed) return MI_E_ARG;
+    const KnnEpochGraph g{{index, rev_ptr, rev_edge, (int)n, k}, mutual, eps};
+    if (!g.complete() || !label_in || !label_out || label_in == label_out || !changed) return MI_E_ARG;
     const int rc = mi_umap_check(n, k);
     if (rc != MI_OK) return rc;
-    hipLaunchKernelGGL(sp_components_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, index, eps, mutual, rev_ptr,
-                       rev_edge, (int)n, k, label_in, label_out, changed);
+    hipLaunchKernelGGL(sp_components_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, label_in, label_out,
+                       changed);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
 
 extern "C" int mi_spectral_degree(const int32_t* index, const float* wsym, const double* eps, const uint8_t* mutual, const int32_t* rev_ptr,
                                   const int32_t* rev_edge, long n, int k, double* out_deg, double* out_dis, mi_stream_t stream) {
-    if (!index || !wsym || !eps || !mutual || !rev_ptr || !rev_edge || !out_deg || !out_dis) return MI_E_ARG;
+    const KnnEpochGraph g{{index, rev_ptr, rev_edge, (int)n, k}, mutual, eps};
+    if (!g.complete() || !wsym || !out_deg || !out_dis) return MI_E_ARG;
     const int rc = mi_umap_check(n, k);
     if (rc != MI_OK) return rc;
-    hipLaunchKernelGGL(sp_degree_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, index, wsym, eps, mutual, rev_ptr,
-                       rev_edge, (int)n, k, out_deg, out_dis);
+    hipLaunchKernelGGL(sp_degree_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, wsym, out_deg, out_dis);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
@@ -176,12 +160,13 @@ extern "C" int mi_spectral_degree(const int32_t* index, const float* wsym, const
 extern "C" int mi_spectral_spmv(const int32_t* index, const float* wsym, const double* eps, const uint8_t* mutual, const int32_t* rev_ptr,
                                 const int32_t* rev_edge, long n, int k, const double* dis, const double* x, double* y, long row0,
                                 long nrows, mi_stream_t stream) {
-    if (!index || !wsym || !eps || !mutual || !rev_ptr || !rev_edge || !dis || !x || !y || x == y) return MI_E_ARG;
+    const KnnEpochGraph g{{index, rev_ptr, rev_edge, (int)n, k}, mutual, eps};
+    if (!g.complete() || !wsym || !dis || !x || !y || x == y) return MI_E_ARG;
     const int rc = mi_umap_check(n, k);
     if (rc != MI_OK) return rc;
     if (row0 < 0 || nrows < 1 || row0 + nrows > n) return MI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(sp_spmv_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, index, wsym, eps, mutual, rev_ptr,
-                       rev_edge, (int)n, k, dis, x, y, (int)row0, (int)nrows);
+    hipLaunchKernelGGL(sp_spmv_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, wsym, dis, x, y, (int)row0,
+                       (int)nrows);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }

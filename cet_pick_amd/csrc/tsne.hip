@@ -10,13 +10,14 @@
 //                          end of the split test j != i and j < end.
 //                 merge      per point the splits in split order (double), and per workgroup the sum of its points' sum q.
 //                 finish     Z = the workgroups' sums in a fixed tree, the same in every workgroup; one wave per point gathers
-//                            the K forward and the reverse edges (double), grad = 4 (attr - rep / Z); with out_kl the
-//                            wave's share of KL, per workgroup.
+//                            the K forward and the reverse edges (double; the graph: see knn_graph.h), grad = 4 (attr - rep / Z);
+//                            with out_kl the wave's share of KL, per workgroup.
 //                 kl         one workgroup adds those in a fixed tree.
 //   update      sklearn's _gradient_descent step, element-wise, every product and sum rounded once (fp contract off).
 // No floating-point atomics and no order that depends on timing: same inputs and same n_split -> same bytes.
 // hipcc-flags: -fno-slp-vectorize
 #include "common.h"
+#include "knn_graph.h"
 #include "../../include/cetpick_hip.h"
 
 namespace {
@@ -154,24 +155,14 @@ __global__ __launch_bounds__(256) void ts_merge_kernel(const double* part, int n
     if (tid == 0) zpart[blockIdx.x] = z;
 }
 
-// the number of entries of the ascending list e[lo, hi) whose source row (edge id / K) is below src
-__device__ __forceinline__ int ts_lower(const int* e, int lo, int hi, int K, int src) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e[mid] / K < src) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// One wave per point.  Edge e = i K + k runs from i to index[e] with conditional affinity p[e]; the joint affinity of the
-// pair {i, j} is (p[i -> j] + p[j -> i]) / 2N, a missing direction counting 0.  Edges that point outside [0, N) and edge ids
-// outside [0, N K) are passed over, so a damaged graph cannot address memory outside the tables.
-__global__ __launch_bounds__(256) void ts_finish_kernel(const float* y, const int* index, const float* p, const int* rev_ptr,
-                                                        const int* rev_edge, int n, int K, float exaggeration, const double* rep,
+// One wave per point over the graph of knn_graph.h: edge e has the conditional affinity p[e], and the joint affinity of the
+// pair {i, j} is (p[i -> j] + p[j -> i]) / 2N, a missing direction counting 0.
+__global__ __launch_bounds__(256) void ts_finish_kernel(const float* y, KnnGraph g, const float* p, float exaggeration, const double* rep,
                                                         const double* zpart, int nzb, float* grad, float* out_z, double* klpart) {
     __shared__ double red[4];
     __shared__ double klw[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = g.n;
     double zp = 0.0;
     for (int b = tid; b < nzb; b += 256) zp += zpart[b];
     const double Z = block_sum_256(zp, red, tid);
@@ -180,56 +171,37 @@ __global__ __launch_bounds__(256) void ts_finish_kernel(const float* y, const in
     const bool want_kl = klpart != nullptr;
     double ax = 0.0, ay = 0.0, kl = 0.0;
     if (i < n) {                                           // (wave-uniform)
-        const long ne = (long)n * K;
         const double xi = y[2 * (size_t)i], yi = y[2 * (size_t)i + 1];
         const double w2n = 1.0 / (2.0 * (double)n), ex = (double)exaggeration;
-        int r0 = rev_ptr[i], r1 = rev_ptr[i + 1];
-        r0 = r0 < 0 ? 0 : r0;
-        r1 = r1 > ne ? (int)ne : r1;
-        for (int k = lane; k < K; k += 64) {               // forward edges
-            const size_t e = (size_t)i * K + k;
-            const int j = index[e];
-            if (j < 0 || j >= n || j == i) continue;
+        // the attractive term of one directed edge between i and j with conditional affinity pe; returns q_ij
+        const auto attract = [&](int j, double pe) __attribute__((always_inline)) {
             const double dx = xi - (double)y[2 * (size_t)j], dy = yi - (double)y[2 * (size_t)j + 1];
             const double q = 1.0 / (1.0 + dx * dx + dy * dy);
-            const double pe = (double)p[e];
             const double w = pe * w2n * ex * q;
             ax += w * dx;
             ay += w * dy;
+            return q;
+        };
+        int j, e2;
+        for (int c = lane; c < g.k; c += 64) {             // forward edges
+            const long e = (long)i * g.k + c;
+            if (!g.forward(i, e, j)) continue;
+            const double pe = (double)p[e], q = attract(j, pe);
             if (want_kl) {                                 // the pair's joint affinity: add the edge j -> i where it exists
-                double pj = pe;
-                const int at = ts_lower(rev_edge, r0, r1, K, j);
-                if (at < r1) {
-                    const int e2 = rev_edge[at];
-                    if (e2 >= 0 && e2 < ne && e2 / K == j) pj += (double)p[e2];
-                }
-                pj *= w2n;
+                const int back = g.opposite(i, j);
+                const double pj = (back >= 0 ? pe + (double)p[back] : pe) * w2n;
                 if (pj > 0.0) kl += pj * log(pj * Z / q);
             }
         }
-        for (int r = r0 + lane; r < r1; r += 64) {         // reverse edges: j -> i
-            const int e2 = rev_edge[r];
-            if (e2 < 0 || e2 >= ne) continue;
-            const int j = e2 / K;
+        const KnnGraph::Range rr = g.rev_range(i);
+        for (long r = (long)rr.r0 + lane; r < rr.r1; r += 64) {        // reverse edges: j -> i
+            if (!g.reverse(r, e2)) continue;
+            j = g.source(e2);
             if (j == i) continue;
-            const double dx = xi - (double)y[2 * (size_t)j], dy = yi - (double)y[2 * (size_t)j + 1];
-            const double q = 1.0 / (1.0 + dx * dx + dy * dy);
-            const double pe = (double)p[e2];
-            const double w = pe * w2n * ex * q;
-            ax += w * dx;
-            ay += w * dy;
-            if (want_kl) {                                 // counted above when i -> j exists too: that is an edge into j from i
-                int a0 = rev_ptr[j], a1 = rev_ptr[j + 1];
-                a0 = a0 < 0 ? 0 : a0;
-                a1 = a1 > ne ? (int)ne : a1;
-                const int at = ts_lower(rev_edge, a0, a1, K, i);
-                bool both = false;
-                if (at < a1) {
-                    const int e3 = rev_edge[at];
-                    both = e3 >= 0 && e3 < ne && e3 / K == i;
-                }
+            const double pe = (double)p[e2], q = attract(j, pe);
+            if (want_kl) {                                 // counted above when i -> j exists too
                 const double pj = pe * w2n;
-                if (!both && pj > 0.0) kl += pj * log(pj * Z / q);
+                if (g.opposite(j, i) < 0 && pj > 0.0) kl += pj * log(pj * Z / q);
             }
         }
         ax = wave_sum(ax);
@@ -327,7 +299,8 @@ extern "C" size_t mi_tsne_workspace_bytes(long n, int k, int n_split) {
 extern "C" int mi_tsne_gradient(const float* y, const int32_t* index, const float* p, const int32_t* rev_ptr, const int32_t* rev_edge, long n,
                                 int k, float exaggeration, int n_split, float* out_grad, float* out_z, float* out_kl, void* ws,
                                 size_t ws_bytes, mi_stream_t stream) {
-    if (!y || !index || !p || !rev_ptr || !rev_edge || !out_grad || !out_z || !ws) return MI_E_ARG;
+    const KnnGraph g{index, rev_ptr, rev_edge, (int)n, k};
+    if (!y || !g.complete() || !p || !out_grad || !out_z || !ws) return MI_E_ARG;
     const int rc = ts_check(n, k, n_split);
     if (rc != MI_OK) return rc;
     if ((uintptr_t)ws & 15) return MI_E_ARG;
@@ -342,8 +315,8 @@ extern "C" int mi_tsne_gradient(const float* y, const int32_t* index, const floa
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ts_repulsion_kernel, dim3((unsigned)pl.iblocks, (unsigned)pl.S), dim3(256), 0, st, y, (int)n, pl.jps, pl.S, part);
     hipLaunchKernelGGL(ts_merge_kernel, dim3((unsigned)pl.mblocks), dim3(256), 0, st, part, (int)n, pl.S, rep, zpart);
-    hipLaunchKernelGGL(ts_finish_kernel, dim3((unsigned)pl.fblocks), dim3(256), 0, st, y, index, p, rev_ptr, rev_edge, (int)n, k, exaggeration,
-                       rep, zpart, pl.mblocks, out_grad, out_z, klpart);
+    hipLaunchKernelGGL(ts_finish_kernel, dim3((unsigned)pl.fblocks), dim3(256), 0, st, y, g, p, exaggeration, rep, zpart, pl.mblocks,
+                       out_grad, out_z, klpart);
     if (out_kl) hipLaunchKernelGGL(ts_kl_kernel, dim3(1), dim3(256), 0, st, klpart, pl.fblocks, out_kl);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;

@@ -4,19 +4,20 @@
 //               fp32, rho = the row's smallest positive d, sigma by umap-learn's bisection in double (from 1, doubling while
 //               unbounded, <= 64 steps, |sum - log2(k + 1)| < 1e-5), floored at 1e-3 of the row's (or the table's) mean
 //               distance; w = exp(-max(0, d - rho) / sigma).
-//   union       one thread per directed edge: wsym = a + b - a b with b the weight of the opposite edge (found by binary search
-//               in the reverse list) or 0, whether that edge exists, and the edge's spacing eps = wmax / wsym in double (+inf
-//               for an edge pruned at wsym < wmax / n_epochs).
+// The graph, its transpose, the incident list of a vertex and its slot numbers: see knn_graph.h.
+//   union       one thread per directed edge: wsym = a + b - a b with b the weight of the opposite edge or 0, whether that edge
+//               exists, and the edge's spacing eps = wmax / wsym in double (+inf for an edge pruned at wsym < wmax / n_epochs).
 //   rowmax,     the label-supervised map (fit_transform(x, y=labels)): s = wsym f(labels of the two ends), m_i the
 //   supervise   largest s over the pairs of vertex i (one wave per vertex), wsup = p + q - p q with p = s / m_i, q = s / m_j (one
 //               thread per directed edge), and the spacing of wsup as the union writes it.
-//   epoch       one wave (one workgroup) per vertex.  The lanes stride over the vertex's incident pairs - its forward edges, then
-//               the reverse edges without an opposite edge - 64 at a time; the pairs that fire this epoch are listed in LDS, and
-//               the lanes then stride over (firing, term): term 0 the attraction, terms 1..5 the negatives, drawn by Philox from
+//   epoch       one wave (one workgroup) per vertex.  The lanes stride over the vertex's incident list 64 entries at a time; the
+//               pairs that fire this epoch are listed in LDS, and the lanes then stride over (firing, term): term 0 the
+//               attraction, terms 1..5 the negatives, drawn by Philox from
 //               (vertex, slot, epoch).  Every term is evaluated in double from the positions at the START of the epoch; the
 //               lanes' sums go through a fixed butterfly, and y_out = fp32(y + alpha acc) is the only rounding to fp32.
 // No floating-point atomics, no order that depends on timing: the same inputs give the same bytes.
 #include "common.h"
+#include "knn_graph.h"
 #include "philox.h"
 #include "../../include/cetpick_hip.h"
 
@@ -71,48 +72,35 @@ __global__ __launch_bounds__(256) void um_smooth_kernel(const float* dist2, long
     }
 }
 
-// the number of entries of the ascending list e[lo, hi) whose source row (edge id / k) is below src
-__device__ __forceinline__ int um_lower(const int* e, int lo, int hi, int k, int src) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e[mid] / k < src) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+// the spacing in epochs of an edge of weight ws (+inf: pruned, it never fires), wmax the largest weight of the graph
+__device__ __forceinline__ double um_spacing(float ws, float wmax, int n_epochs) {
+    const double wm = (double)wmax, v = (double)ws;
+    return (!(v > 0.0) || v < wm / (double)n_epochs) ? (double)INFINITY : wm / v;
 }
 
 // ---- union -----------------------------------------------------------------------------------------------------------------
-// An edge that points outside [0, n) or at its own row gets wsym 0, mutual 0 and (with wmax) eps +inf: it never fires.
-__global__ __launch_bounds__(256) void um_union_kernel(const int* index, const float* w, const int* rev_ptr, const int* rev_edge, int n,
-                                                       int k, const float* wmax, int n_epochs, float* out_wsym, uint8_t* out_mutual,
-                                                       double* out_eps) {
-    const long ne = (long)n * k;
+// An edge the graph passes over gets wsym 0, mutual 0 and (with wmax) eps +inf.
+__global__ __launch_bounds__(256) void um_union_kernel(KnnGraph g, const float* w, const float* wmax, int n_epochs, float* out_wsym,
+                                                       uint8_t* out_mutual, double* out_eps) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ne) return;
-    const int i = (int)(e / k), j = index[e];
+    if (e >= g.ne()) return;
+    const int i = (int)(e / g.k);
+    int j;
     float ws = 0.f;
     uint8_t mu = 0;
-    if (j >= 0 && j < n && j != i) {
+    if (g.forward(i, e, j)) {
         const double a = (double)w[e];
         double b = 0.0;
-        int r0 = rev_ptr[i], r1 = rev_ptr[i + 1];          // the edges that end in i: is one of them j -> i?
-        r0 = r0 < 0 ? 0 : r0;
-        r1 = r1 > ne ? (int)ne : r1;
-        const int at = um_lower(rev_edge, r0, r1, k, j);
-        if (at < r1) {
-            const int e2 = rev_edge[at];
-            if (e2 >= 0 && e2 < ne && e2 / k == j) {
-                mu = 1;
-                b = (double)w[e2];
-            }
+        const int e2 = g.opposite(i, j);
+        if (e2 >= 0) {
+            mu = 1;
+            b = (double)w[e2];
         }
         ws = (float)(a + b - a * b);
     }
     out_wsym[e] = ws;
     out_mutual[e] = mu;
-    if (wmax) {
-        const double wm = (double)wmax[0], v = (double)ws;
-        out_eps[e] = (!(v > 0.0) || v < wm / (double)n_epochs) ? (double)INFINITY : wm / v;
-    }
+    if (wmax) out_eps[e] = um_spacing(ws, wmax[0], n_epochs);
 }
 
 // ---- label supervision -----------------------------------------------------------------------------------------------------
@@ -121,54 +109,48 @@ __device__ __forceinline__ double um_factor(int la, int lb, double f_far, double
     return (la < 0 || lb < 0) ? f_unknown : (la != lb ? f_far : 1.0);
 }
 
-// m_i = the largest wsym f over the pairs of vertex i: its k forward edges, then every edge of its reverse list (a mutual pair
+// m_i = the largest wsym f over the pairs of vertex i: its k forward edges, then every edge of its reverse range (a mutual pair
 // is met twice with the same value).  One wave per vertex; a maximum does not depend on the order.
-__global__ __launch_bounds__(256) void um_rowmax_kernel(const int* index, const float* wsym, const int* label, const int* rev_ptr,
-                                                        const int* rev_edge, int n, int k, double f_far, double f_unknown,
+__global__ __launch_bounds__(256) void um_rowmax_kernel(KnnGraph g, const float* wsym, const int* label, double f_far, double f_unknown,
                                                         double* out_m) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= n) return;                                  // (wave-uniform)
-    const long ne = (long)n * k;
+    if (row >= g.n) return;                                // (wave-uniform)
     const int i = (int)row, li = label[i];
     double m = 0.0;
-    for (int c = lane; c < k; c += 64) {
-        const size_t e = (size_t)i * k + c;
-        const int j = index[e];
-        if (j >= 0 && j < n && j != i) m = fmax(m, (double)wsym[e] * um_factor(li, label[j], f_far, f_unknown));
+    int j, e2;
+    for (int c = lane; c < g.k; c += 64) {
+        const long e = (long)i * g.k + c;
+        if (g.forward(i, e, j)) m = fmax(m, (double)wsym[e] * um_factor(li, label[j], f_far, f_unknown));
     }
-    int r0 = rev_ptr[i], r1 = rev_ptr[i + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > ne ? (int)ne : r1;
-    for (long r = (long)r0 + lane; r < r1; r += 64) {
-        const int e2 = rev_edge[r];
-        if (e2 >= 0 && e2 < ne && e2 / k != i) m = fmax(m, (double)wsym[e2] * um_factor(label[e2 / k], li, f_far, f_unknown));
+    const KnnGraph::Range rr = g.rev_range(i);
+    for (long r = (long)rr.r0 + lane; r < rr.r1; r += 64) {
+        if (!g.reverse(r, e2)) continue;
+        j = g.source(e2);
+        if (j != i) m = fmax(m, (double)wsym[e2] * um_factor(label[j], li, f_far, f_unknown));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
     if (lane == 0) out_m[i] = m;
 }
 
-// An edge that points outside [0, n) or at its own row gets wsup 0 and (with wmax) eps +inf, as in the union.
-__global__ __launch_bounds__(256) void um_supervise_kernel(const int* index, const float* wsym, const int* label, const double* rowmax,
-                                                           int n, int k, double f_far, double f_unknown, const float* wmax, int n_epochs,
+// An edge the graph passes over gets wsup 0 and (with wmax) eps +inf, as in the union.
+__global__ __launch_bounds__(256) void um_supervise_kernel(KnnGraph g, const float* wsym, const int* label, const double* rowmax,
+                                                           double f_far, double f_unknown, const float* wmax, int n_epochs,
                                                            float* out_wsup, double* out_eps) {
-    const long ne = (long)n * k;
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ne) return;
-    const int i = (int)(e / k), j = index[e];
+    if (e >= g.ne()) return;
+    const int i = (int)(e / g.k);
+    int j;
     float ws = 0.f;
-    if (j >= 0 && j < n && j != i) {
+    if (g.forward(i, e, j)) {
         const double s = (double)wsym[e] * um_factor(label[i], label[j], f_far, f_unknown);
         const double mi = rowmax[i], mj = rowmax[j];
         const double p = s / (mi > 0.0 ? mi : 1.0), q = s / (mj > 0.0 ? mj : 1.0);
         ws = (float)(p + q - p * q);
     }
     out_wsup[e] = ws;
-    if (wmax) {
-        const double wm = (double)wmax[0], v = (double)ws;
-        out_eps[e] = (!(v > 0.0) || v < wm / (double)n_epochs) ? (double)INFINITY : wm / v;
-    }
+    if (wmax) out_eps[e] = um_spacing(ws, wmax[0], n_epochs);
 }
 
 // ---- epoch -----------------------------------------------------------------------------------------------------------------
@@ -212,56 +194,23 @@ __device__ __forceinline__ void um_terms(const UmPair* list, int nf, int lane, c
     }
 }
 
-// One wave = one workgroup per vertex, so the barriers around the LDS list are wave-wide.  Every loop bound below is the same
-// in all 64 lanes.
-__global__ __launch_bounds__(64) void um_epoch_kernel(const float* __restrict__ y, float* __restrict__ y_out, const int* index,
-                                                      const int* rev_ptr, const int* rev_edge, const uint8_t* mutual, const double* eps,
-                                                      int n, int k, int epoch, int n_epochs, double a, double b, uint32_t k0,
-                                                      uint32_t k1) {
+// One wave = one workgroup per vertex, so the barriers around the LDS list are wave-wide.  Per batch of the incident list the
+// entries that fire this epoch are listed in LDS, then the lanes stride over their terms.
+__global__ __launch_bounds__(64) void um_epoch_kernel(const float* __restrict__ y, float* __restrict__ y_out, KnnEpochGraph g, int epoch,
+                                                      int n_epochs, double a, double b, uint32_t k0, uint32_t k1) {
     __shared__ UmPair list[64];
     const int lane = threadIdx.x, i = blockIdx.x;
-    const long ne = (long)n * k;
     const double xi = (double)y[2 * (size_t)i], yi = (double)y[2 * (size_t)i + 1], en = (double)epoch;
     const unsigned long long below_me = (1ull << lane) - 1ull;
     double ax = 0.0, ay = 0.0;
-    for (int c0 = 0; c0 < k; c0 += 64) {                   // forward edges: slot = column
-        const int c = c0 + lane;
-        bool fire = false;
-        int j = 0;
-        if (c < k) {
-            const size_t e = (size_t)i * k + c;
-            j = index[e];
-            fire = j >= 0 && j < n && j != i && um_fires(eps[e], en);
-        }
+    g.for_incident(i, lane, [&](const KnnEpochGraph::Entry& t) __attribute__((always_inline)) {
+        const bool fire = t.has && um_fires(g.eps[t.e], en);
         const unsigned long long mask = __ballot(fire);
-        if (fire) list[__popcll(mask & below_me)] = UmPair{j, c};
+        if (fire) list[__popcll(mask & below_me)] = UmPair{t.j, t.slot};
         __syncthreads();
-        um_terms(list, __popcll(mask), lane, y, i, n, epoch, xi, yi, a, b, k0, k1, ax, ay);
+        um_terms(list, __popcll(mask), lane, y, i, g.n, epoch, xi, yi, a, b, k0, k1, ax, ay);
         __syncthreads();
-    }
-    int r0 = rev_ptr[i], r1 = rev_ptr[i + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > ne ? (int)ne : r1;
-    int slot0 = k;                                         // reverse edges without an opposite edge: slots k, k + 1, ... in list order
-    for (int rb = r0; rb < r1; rb += 64) {
-        const int r = rb + lane;
-        bool mine = false, fire = false;
-        int j = 0;
-        if (r < r1) {
-            const int e2 = rev_edge[r];
-            if (e2 >= 0 && e2 < ne && !mutual[e2]) {
-                mine = true;
-                j = e2 / k;
-                fire = j != i && um_fires(eps[e2], en);
-            }
-        }
-        const unsigned long long mm = __ballot(mine), mask = __ballot(fire);
-        if (fire) list[__popcll(mask & below_me)] = UmPair{j, slot0 + (int)__popcll(mm & below_me)};
-        slot0 += __popcll(mm);
-        __syncthreads();
-        um_terms(list, __popcll(mask), lane, y, i, n, epoch, xi, yi, a, b, k0, k1, ax, ay);
-        __syncthreads();
-    }
+    });
     ax = wave_sum(ax);
     ay = wave_sum(ay);
     if (lane == 0) {
@@ -288,12 +237,13 @@ extern "C" int mi_umap_smooth_knn(const float* dist2, long n, int k, double mean
 
 extern "C" int mi_umap_union(const int32_t* index, const float* w, const int32_t* rev_ptr, const int32_t* rev_edge, long n, int k,
                              const float* wmax, int n_epochs, float* out_wsym, uint8_t* out_mutual, double* out_eps, mi_stream_t stream) {
-    if (!index || !w || !rev_ptr || !rev_edge || !out_wsym || !out_mutual || (wmax && !out_eps)) return MI_E_ARG;
+    const KnnGraph g{index, rev_ptr, rev_edge, (int)n, k};
+    if (!g.complete() || !w || !out_wsym || !out_mutual || (wmax && !out_eps)) return MI_E_ARG;
     const int rc = um_check(n, k);
     if (rc != MI_OK) return rc;
     if (n_epochs < 1) return MI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(um_union_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream, index, w, rev_ptr, rev_edge,
-                       (int)n, k, wmax, n_epochs, out_wsym, out_mutual, out_eps);
+    hipLaunchKernelGGL(um_union_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, w, wmax, n_epochs, out_wsym,
+                       out_mutual, out_eps);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
@@ -301,11 +251,12 @@ extern "C" int mi_umap_union(const int32_t* index, const float* w, const int32_t
 extern "C" int mi_umap_rowmax(const int32_t* index, const float* wsym, const int32_t* label, const int32_t* rev_ptr,
                               const int32_t* rev_edge, long n, int k, double f_far, double f_unknown, double* out_rowmax,
                               mi_stream_t stream) {
-    if (!index || !wsym || !label || !rev_ptr || !rev_edge || !out_rowmax) return MI_E_ARG;
+    const KnnGraph g{index, rev_ptr, rev_edge, (int)n, k};
+    if (!g.complete() || !wsym || !label || !out_rowmax) return MI_E_ARG;
     const int rc = um_check(n, k);
     if (rc != MI_OK) return rc;
-    hipLaunchKernelGGL(um_rowmax_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, index, wsym, label, rev_ptr,
-                       rev_edge, (int)n, k, f_far, f_unknown, out_rowmax);
+    hipLaunchKernelGGL(um_rowmax_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, wsym, label, f_far, f_unknown,
+                       out_rowmax);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
@@ -317,8 +268,8 @@ extern "C" int mi_umap_supervise(const int32_t* index, const float* wsym, const 
     const int rc = um_check(n, k);
     if (rc != MI_OK) return rc;
     if (n_epochs < 1) return MI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(um_supervise_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream, index, wsym, label,
-                       rowmax, (int)n, k, f_far, f_unknown, wmax, n_epochs, out_wsup, out_eps);
+    hipLaunchKernelGGL(um_supervise_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       KnnGraph{index, nullptr, nullptr, (int)n, k}, wsym, label, rowmax, f_far, f_unknown, wmax, n_epochs, out_wsup, out_eps);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }
@@ -326,12 +277,13 @@ extern "C" int mi_umap_supervise(const int32_t* index, const float* wsym, const 
 extern "C" int mi_umap_epoch(const float* y_in, float* y_out, const int32_t* index, const int32_t* rev_ptr, const int32_t* rev_edge,
                              const uint8_t* mutual, const double* eps, long n, int k, int epoch, int n_epochs, double a, double b,
                              uint64_t seed, mi_stream_t stream) {
-    if (!y_in || !y_out || y_in == y_out || !index || !rev_ptr || !rev_edge || !mutual || !eps) return MI_E_ARG;
+    const KnnEpochGraph g{{index, rev_ptr, rev_edge, (int)n, k}, mutual, eps};
+    if (!y_in || !y_out || y_in == y_out || !g.complete()) return MI_E_ARG;
     const int rc = um_check(n, k);
     if (rc != MI_OK) return rc;
     if (n_epochs < 1 || epoch < 1 || epoch > n_epochs) return MI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(um_epoch_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, y_in, y_out, index, rev_ptr, rev_edge, mutual, eps,
-                       (int)n, k, epoch, n_epochs, a, b, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32));
+    hipLaunchKernelGGL(um_epoch_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, y_in, y_out, g, epoch, n_epochs, a, b,
+                       (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32));
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }

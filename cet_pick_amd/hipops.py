@@ -2558,13 +2558,33 @@ def knn_search(q, x, k, metric="ip", exclude_self=False, n_split=0, out=None):
     return index, value
 
 
-# ---- t-SNE over the neighbour graph (csrc/tsne.hip) ------------------------------------------------------------------------
+# ---- the neighbour graph of the t-SNE, UMAP and spectral kernels (csrc/knn_graph.h) ----------------------------------------
 
-def _ts_table(t, name, shape, dtype=torch.float32):
+def _table(t, name, shape, dtype=torch.float32):
     L.require_cuda(t, name, dtype)
     if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise L.HipExtensionError("%s must be a contiguous %s tensor, got %s" % (name, tuple(shape), tuple(t.shape)))
     return t
+
+
+def _graph_tables(index, rev_ptr=None, rev_edge=None, n=None, transpose=True, **tables):
+    """(N, k) of the graph index (N, k) int32 (N = n where given), after checking it, its transpose (rev_ptr (N + 1,), rev_edge
+    (N k,) int32: utils/graph.reverse_graph; transpose=False for an entry that takes none), and the per-edge tables (N, k),
+    each passed as name=(tensor, dtype)."""
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2 or (n is not None and index.shape[0] != n):
+        raise L.HipExtensionError("index must be (N, k)%s, got %s" % ("" if n is None else " with N = %d" % n, tuple(index.shape)))
+    n, k = index.shape
+    _table(index, "index", (n, k), torch.int32)
+    for name, (t, dtype) in tables.items():
+        _table(t, name, (n, k), dtype)
+    if transpose:
+        _table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
+        _table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    return n, k
+
+
+# ---- t-SNE over the neighbour graph (csrc/tsne.hip) ------------------------------------------------------------------------
 
 
 def tsne_affinities(dist, perplexity):
@@ -2588,28 +2608,22 @@ def tsne_workspace(n, k, n_split, device):
 
 def tsne_gradient(y, index, p, rev_ptr, rev_edge, exaggeration=1.0, n_split=0, kl=True, out=None, ws=None):
     """(grad (N, 2) fp32, z (1,) fp32, kl (1,) fp32 or None): the exact t-SNE gradient of y (N, 2) for the graph index (N, K)
-    int32 with conditional affinities p (N, K) and its transpose (rev_ptr, rev_edge: utils/tsne.reverse_graph); z = the sum
+    int32 with conditional affinities p (N, K) and its transpose (rev_ptr, rev_edge: utils/graph.reverse_graph); z = the sum
     of q over i != j; kl (kl=True) the divergence without the exaggeration.  n_split: parts of the all-pairs sum (0: from N)."""
     y = _km_x(y, "y")
     n = y.shape[0]
     if y.shape[1] != 2:
         raise L.HipExtensionError("y must be (N, 2), got %s" % (tuple(y.shape),))
-    L.require_cuda(index, "index", torch.int32)
-    if index.dim() != 2 or index.shape[0] != n:
-        raise L.HipExtensionError("index must be (N, K) with N = %d, got %s" % (n, tuple(index.shape)))
-    k, n_split = index.shape[1], int(n_split)
-    _ts_table(index, "index", (n, k), torch.int32)
-    _ts_table(p, "p", (n, k))
-    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
-    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, n=n, p=(p, torch.float32))
+    n_split = int(n_split)
     if ws is None:
         ws = tsne_workspace(n, k, n_split, y.device)
     if out is None:
         out = (torch.empty(n, 2, dtype=torch.float32, device=y.device), torch.empty(1, dtype=torch.float32, device=y.device),
                torch.empty(1, dtype=torch.float32, device=y.device) if kl else None)
-    grad, z, klt = _ts_table(out[0], "out[0]", (n, 2)), _ts_table(out[1], "out[1]", (1,)), out[2] if kl else None
+    grad, z, klt = _table(out[0], "out[0]", (n, 2)), _table(out[1], "out[1]", (1,)), out[2] if kl else None
     if klt is not None:
-        _ts_table(klt, "out[2]", (1,))
+        _table(klt, "out[2]", (1,))
     L.check(L.lib().mi_tsne_gradient(L.ptr(y), L.ptr(index), L.ptr(p), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, float(exaggeration),
                                      n_split, L.ptr(grad), L.ptr(z), L.ptr(klt), L.ptr(ws), ws.numel(), L.stream()),
             "mi_tsne_gradient(N=%d, K=%d, n_split=%d)" % (n, k, n_split))
@@ -2620,7 +2634,7 @@ def tsne_update(y, grad, velocity, gains, momentum, lr, min_gain=0.01):
     """sklearn's gradient-descent step with gains, in place on y, velocity and gains (all (N, 2) fp32)."""
     y = _km_x(y, "y")
     for t, name in ((grad, "grad"), (velocity, "velocity"), (gains, "gains")):
-        _ts_table(t, name, tuple(y.shape))
+        _table(t, name, tuple(y.shape))
     if y.shape[1] != 2:
         raise L.HipExtensionError("y must be (N, 2), got %s" % (tuple(y.shape),))
     L.check(L.lib().mi_tsne_update(L.ptr(y), L.ptr(grad), L.ptr(velocity), L.ptr(gains), y.shape[0], float(momentum), float(lr),
@@ -2644,45 +2658,26 @@ def umap_smooth_knn(dist2, mean_all):
 
 def umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=None, out=None):
     """(wsym (N, k) fp32, mutual (N, k) uint8, eps (N, k) float64) of the graph index (N, k) int32 with membership weights w and
-    its transpose (utils/tsne.reverse_graph).  wmax: a (1,) fp32 device tensor holding the largest wsym; without it eps is not
+    its transpose (utils/graph.reverse_graph).  wmax: a (1,) fp32 device tensor holding the largest wsym; without it eps is not
     written (the first of the two launches: wsym, its maximum by torch, then the spacings)."""
-    L.require_cuda(index, "index", torch.int32)
-    if index.dim() != 2:
-        raise L.HipExtensionError("index must be (N, k), got %s" % (tuple(index.shape),))
-    n, k = index.shape
-    _ts_table(index, "index", (n, k), torch.int32)
-    _ts_table(w, "w", (n, k))
-    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
-    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, w=(w, torch.float32))
     if wmax is not None:
-        _ts_table(wmax, "wmax", (1,))
+        _table(wmax, "wmax", (1,))
     if out is None:
         out = (torch.empty(n, k, dtype=torch.float32, device=w.device), torch.empty(n, k, dtype=torch.uint8, device=w.device),
                torch.empty(n, k, dtype=torch.float64, device=w.device))
-    wsym, mutual, eps = _ts_table(out[0], "out[0]", (n, k)), _ts_table(out[1], "out[1]", (n, k), torch.uint8), \
-        _ts_table(out[2], "out[2]", (n, k), torch.float64)
+    wsym, mutual, eps = _table(out[0], "out[0]", (n, k)), _table(out[1], "out[1]", (n, k), torch.uint8), \
+        _table(out[2], "out[2]", (n, k), torch.float64)
     L.check(L.lib().mi_umap_union(L.ptr(index), L.ptr(w), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, L.ptr(wmax), int(n_epochs),
                                   L.ptr(wsym), L.ptr(mutual), L.ptr(eps), L.stream()), "mi_umap_union(N=%d, k=%d)" % (n, k))
     return wsym, mutual, eps
 
 
-def _um_labelled(index, wsym, label):
-    L.require_cuda(index, "index", torch.int32)
-    if index.dim() != 2:
-        raise L.HipExtensionError("index must be (N, k), got %s" % (tuple(index.shape),))
-    n, k = index.shape
-    _ts_table(index, "index", (n, k), torch.int32)
-    _ts_table(wsym, "wsym", (n, k))
-    _ts_table(label, "label", (n,), torch.int32)
-    return n, k
-
-
 def umap_rowmax(index, wsym, label, rev_ptr, rev_edge, f_far, f_unknown):
     """rowmax (N,) float64 of the label-supervised map: the largest wsym f over the pairs of every vertex (its forward edges and
     its reverse list), f = f_unknown where an end has a negative label (N,) int32, f_far where the labels differ, else 1."""
-    n, k = _um_labelled(index, wsym, label)
-    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
-    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, wsym=(wsym, torch.float32))
+    _table(label, "label", (n,), torch.int32)
     rowmax = torch.empty(n, dtype=torch.float64, device=wsym.device)
     L.check(L.lib().mi_umap_rowmax(L.ptr(index), L.ptr(wsym), L.ptr(label), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, float(f_far),
                                    float(f_unknown), L.ptr(rowmax), L.stream()), "mi_umap_rowmax(N=%d, k=%d)" % (n, k))
@@ -2693,13 +2688,14 @@ def umap_supervise(index, wsym, label, rowmax, f_far, f_unknown, n_epochs, wmax=
     """(wsup (N, k) fp32, eps (N, k) float64): umap-learn's categorical intersection and reset_local_connectivity per directed
     edge, wsup = p + q - p q with p = wsym f / rowmax_i, q = wsym f / rowmax_j, and the spacings of wsup.  wmax: a (1,) fp32
     device tensor holding the largest wsup; without it eps is not written (the two launches of umap_union)."""
-    n, k = _um_labelled(index, wsym, label)
-    _ts_table(rowmax, "rowmax", (n,), torch.float64)
+    n, k = _graph_tables(index, transpose=False, wsym=(wsym, torch.float32))
+    _table(label, "label", (n,), torch.int32)
+    _table(rowmax, "rowmax", (n,), torch.float64)
     if wmax is not None:
-        _ts_table(wmax, "wmax", (1,))
+        _table(wmax, "wmax", (1,))
     if out is None:
         out = (torch.empty(n, k, dtype=torch.float32, device=wsym.device), torch.empty(n, k, dtype=torch.float64, device=wsym.device))
-    wsup, eps = _ts_table(out[0], "out[0]", (n, k)), _ts_table(out[1], "out[1]", (n, k), torch.float64)
+    wsup, eps = _table(out[0], "out[0]", (n, k)), _table(out[1], "out[1]", (n, k), torch.float64)
     L.check(L.lib().mi_umap_supervise(L.ptr(index), L.ptr(wsym), L.ptr(label), L.ptr(rowmax), n, k, float(f_far), float(f_unknown),
                                       L.ptr(wmax), int(n_epochs), L.ptr(wsup), L.ptr(eps), L.stream()),
             "mi_umap_supervise(N=%d, k=%d)" % (n, k))
@@ -2713,18 +2709,10 @@ def umap_epoch(y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epoc
     n = y_in.shape[0]
     if y_in.shape[1] != 2:
         raise L.HipExtensionError("y_in must be (N, 2), got %s" % (tuple(y_in.shape),))
-    _ts_table(y_out, "y_out", (n, 2))
+    _table(y_out, "y_out", (n, 2))
     if y_out.data_ptr() == y_in.data_ptr():
         raise L.HipExtensionError("y_out may not alias y_in")
-    L.require_cuda(index, "index", torch.int32)
-    if index.dim() != 2 or index.shape[0] != n:
-        raise L.HipExtensionError("index must be (N, k) with N = %d, got %s" % (n, tuple(index.shape)))
-    k = index.shape[1]
-    _ts_table(index, "index", (n, k), torch.int32)
-    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
-    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
-    _ts_table(mutual, "mutual", (n, k), torch.uint8)
-    _ts_table(eps, "eps", (n, k), torch.float64)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, n=n, mutual=(mutual, torch.uint8), eps=(eps, torch.float64))
     L.check(L.lib().mi_umap_epoch(L.ptr(y_in), L.ptr(y_out), L.ptr(index), L.ptr(rev_ptr), L.ptr(rev_edge), L.ptr(mutual), L.ptr(eps),
                                   n, k, int(epoch), int(n_epochs), float(a), float(b), int(seed) & (2 ** 64 - 1), L.stream()),
             "mi_umap_epoch(N=%d, k=%d, epoch %d of %d)" % (n, k, epoch, n_epochs))
@@ -2733,25 +2721,10 @@ def umap_epoch(y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epoc
 
 # ---- the spectral start of the UMAP map (csrc/spectral.hip) ----------------------------------------------------------------
 
-def _sp_graph(index, eps, mutual, rev_ptr, rev_edge, wsym=None):
-    L.require_cuda(index, "index", torch.int32)
-    if index.dim() != 2:
-        raise L.HipExtensionError("index must be (N, k), got %s" % (tuple(index.shape),))
-    n, k = index.shape
-    _ts_table(index, "index", (n, k), torch.int32)
-    _ts_table(eps, "eps", (n, k), torch.float64)
-    _ts_table(mutual, "mutual", (n, k), torch.uint8)
-    _ts_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32)
-    _ts_table(rev_edge, "rev_edge", (n * k,), torch.int32)
-    if wsym is not None:
-        _ts_table(wsym, "wsym", (n, k))
-    return n, k
-
-
 def graph_components(index, eps, mutual, rev_ptr, rev_edge):
     """(label (N,) int32, sweeps): the smallest vertex id of every vertex's connected component in the graph the UMAP epochs walk
     (forward edges and lone reverse edges, finite eps only).  One launch per sweep; the device flag is read between launches."""
-    n, k = _sp_graph(index, eps, mutual, rev_ptr, rev_edge)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, eps=(eps, torch.float64), mutual=(mutual, torch.uint8))
     a = torch.arange(n, dtype=torch.int32, device=index.device)
     b, flag = torch.empty_like(a), torch.zeros(1, dtype=torch.int32, device=index.device)
     sweeps = 0
@@ -2767,7 +2740,8 @@ def graph_components(index, eps, mutual, rev_ptr, rev_edge):
 
 def spectral_degree(index, wsym, eps, mutual, rev_ptr, rev_edge):
     """(deg (N,), dis (N,)) float64: the sum of every vertex's incident weights and 1 / sqrt of it (0 for an isolated vertex)."""
-    n, k = _sp_graph(index, eps, mutual, rev_ptr, rev_edge, wsym)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, eps=(eps, torch.float64), mutual=(mutual, torch.uint8),
+                         wsym=(wsym, torch.float32))
     deg = torch.empty(n, dtype=torch.float64, device=index.device)
     dis = torch.empty_like(deg)
     L.check(L.lib().mi_spectral_degree(L.ptr(index), L.ptr(wsym), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k,
@@ -2777,15 +2751,16 @@ def spectral_degree(index, wsym, eps, mutual, rev_ptr, rev_edge):
 
 def spectral_spmv(index, wsym, eps, mutual, rev_ptr, rev_edge, dis, x, y=None, row0=0):
     """y = A x, A = D^-1/2 W D^-1/2 restricted to the rows [row0, row0 + len(x)); x, y float64 vectors of that range."""
-    n, k = _sp_graph(index, eps, mutual, rev_ptr, rev_edge, wsym)
-    _ts_table(dis, "dis", (n,), torch.float64)
+    n, k = _graph_tables(index, rev_ptr, rev_edge, eps=(eps, torch.float64), mutual=(mutual, torch.uint8),
+                         wsym=(wsym, torch.float32))
+    _table(dis, "dis", (n,), torch.float64)
     L.require_cuda(x, "x", torch.float64)
     if x.dim() != 1 or not x.is_contiguous():
         raise L.HipExtensionError("x must be a contiguous vector, got %s" % (tuple(x.shape),))
     nrows = x.shape[0]
     if y is None:
         y = torch.empty_like(x)
-    _ts_table(y, "y", (nrows,), torch.float64)
+    _table(y, "y", (nrows,), torch.float64)
     if y.data_ptr() == x.data_ptr():
         raise L.HipExtensionError("y may not alias x")
     L.check(L.lib().mi_spectral_spmv(L.ptr(index), L.ptr(wsym), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k,
@@ -2799,10 +2774,10 @@ def _sp_basis(Q, w, c):
     if Q.dim() != 2 or Q.stride(1) != 1 or Q.shape[0] < 1 or (Q.shape[0] > 1 and Q.stride(0) < Q.shape[1]):
         raise L.HipExtensionError("Q must be (m, n) float64 with contiguous rows, got %s" % (tuple(Q.shape),))
     m, n = Q.shape
-    _ts_table(w, "w", (n,), torch.float64)
+    _table(w, "w", (n,), torch.float64)
     if c is None:
         c = torch.empty(m, dtype=torch.float64, device=Q.device)
-    _ts_table(c, "c", (m,), torch.float64)
+    _table(c, "c", (m,), torch.float64)
     return m, n, (Q.stride(0) if m > 1 else n), c
 
 

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from .. import hipops as H
-from .tsne import reverse_graph
+from .graph import reverse_graph
 
 MAX_COMPONENTS = 256
 MAX_RESTARTS = 300

@@ -19,6 +19,7 @@ import torch
 
 from .. import _lib as L
 from .. import hipops as H
+from .graph import reverse_graph          # its home; kept importable from here
 
 PERPLEXITY_MIN, PERPLEXITY_MAX = 2, 42          # K = 3 perplexity + 1 <= 127 fits the neighbour search's k <= 128
 N_ITER_CHECK, EXPLORATION_ITER, MIN_GRAD_NORM = 50, 250, 1e-7
@@ -36,21 +37,6 @@ def check_range(n, perplexity):
                          % (PERPLEXITY_MIN, PERPLEXITY_MAX, perplexity))
     if n < perplexity + 2:
         raise ValueError("perplexity %d needs N >= perplexity + 2 = %d points, got %d" % (perplexity, perplexity + 2, n))
-
-
-def reverse_graph(index):
-    """(rev_ptr (N + 1,) int32, rev_edge (N K,) int32) of index (N, K): the ids e = i K + c of the edges whose destination
-    index[e] is row r are rev_edge[rev_ptr[r] : rev_ptr[r + 1]], in ascending order.  CPU or device tensors."""
-    n, k = index.shape
-    if n * k >= 2 ** 31:
-        raise ValueError("N K = %d edges do not fit int32 edge ids" % (n * k))
-    dest = index.reshape(-1).to(torch.int64)
-    if n * k and (int(dest.min()) < 0 or int(dest.max()) >= n):
-        raise ValueError("index holds rows outside [0, %d)" % n)
-    order = torch.sort(dest, stable=True)[1]
-    ptr = torch.zeros(n + 1, dtype=torch.int64, device=index.device)
-    ptr[1:] = torch.cumsum(torch.bincount(dest, minlength=n), 0)
-    return ptr.to(torch.int32), order.to(torch.int32)
 
 
 class TSNE:

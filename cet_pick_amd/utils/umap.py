@@ -35,7 +35,7 @@ import torch
 
 from .. import _lib as L
 from .. import hipops as H
-from .tsne import reverse_graph
+from .graph import reverse_graph
 
 N_NEIGHBORS_MIN, N_NEIGHBORS_MAX = 2, 128       # K - 1 <= 127 columns, and the neighbour search's k <= 128
 EPOCHS_SMALL, EPOCHS_LARGE, SMALL_N = 500, 200, 10000

@@ -93,21 +93,30 @@ def test_components_match_scipy(name):
         assert (want == 0).all() and sweeps >= 3
 
 
-def _strip_graph(golden, which):
-    """A strip of the fixture: its search and union on the device, the device tables, and the arbiter's dense W of them."""
-    if which not in _cache:
+def _search_graph(key, x, K):
+    """The search and union of x on the device, once per key: the device tables, and the arbiter's dense W of them."""
+    if key not in _cache:
         from cet_pick_amd import hipops as H
         from cet_pick_amd.utils.umap import UMAP
-        n, K, seed = (int(v) for v in golden("spectral_small.npz")[which])
-        x = R.strip(n, seed)[0]
         index, dist = H.knn_search(_dev(x), _dev(x), K, metric="l2", exclude_self=True)
         index, dist = index[:, :K - 1].contiguous(), dist[:, :K - 1].contiguous()
         rev_ptr, rev_edge, mutual, eps, wsym = UMAP(K).setup(index, dist, 500, with_wsym=True)
         g = (index, wsym, eps, mutual, rev_ptr, rev_edge)
         W = R.dense_w(index.cpu().numpy(), wsym.cpu().numpy(), eps.cpu().numpy())
         assert np.array_equal(W, W.T) and (R.components(W) == 0).all()
-        _cache[which] = dict(x=x, K=K, g=g, W=W, graph=(index, dist))
-    return _cache[which]
+        _cache[key] = dict(x=x, K=K, g=g, W=W, graph=(index, dist))
+    return _cache[key]
+
+
+def _strip_graph(golden, which):
+    """A strip of the fixture."""
+    n, K, seed = (int(v) for v in golden("spectral_small.npz")[which])
+    return _search_graph(which, R.strip(n, seed)[0], K)
+
+
+def _wide_graph():
+    """150 points in one blob with 70 columns: the lanes take the forward edges in a full batch of 64 and one of 6."""
+    return _search_graph("wide", T.make_blobs(150, 12, 1, seed=150)[0], 71)
 
 
 def _hub_graph():
@@ -118,11 +127,11 @@ def _hub_graph():
     return _cache["hub"]
 
 
-@pytest.mark.parametrize("which", ["small", "strip", "hub"])
+@pytest.mark.parametrize("which", ["small", "strip", "hub", "wide"])
 def test_degree_and_spmv_match_float64(golden, which):
     import torch
     from cet_pick_amd import hipops as H
-    s = _hub_graph() if which == "hub" else _strip_graph(golden, which)
+    s = _hub_graph() if which == "hub" else _wide_graph() if which == "wide" else _strip_graph(golden, which)
     g, W = s["g"], s["W"]
     n = len(W)
     deg, dis = H.spectral_degree(*g)
@@ -145,6 +154,9 @@ def test_degree_and_spmv_match_float64(golden, which):
         assert H.spectral_spmv(*g, dis, _dev(x[sl]), torch.empty_like(y), row0=row0).cpu().numpy().tobytes() == got.tobytes()
     if which == "hub":
         assert count.max() > 64 and (count == 1).any()
+    if which == "wide":
+        assert g[0].shape == (150, 70) and count.max() > 64
+        assert np.isfinite(g[2][:, 64:].cpu().numpy()).any()     # the lanes' second pass over the columns meets live edges
 
 
 @pytest.mark.parametrize("n,m", [(n, m) for n in (96, 333, 600) for m in (1, 3, 64, 65, 130) if m <= n])

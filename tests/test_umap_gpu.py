@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_EPOCHS = 500
-SHAPES = {"smallest": (17, 16), "hub": (300, 14)}          # N, K
+SHAPES = {"smallest": (17, 16), "hub": (300, 14), "wide": (150, 71)}      # N, K; wide: 70 columns, a full batch of 64 lanes and 6
 SEEDS = (42, (7 << 32) | 5)                                 # the second one reaches the key's high word
 _cache = {}
 
@@ -49,7 +49,9 @@ def _setup(name):
         from cet_pick_amd import hipops as H
         from cet_pick_amd.utils.tsne import reverse_graph
         N, K = SHAPES[name]
-        x = T.make_blobs(N, 12, 3, seed=N)[0]
+        # wide: one blob, so that the columns past the first 64 hold live edges (with three, they all lead to another blob
+        # and are pruned)
+        x = T.make_blobs(N, 12, 1 if name == "wide" else 3, seed=N)[0]
         if name == "hub":
             x[N - 1] += 100.0                                # nobody's neighbour: a vertex without reverse edges
         index, dist2 = H.knn_search(_dev(x), _dev(x), K, metric="l2", exclude_self=True)
@@ -139,6 +141,8 @@ def test_union_matches_float64(name):
     if name == "hub":
         ptr, _ = U.reverse_lists(g["index"])
         assert ptr[1] - ptr[0] > 64 and ptr[N] - ptr[N - 1] == 0 and np.isinf(want).sum() > 0
+    if name == "wide":                                       # the lanes' second pass over the columns meets live edges
+        assert k == 70 and np.isfinite(want[:, 64:]).any()
 
 
 # epoch ------------------------------------------------------------------------------------------------------------------------
@@ -148,7 +152,7 @@ def _positions(g):
     N = g["N"]
     Y = U.start(N, 3)
     i = int(np.argmax((g["eps"][:, 0] == 1.0) & (np.arange(N) > 12)))
-    group = [1, 2, 5, 9] if N < 100 else list(range(130, 160))
+    group = [1, 2, 5, 9] if N < 100 else list(range(130, min(160, N)))
     Y[group] = Y[group[0]]
     Y[g["index"][i, 0]] = Y[i]
     return Y, i, group

@@ -1,5 +1,5 @@
 """The label-supervised UMAP map on the MI355X (csrc/umap.hip: um_rowmax_kernel, um_supervise_kernel; utils/umap.py; plot_2d
---label_map) against the float64 arbiter tests/umap_sup_ref.py, on the two graphs of test_umap_gpu.py.
+--label_map) against the float64 arbiter tests/umap_sup_ref.py, on the graphs of test_umap_gpu.py.
 
 Bands.  rowmax: s = wsym f is one double product of the device's own fp32 wsym and the host's factor, and a maximum rounds
 nothing, so the device's value is the arbiter's up to the one rounding of that product, 2^-53 relative; IEEE multiplication
@@ -23,7 +23,8 @@ pytestmark = pytest.mark.gpu
 
 REPO = G.REPO
 N_EPOCHS = G.N_EPOCHS
-CASES = [("smallest", "mod3", 0.5), ("hub", "mod3", 0.5), ("hub", "distinct", 0.5), ("hub", "mod3", 1.0), ("hub", "distinct", 1.0)]
+CASES = [("smallest", "mod3", 0.5), ("hub", "mod3", 0.5), ("hub", "distinct", 0.5), ("hub", "mod3", 1.0), ("hub", "distinct", 1.0),
+         ("wide", "mod3", 0.5)]
 LISTED = ["a", "b", "far_dist", "label", "min_dist", "n_epochs", "n_neighbors", "seed", "target_weight", "y", "y01"]
 _cache = {}
 

@@ -84,7 +84,7 @@ def main():
     rev_ptr, rev_edge, mutual, eps, wsym = um.setup(index, dist, n_epochs, with_wsym=True)
     g = (index, wsym, eps, mutual, rev_ptr, rev_edge)
     live = torch.isfinite(eps)
-    r = {"kernels_sha16": source_sha16(["spectral"]), "device": torch.cuda.get_device_name(0), "N": N, "d": a_.d, "n_neighbors": K,
+    r = {"kernels_sha16": source_sha16(["spectral", "knn_graph"]), "device": torch.cuda.get_device_name(0), "N": N, "d": a_.d, "n_neighbors": K,
          "columns": k, "n_epochs": n_epochs, "incident": int(live.sum()) + int((live & (mutual == 0)).sum())}
     r["components_ms"], r["components_ms_all"] = _events_ms(lambda: H.graph_components(index, eps, mutual, rev_ptr, rev_edge))
     label, r["sweeps"] = H.graph_components(index, eps, mutual, rev_ptr, rev_edge)

@@ -75,7 +75,8 @@ def main():
     assert torch.cuda.is_available(), "a measurement needs the MI355X"
     from cet_pick_amd import hipops as H
     from cet_pick_amd.build import source_sha16
-    from cet_pick_amd.utils.tsne import n_neighbors, reverse_graph
+    from cet_pick_amd.utils.graph import reverse_graph
+    from cet_pick_amd.utils.tsne import n_neighbors
     N, P = a.n, a.perplexity
     K = n_neighbors(N, P)
     g = torch.Generator(device="cuda").manual_seed(7)
@@ -88,7 +89,7 @@ def main():
     ws = H.tsne_workspace(N, K, 0, x.device)
     grad, z, kl = H.tsne_gradient(y, index, p, rev_ptr, rev_edge, 1.0, ws=ws)
     vel, gains, y2 = torch.zeros_like(y), torch.ones_like(y), y.clone()
-    r = {"kernels_sha16": source_sha16(["tsne"]), "device": torch.cuda.get_device_name(0), "N": N, "perplexity": P, "K": K,
+    r = {"kernels_sha16": source_sha16(["tsne", "knn_graph"]), "device": torch.cuda.get_device_name(0), "N": N, "perplexity": P, "K": K,
          "torch_chunk": a.chunk, "workspace_bytes": int(ws.numel()), "f32_vector_peak_tflops": F32_VECTOR_PEAK / 1e12,
          "flop_per_pair": FLOP_PER_PAIR}
 

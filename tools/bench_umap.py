@@ -88,7 +88,7 @@ def main():
     assert torch.cuda.is_available(), "a measurement needs the MI355X"
     from cet_pick_amd import hipops as H
     from cet_pick_amd.build import source_sha16
-    from cet_pick_amd.utils.tsne import reverse_graph
+    from cet_pick_amd.utils.graph import reverse_graph
     from cet_pick_amd.utils.umap import UMAP, find_ab_params
     N, K = a_.n, a_.n_neighbors
     k = K - 1
@@ -108,7 +108,7 @@ def main():
     _, mutual, eps = H.umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=wmax, out=out)
     y = torch.from_numpy(np.random.RandomState(42).uniform(-10, 10, (N, 2)).astype(np.float32)).cuda()
     y2 = torch.empty_like(y)
-    r = {"kernels_sha16": source_sha16(["umap"]), "device": torch.cuda.get_device_name(0), "N": N, "d": a_.d, "n_neighbors": K,
+    r = {"kernels_sha16": source_sha16(["umap", "knn_graph"]), "device": torch.cuda.get_device_name(0), "N": N, "d": a_.d, "n_neighbors": K,
          "columns": k, "n_epochs": n_epochs, "a": a, "b": b, "f64_vector_peak_tflops": F64_VECTOR_PEAK / 1e12}
     r["smooth_knn_ms"], r["smooth_knn_ms_all"] = _events_ms(lambda: H.umap_smooth_knn(dist, mean_all))
     r["union_ms"], r["union_ms_all"] = _events_ms(lambda: H.umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=wmax, out=out))
