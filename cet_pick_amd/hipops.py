@@ -2448,6 +2448,11 @@ class HipZHead(nn.Module):
             self.weight.normal_(std=0.001)
 
     def forward(self, x):
+        # mi_zhead_fwd takes any C % 4 == 0, mi_zhead_bwd only a C that divides 256 (its weight-gradient block is 256 / C row groups):
+        # say so here, where the graph is built, not as a bad-argument code out of the middle of backward()
+        if 256 % self.c and torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
+            raise L.HipExtensionError("HipZHead(%d, %d) runs at inference only (under torch.no_grad()): its backward kernels take a "
+                                      "channel count that divides 256 (4, 8, ..., 256)" % (self.c, self.k_out))
         return _ZHeadFn.apply(_f32c(x, "x"), self.weight, self)
 
 
