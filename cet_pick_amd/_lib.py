@@ -240,6 +240,10 @@ SIGNATURES = {
     "mi_plot_patch_bytes": (_I, [_P, _L, _I, _I, _P, _P, _P]),
     "mi_plot_raster_workspace_bytes": (_Z, [_I]),
     "mi_plot_raster": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _PL, _I, _P, _P, _Z, _P]),
+    # slice pictures of the detector's validation, --debug 4 (csrc/debug_vis.hip)
+    "mi_dbgvis_minmax": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "mi_dbgvis_workspace_bytes": (_Z, [_I, _L, _L]),
+    "mi_dbgvis_render": (_I, [_P, _P, _P] + [_I] * 7 + [_P, _P, _L, _P, _L, _F, _I, _P, _P, _Z, _P]),
 }
 
 _lib = None

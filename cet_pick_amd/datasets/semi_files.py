@@ -11,7 +11,10 @@
     val: one sample per listed image (images without particles included): the whole tomogram and its label volume, or
         tomo[:110, 200:700, 200:700] / hm[:110, 100:350, 100:350] when D >= 100 and H > 512 (particle_moco.py:164-177)
 
-Out of scope: --pn / --ge, the unused batch keys (hm_aug, ind, gt_det, pair_*), a CPU path.
+         meta['gt_det']: the tomogram's downscaled (x, y, z) centres shifted into that window and filtered to it (`window_gt_det`;
+         the reference leaves them unshifted)
+
+Out of scope: --pn / --ge, the unused batch keys (hm_aug, ind, pair_*), a CPU path.
 """
 import math
 import os
@@ -233,6 +236,19 @@ def val_window(shape):
     return (slice(None),) * 3, (slice(None),) * 3
 
 
+def window_gt_det(centres, shape):
+    """The ground-truth centres of a val sample: `centres` (n, 3) downscaled (x, y, z) of a tomogram of extents `shape`
+    (D, H, W), shifted by the origin of `val_window`'s label window and filtered to it.  -> (m, 3) float32.  Host only."""
+    D, H, W = (int(s) for s in shape)
+    _, wl = val_window((D, H, W))
+    z0, z1, _ = wl[0].indices(D)
+    y0, y1, _ = wl[1].indices(H // 2)
+    x0, x1, _ = wl[2].indices(W // 2)
+    c = np.asarray(centres, dtype=np.int64).reshape(-1, 3)
+    keep = ((c[:, 0] >= x0) & (c[:, 0] < x1) & (c[:, 1] >= y0) & (c[:, 1] < y1) & (c[:, 2] >= z0) & (c[:, 2] < z1))
+    return (c[keep] - np.array([x0, y0, z0], dtype=np.int64)).astype(np.float32)
+
+
 def net_hm_extent(h):
     """height / width of the detector's heat-map for an input extent h: the stride-2 7x7 stem with padding 3"""
     return (h - 1) // 2 + 1
@@ -320,6 +336,7 @@ class TomoFileDetectorDataset:
                 if tuple(xl.shape) != want:
                     raise ValueError("val tomogram %s: input %s gives a %s heat-map, the label is %s (odd extents?)"
                                      % (n, tuple(xi.shape), want, tuple(xl.shape)))
+            self.gt_dets = [window_gt_det(self.anns[self.anns[:, 3] == i, :3], self.shapes[i]) for i in range(len(self.names))]
             self.num_samples = len(self.names)
         print("Loaded {} {} samples".format(split, self.num_samples))
 
@@ -343,9 +360,10 @@ class TomoFileDetectorDataset:
 
     def __iter__(self):
         if self.split != "train":
-            for n, t, hm in zip(self.names, self.tomos, self.labels):
+            for n, t, hm, gt in zip(self.names, self.tomos, self.labels, self.gt_dets):
                 wi, wl = val_window(tuple(t.shape))
-                yield {"input": t[wi].contiguous()[None], "hm": hm[wl].contiguous()[None, None], "meta": {"name": [n]}}
+                yield {"input": t[wi].contiguous()[None], "hm": hm[wl].contiguous()[None, None],
+                       "meta": {"name": [n], "gt_det": gt}}
             return
         if self._table_epoch != self.epoch:
             self.set_epoch(self.epoch)

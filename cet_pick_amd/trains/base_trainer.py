@@ -211,6 +211,9 @@ class BaseTrainer(object):
 
         if self.engine is not None and self.optimizer is not None:
             self.engine.set_lr(self._lr())                  # adjust_learning_rate acted on the optimizer
+        # base_trainer.py:532-533: debug() per validation sample, where the trainer has one and the batch names its tomogram
+        debug_on = phase != "train" and getattr(opt, "debug", 0) > 0 and type(self).debug is not BaseTrainer.debug
+        debugged = False
         for iter_id, batch in enumerate(data_loader):
             if iter_id >= num_iters:
                 break
@@ -237,6 +240,9 @@ class BaseTrainer(object):
                 for l in self.loss_stats:
                     v = loss_stats[l].detach().float().mean()
                     dev_sums[l] = v.clone() if dev_sums[l] is None else dev_sums[l] + v
+            if debug_on and batch.get("meta") and batch["meta"].get("name"):
+                self.debug(batch, output, iter_id)
+                debugged = True
             n_pending += 1
             batch_time.update(time.time() - end)
             end = time.time()
@@ -249,6 +255,8 @@ class BaseTrainer(object):
                     msg += "|Data {dt.val:.3f}s({dt.avg:.3f}s) |Net {bt.avg:.3f}s".format(dt=data_time, bt=batch_time)
                 print(msg)
         flush()
+        if debugged and hasattr(self, "debug_finish"):
+            self.debug_finish()                             # the epoch's files are on disk when val() returns
         ret = {k: v.avg for k, v in avg_loss_stats.items()}
         ret["time"] = (time.time() - t0) / 60.0
         return ret, results

@@ -2,7 +2,8 @@
 the heat-map + debiased contrastive regularisation between the two augmented views + consistency, composed from the
 HIP losses in models/loss.py.  The `--pn` (SupConLossV2_more) and `--ge` (PUGELoss) variants are outside the hot path.
 
-`TomoCRSemiTrainer` drives it through the shared `BaseTrainer` loop (two forward passes per step).
+`TomoCRSemiTrainer` drives it through the shared `BaseTrainer` loop (two forward passes per step).  Its `debug`
+(:123-186) is utils/debug_vis.py: the detection table and, under --debug 4, the slice pictures of every validation sample.
 """
 import torch
 
@@ -65,3 +66,20 @@ class TomoCRSemiTrainer(BaseTrainer):
 
     def _get_losses(self, opt):
         return ["loss", "hm_loss", "cr_loss", "consis_loss"], TomoCRSemiLoss(opt)
+
+    def debug(self, batch, output, iter_id):
+        """tomo_cr_semi_trainer.py:123-186 on the device; the files are complete after `debug_finish()`."""
+        from ..utils.debug_vis import render_validation_sample
+        render_validation_sample(self.opt, batch, output, iter_id)
+
+    def debug_finish(self):
+        from ..utils.debug_vis import finish
+        finish()
+
+    def save_result(self, output, batch, results):
+        """:189-193 `save_results`: the decoded picks (1, K, 5) in heat-map coordinates."""
+        from ..models.decode import tomo_decode
+        dets = tomo_decode(output["hm"], K=self.opt.K, if_fiber=self.opt.fiber)
+        return dets.detach().cpu().numpy().reshape(1, -1, dets.shape[2])
+
+    save_results = save_result

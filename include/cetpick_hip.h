@@ -1026,6 +1026,34 @@ int mi_plot_raster(const float* y01, long N, const int32_t* idx, long n_shown, c
                    const int32_t* labels, const uint8_t* glyphs, const mi_plot_layout* layout, int mode, uint8_t* out, void* ws,
                    size_t ws_bytes, mi_stream_t stream);
 
+/* The slice pictures of the detector's validation (`--debug 4`; reference trains/tomo_cr_semi_trainer.py:123-186 with
+ * utils/debugger.py), DESIGN.md 4.19.  Volumes are row-major, addressed with 64-bit offsets.
+ *   mi_dbgvis_minmax  vol (D, H, W) fp32, finite: out_minmax[2 i], [2 i + 1] = min, max of slice z0 + i, i < nz.  One
+ *                     workgroup per slice; nz <= 65535.
+ *   mi_dbgvis_render  tomo (D, H, W), hm_pred and hm_gt (D, h, w) fp32 with H == 2 h and W == 2 w (MI_E_ARG otherwise), minmax as
+ *                     above for the same z0, nz.  out uint8 [4][nz][H][W][3], RGB, pictures pred_hm, gt_hm, pred_out, gt_out
+ *                     of slice z = z0 + i:
+ *                       grey     float32, every operation rounded: s = 1 / (mx - mn) (0 when mx == mn), t = (v - mn) s,
+ *                                g = trunc(min(max(255 t, 0), 255)), three equal channels
+ *                       up(m)    a = trunc(min(max(255 m, 0), 255)) in float32, then the 2 x bilinear enlargement with
+ *                                half-pixel centres and replicated edges: (9 a00 + 3 a01 + 3 a10 + a11 + 8) >> 4, a00 the
+ *                                nearest source pixel, the others its neighbours toward the output pixel's side
+ *                       pred_hm  up(hm_pred), three equal channels
+ *                       gt_hm    trunc(min(max(grey (1.0 - 0.7) + up(hm_gt) 0.7, 0), 255)) in float64
+ *                       pred_out grey with, in (0, 0, 255), the ring of every pick with conf > conf_thresh and
+ *                                (int)z_pick == z, centred at ((int)x, (int)y); gt_out the same for every centre of gt_dets
+ *                                with (int)z == z.  A ring is the pixel set of the midpoint circle algorithm at `radius`
+ *                                (0..31, MI_E_UNSUPPORTED above), clipped at the picture.
+ *                     pred_dets (n_pred, 5) [x, y, z, score, conf] and gt_dets (n_gt, 3) [x, y, z] fp32 are HOST arrays in
+ *                     picture coordinates: the entry builds the ring mask and the per-slice lists of centres on the host
+ *                     and copies them into ws (mi_dbgvis_workspace_bytes(nz, n_pred, n_gt)) on the stream before the
+ *                     launch.  Rows that are not finite are ignored.  nz <= 65535. */
+int mi_dbgvis_minmax(const float* vol, int D, int H, int W, int z0, int nz, float* out_minmax, mi_stream_t stream);
+size_t mi_dbgvis_workspace_bytes(int nz, long n_pred, long n_gt);
+int mi_dbgvis_render(const float* tomo, const float* hm_pred, const float* hm_gt, int D, int H, int W, int h, int w, int z0,
+                     int nz, const float* minmax, const float* pred_dets, long n_pred, const float* gt_dets, long n_gt,
+                     float conf_thresh, int radius, uint8_t* out, void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
