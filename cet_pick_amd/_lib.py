@@ -145,6 +145,9 @@ SIGNATURES = {
     "mi_pu_focal_loss_bwd": (_I, [_P, _P, _L, _D, _P, _P, _P, _P]),
     "mi_focal_loss_fwd": (_I, [_P, _P, _L, _P, _P, _P, _Z, _P]),
     "mi_focal_loss_bwd": (_I, [_P, _P, _L, _P, _P, _P, _P]),
+    "mi_pu_ge_loss_workspace_bytes": (_Z, [_L]),
+    "mi_pu_ge_loss_fwd": (_I, [_P, _P, _L, _D, _D, _D, _P, _P, _P, _Z, _P]),
+    "mi_pu_ge_loss_bwd": (_I, [_P, _P, _L, _D, _P, _P, _P, _P]),
     "mi_mse_loss_fwd": (_I, [_P, _P, _L, _P, _P, _P, _Z, _P]),
     "mi_mse_loss_bwd": (_I, [_P, _P, _L, _P, _P, _P, _P, _P]),
     "mi_ucl_rowsums_fwd": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),

@@ -14,7 +14,8 @@
          meta['gt_det']: the tomogram's downscaled (x, y, z) centres shifted into that window and filtered to it (`window_gt_det`;
          the reference leaves them unshifted)
 
-Out of scope: --pn / --ge, the unused batch keys (hm_aug, ind, pair_*), a CPU path.
+Out of scope: --pn, the unused batch keys (hm_aug, ind, pair_*), a CPU path.  (--ge changes the loss alone,
+trains/tomo_cr_semi_trainer.py: the batches are these.)
 """
 import math
 import os
@@ -290,7 +291,7 @@ class TomoFileDetectorDataset:
             raise ValueError("--down_ratio %d: the detector's crops (6 x 64 x 64 in, 6 x 32 x 32 labels) need --down_ratio 2"
                              % int(opt.down_ratio))
         if getattr(opt, "pn", False):
-            raise NotImplementedError("--pn / --ge loss variants of the reference are outside the MI355X hot path")
+            raise NotImplementedError("--pn loss variant of the reference is outside the MI355X hot path")
 
     def _setup(self, opt, split, tomos, coords, device, rank, world):
         self.opt, self.split, self.device = opt, split, torch.device(device)

@@ -1,9 +1,10 @@
 """Detector-training losses on the MI355X: mirror of the reference's `cet_pick/models/loss.py` for the classes the
 semi-supervised trainer uses (trains/tomo_cr_semi_trainer.py:23-41): `_neg_loss` / `FocalLoss` (:378-411),
-`_pu_neg_loss` / `PULoss` (:255-324), `ConsistencyLoss` (:701-712), `UnbiasedConLoss` (:571-699).
+`_pu_neg_loss` / `PULoss` (:255-324), `_pu_ge_loss` / `PUGELoss` (:215-253, :327-337, the trainer's --ge),
+`ConsistencyLoss` (:701-712), `UnbiasedConLoss` (:571-699).
 
-The voxel losses are single fused reductions (csrc/loss_ops.hip) with hand-written backward kernels; the
-data-dependent branch of the PU risk is taken on the device.  `UnbiasedConLoss` never builds the (2N)^2 similarity
+The voxel losses are single fused reductions (csrc/loss_ops.hip, csrc/loss_ge.hip) with hand-written backward kernels; the
+data-dependent branch of the PU risk is taken on the device, and so is the count sum of the GE penalty.  `UnbiasedConLoss` never builds the (2N)^2 similarity
 matrix: an MFMA kernel streams its tiles and returns the four row sums the loss is a function of; the O(N) tail
 (clamps, logs, masked means) is ordinary tensor arithmetic on those vectors.
 """
@@ -100,6 +101,65 @@ class PULoss(nn.Module):
 
     def forward(self, pred, gt):
         return self.puloss(pred, gt, self.tau, self.beta, self.gamma)
+
+
+def _check_tau(tau):
+    if not 0.0 < float(tau) < 1.0:           # log Binom(k; N, tau) is infinite at the ends
+        raise ValueError("PUGELoss needs 0 < tau < 1, got %r" % (tau,))
+
+
+class _PUGELossFn(torch.autograd.Function):
+    """mi_pu_ge_loss_fwd / _bwd; `grad_fn.sums` is the 16-double record of include/cetpick_hip.h."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, tau, slack, entropy_penalty):
+        _check_tau(tau)
+        p, g = _flat(pred, "pred"), _flat(gt, "gt")
+        if p.numel() != g.numel():
+            raise ValueError("pred and gt differ in size: %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
+        n = p.numel()
+        if n == 0:
+            raise ValueError("voxel loss of an empty tensor: pred %s, gt %s" % (tuple(pred.shape), tuple(gt.shape)))
+        lib = L.lib()
+        ws = L.workspace(lib.mi_pu_ge_loss_workspace_bytes(n), p.device, "geloss")
+        sums = torch.empty(16, dtype=torch.float64, device=p.device)
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        L.check(lib.mi_pu_ge_loss_fwd(L.ptr(p), L.ptr(g), n, float(tau), float(slack), float(entropy_penalty), L.ptr(sums),
+                                      L.ptr(loss), L.ptr(ws), ws.numel(), L.stream()), "mi_pu_ge_loss_fwd")
+        ctx.save_for_backward(p, g, sums)
+        ctx.slack, ctx.shape_p = float(slack), pred.shape
+        ctx.sums = sums
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        p, g, sums = ctx.saved_tensors
+        dl = dloss.contiguous().float()
+        dp = torch.empty_like(p)
+        L.check(L.lib().mi_pu_ge_loss_bwd(L.ptr(p), L.ptr(g), p.numel(), ctx.slack, L.ptr(sums), L.ptr(dl), L.ptr(dp), L.stream()),
+                "mi_pu_ge_loss_bwd")
+        return dp.view(ctx.shape_p), None, None, None, None
+
+
+class PUGELoss(nn.Module):
+    """loss.py:215-253, :327-337: the generalised-expectation form of the positive-unlabeled objective - the focal loss on the
+    labelled voxels (gt >= 0) + slack x a penalty that ties the expected particle count among the unlabeled voxels (gt == -1) to a
+    Binomial(N, tau) prior (csrc/loss_ge.hip has the formula).  The classifier part is the fused focal loss: `criteria` is None or
+    a `FocalLoss` (what the trainer passes, tomo_cr_semi_trainer.py:27-29), anything else is refused.  Labels without an unlabeled
+    voxel give the focal loss alone.  With entropy_penalty > 0 and v = sum p (1 - p) = 0 over the unlabeled voxels the loss is
+    -inf, as the reference's is."""
+
+    def __init__(self, tau, criteria=None, slack=1, entropy_penalty=0):
+        super().__init__()
+        _check_tau(tau)
+        if criteria is not None and not isinstance(criteria, FocalLoss):
+            raise L.HipExtensionError("PUGELoss runs its classifier part fused with the penalty: criteria must be None or a "
+                                      "FocalLoss, got %s" % type(criteria).__name__)
+        self.tau, self.slack, self.entropy_penalty = tau, slack, entropy_penalty
+        self.criteria = criteria
+
+    def forward(self, pred, gt):
+        return _PUGELossFn.apply(pred, gt, self.tau, self.slack, self.entropy_penalty)
 
 
 class ConsistencyLoss(nn.Module):

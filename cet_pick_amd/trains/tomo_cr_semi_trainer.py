@@ -1,6 +1,7 @@
 """Mirror of the loss half of `cet_pick/trains/tomo_cr_semi_trainer.py` (`TomoCRSemiLoss` :18-112): PU focal risk on
 the heat-map + debiased contrastive regularisation between the two augmented views + consistency, composed from the
-HIP losses in models/loss.py.  The `--pn` (SupConLossV2_more) and `--ge` (PUGELoss) variants are outside the hot path.
+HIP losses in models/loss.py.  `--ge` swaps the PU risk for the GE-binomial loss (PUGELoss, csrc/loss_ge.hip); the `--pn`
+(SupConLossV2_more) variant is outside the hot path.
 
 `TomoCRSemiTrainer` drives it through the shared `BaseTrainer` loop (two forward passes per step).  Its `debug`
 (:123-186) is utils/debug_vis.py: the detection table and, under --debug 4, the slice pictures of every validation sample.
@@ -8,16 +9,16 @@ HIP losses in models/loss.py.  The `--pn` (SupConLossV2_more) and `--ge` (PUGELo
 import torch
 
 from .base_trainer import BaseTrainer
-from ..models.loss import ConsistencyLoss, FocalLoss, PULoss, UnbiasedConLoss
+from ..models.loss import ConsistencyLoss, FocalLoss, PUGELoss, PULoss, UnbiasedConLoss
 from ..models.utils import _sigmoid
 
 
 class TomoCRSemiLoss(torch.nn.Module):
     def __init__(self, opt):
         super().__init__()
-        if opt.pn or opt.ge:
-            raise NotImplementedError("--pn / --ge loss variants of the reference are outside the MI355X hot path")
-        self.crit = PULoss(opt.tau)
+        if opt.pn:
+            raise NotImplementedError("--pn loss variant of the reference is outside the MI355X hot path")
+        self.crit = PUGELoss(opt.tau, criteria=FocalLoss()) if opt.ge else PULoss(opt.tau)      # :27-31
         self.crit2 = FocalLoss()
         self.cr_loss = UnbiasedConLoss(opt.temp, opt.tau)
         self.cons_loss = ConsistencyLoss()

@@ -782,6 +782,24 @@ int mi_focal_loss_fwd(const float* pred, const float* gt, long n, double* sums, 
                       size_t ws_bytes, mi_stream_t stream);
 int mi_focal_loss_bwd(const float* pred, const float* gt, long n, const double* sums, const float* dloss,
                       float* dpred, mi_stream_t stream);
+/* `_pu_ge_loss(pred, gt, tau, FocalLoss(), slack, entropy_penalty)` loss.py:215-253 (PUGELoss :327-337, the trainer's --ge):
+ *   loss = focal(labelled voxels) + slack * pen.  With U = {gt == -1}, N = |U|, mu = sum_U p, v = sum_U p (1 - p), w = v + 1e-7,
+ *   s_k = -(mu - k)^2 / (2 w), q = softmax(s) over k = 0 .. N, b_k = log Binom(k; N, tau) (lgamma form), B = sum_k q_k b_k:
+ *   pen = -B + [entropy_penalty > 0] entropy_penalty / 2 (log v + log 2 pi + 1)            (v = 0 then gives -inf, as the reference)
+ *   g_mu = -sum_k q_k (b_k - B)(k - mu) / w,  g_v = -sum_k q_k (b_k - B)(k - mu)^2 / (2 w^2) + [..] entropy_penalty / (2 v)
+ *   d loss / d p_i = slack (g_mu + g_v (1 - 2 p_i)) on U; the focal gradient (mi_focal_loss_bwd's) on the labelled voxels.
+ * The count sum runs in double on the device over the window of counts whose term does not underflow against the largest one
+ * (a float64 softmax over all N + 1 counts adds exact zeros outside it); N, mu and v are never read on the host, nothing
+ * synchronises.  N = 0: pen = 0.  tau outside (0, 1): MI_E_ARG, nothing launched.
+ * `sums`, 16 doubles, written by the forward and read by the backward:
+ *   [0] #positive  [1] #soft  [2] N = #unlabeled  [3] sum log(p)(1-p)^2 [positive]  [4] sum log(1-p) p^2 (1-g)^4 [soft]
+ *   [5] mu  [6] v  [7] focal  [8] loss  [9] pen  [10] n  [11] B  [12] g_mu  [13] g_v  [14], [15] first and last count walked
+ * ws: mi_pu_ge_loss_workspace_bytes(n). */
+size_t mi_pu_ge_loss_workspace_bytes(long n);
+int mi_pu_ge_loss_fwd(const float* pred, const float* gt, long n, double tau, double slack, double entropy_penalty,
+                      double* sums, float* loss, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_pu_ge_loss_bwd(const float* pred, const float* gt, long n, double slack, const double* sums, const float* dloss,
+                      float* dpred, mi_stream_t stream);
 /* `ConsistencyLoss` loss.py:701-712: mean((a-b)^2); db may be NULL. */
 int mi_mse_loss_fwd(const float* a, const float* b, long n, double* sums, float* loss, void* ws,
                     size_t ws_bytes, mi_stream_t stream);
