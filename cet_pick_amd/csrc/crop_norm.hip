@@ -53,9 +53,13 @@ __global__ void u8_roundtrip_normalize_kernel(const float* __restrict__ x, float
 
 // window start along an axis: the reference slices [c - s//2, c - s//2 + s) (z windows are odd:
 // c - s//2 .. c + s//2, xy windows even: c - s/2 .. c + s/2 - 1)
+constexpr size_t CROP_STATIC_LDS = sizeof(float[2][4]) + sizeof(double[2][4]);      // crop_body's `red` and `rsum`, beside
+                                                                                    // the dynamic plane of SUMZ
 __device__ __forceinline__ void crop_body(const float* __restrict__ vol, int D, int H, int W, int c_x, int c_y, int c_z,
                                           int cz, int cy, int cx, int mode, int flip_x, float* __restrict__ out) {
-    __shared__ float red[2][4];
+    __shared__ float red[2][4];                    // SUMZ: min, max of each wave
+    __shared__ double rsum[2][4];                  // ZNORM: sum, sum of squares of each wave
+    static_assert(sizeof(red) + sizeof(rsum) == CROP_STATIC_LDS, "the launch guards count these arrays");
     extern __shared__ float plane[];               // SUMZ: cy*cx floats
     const int n = blockIdx.x, tid = threadIdx.x;
     const int x0 = c_x - cx / 2, y0 = c_y - cy / 2, z0 = c_z - cz / 2;
@@ -70,9 +74,8 @@ __device__ __forceinline__ void crop_body(const float* __restrict__ vol, int D, 
         for (int i = tid; i < vox; i += 256) o[i] = at(i / pix, (i / cx) % cy, i % cx);
         return;
     }
-    float a = 0.f, b = 0.f;                        // SUMZ: min, max ; ZNORM: sum, sumsq
     if (mode == CROP_SUMZ_MINMAX) {
-        a = INFINITY; b = -INFINITY;
+        float a = INFINITY, b = -INFINITY;
         for (int i = tid; i < pix; i += 256) {
             float s = 0.f;
             for (int z = 0; z < cz; ++z) s += at(z, i / cx, i % cx);
@@ -80,11 +83,15 @@ __device__ __forceinline__ void crop_body(const float* __restrict__ vol, int D, 
             a = fminf(a, s); b = fmaxf(b, s);
         }
         a = -wave_max(-a); b = wave_max(b);
+        if ((tid & 63) == 0) { red[0][tid >> 6] = a; red[1][tid >> 6] = b; }
     } else {
-        for (int i = tid; i < vox; i += 256) { float v = at(i / pix, (i / cx) % cy, i % cx); a += v; b = fmaf(v, v, b); }
-        a = wave_sum(a); b = wave_sum(b);
+        // sums in double, as crop_fast_body's: in float32 the sum of squares of a crop with mean 100 and sigma 7 loses the
+        // variance's last digits, and ss - vox * mean^2 below cancels the leading ones
+        double s = 0, ss = 0;
+        for (int i = tid; i < vox; i += 256) { const float v = at(i / pix, (i / cx) % cy, i % cx); s += v; ss += (double)v * v; }
+        s = wave_sum(s); ss = wave_sum(ss);
+        if ((tid & 63) == 0) { rsum[0][tid >> 6] = s; rsum[1][tid >> 6] = ss; }
     }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = a; red[1][tid >> 6] = b; }
     __syncthreads();
     if (mode == CROP_SUMZ_MINMAX) {
         const float mn = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
@@ -93,8 +100,8 @@ __device__ __forceinline__ void crop_body(const float* __restrict__ vol, int D, 
         float* o = out + (long)n * pix;
         for (int i = tid; i < pix; i += 256) o[i] = (plane[i] - mn) * inv;
     } else {
-        const double s = (double)red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        const double ss = (double)red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        const double s = rsum[0][0] + rsum[0][1] + rsum[0][2] + rsum[0][3];
+        const double ss = rsum[1][0] + rsum[1][1] + rsum[1][2] + rsum[1][3];
         const double mean = s / vox;
         double var = (ss - vox * mean * mean) / (vox - 1);        // unbiased, as torch.std
         if (var < 0) var = 0;
@@ -236,7 +243,7 @@ extern "C" int mi_crop_normalize(const float* vol, int D, int H, int W, const in
         return MI_OK;
     }
     size_t lds = (mode == CROP_SUMZ_MINMAX) ? sizeof(float) * (size_t)cy * cx : 0;
-    if (lds > 64 * 1024) return MI_E_UNSUPPORTED;
+    if (lds + CROP_STATIC_LDS > 64 * 1024) return MI_E_UNSUPPORTED;
     hipLaunchKernelGGL(crop_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream, vol, D, H, W,
                        (const int*)centres_xyz, cz, cy, cx, mode, flip_x, out);
     MI_RETURN_IF_LAUNCH_FAILED();
@@ -257,7 +264,7 @@ extern "C" int mi_crop_normalize_table(const mi_vol_desc* vols, const int32_t* o
         return MI_OK;
     }
     const size_t lds = (mode == CROP_SUMZ_MINMAX) ? sizeof(float) * (size_t)cy * cx : 0;
-    if (lds > 64 * 1024) return MI_E_UNSUPPORTED;
+    if (lds + CROP_STATIC_LDS > 64 * 1024) return MI_E_UNSUPPORTED;
     hipLaunchKernelGGL(crop_table_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream, vols, (const int*)owner,
                        (const int*)centres_xyz, (const int*)shift_xyz, (const long long*)order, (long long)first, cz, cy, cx,
                        mode, flip_x, out);

@@ -81,13 +81,15 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float* x, long
     const long hi = lo + STAT_CHUNK < slice_elems ? lo + STAT_CHUNK : slice_elems;
     double s1 = 0, s2 = 0;
     float mn = INFINITY, mx = -INFINITY;
+    bool nan = false;                                             // fminf / fmaxf drop a NaN operand: remember it
     for (long i = lo + threadIdx.x; i < hi; i += 256) {
         const float v = xs[i];
         const double d = (double)v - K;
         s1 += d; s2 = fma(d, d, s2);
         mn = fminf(mn, v); mx = fmaxf(mx, v);
-        if (v != v) { mn = v; mx = v; }                           // NaN poisons min / max like numpy
+        nan |= (v != v);
     }
+    if (nan) { mn = NAN; mx = NAN; }                              // NaN poisons min / max like numpy
     __shared__ double r1[256], r2[256];
     __shared__ float rmn[256], rmx[256];
     r1[threadIdx.x] = s1; r2[threadIdx.x] = s2; rmn[threadIdx.x] = mn; rmx[threadIdx.x] = mx;
