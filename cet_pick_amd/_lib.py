@@ -247,6 +247,9 @@ SIGNATURES = {
     "mi_dbgvis_minmax": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "mi_dbgvis_workspace_bytes": (_Z, [_I, _L, _L]),
     "mi_dbgvis_render": (_I, [_P, _P, _P] + [_I] * 7 + [_P, _P, _L, _P, _L, _F, _I, _P, _P, _Z, _P]),
+    # optimal matching of picks to target centres (csrc/match.hip)
+    "mi_match_workspace_bytes": (_Z, [_I, _I, _I]),
+    "mi_match_coordinates": (_I, [_P, _P, _P, _P, _I, _D, _P, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -2817,3 +2817,45 @@ def spectral_combine(Q, c, w, beta=0.0):
     L.check(L.lib().mi_spectral_combine(L.ptr(Q), ldq, m, n, L.ptr(c), L.ptr(w), float(beta), L.stream()),
             "mi_spectral_combine(m=%d, n=%d)" % (m, n))
     return w
+
+
+# ---- optimal matching of picks to target centres (csrc/match.hip) -----------------------------------------------------------
+
+MATCH_MAX_POINTS = 4096      # picks and targets per image (mi_match_coordinates refuses more)
+
+
+def match_coordinates(preds, targets, pred_off, targ_off, radius):
+    """One launch for a whole split: preds (sumP, 3) and targets (sumT, 3) float64 on the device, image i owning the rows
+    [pred_off[i], pred_off[i + 1]) and [targ_off[i], targ_off[i + 1]) (host sequences of n_img + 1 ascending ints).
+    Returns (pred_to_target (sumP,) int32: the matched target's index inside its image or -1, dist (sumP,) float64: the matched
+    pair's distance, 0 where unmatched, total_cost (n_img,) float64) of the minimum-cost assignment under
+    cost = min(d2 - radius ** 3, 0), the reference's cube.  Raises beyond MATCH_MAX_POINTS picks or targets per image."""
+    import numpy as np
+    po = np.ascontiguousarray(np.asarray(pred_off, dtype=np.int64))
+    to = np.ascontiguousarray(np.asarray(targ_off, dtype=np.int64))
+    if po.ndim != 1 or to.ndim != 1 or len(po) != len(to) or len(po) < 1:
+        raise L.HipExtensionError("pred_off and targ_off must be two sequences of n_img + 1 offsets")
+    n_img = len(po) - 1
+    if po[0] != 0 or to[0] != 0 or (np.diff(po) < 0).any() or (np.diff(to) < 0).any() or max(po[-1], to[-1]) >= 2 ** 31:
+        raise L.HipExtensionError("offsets must start at 0, ascend and fit an int")
+    for t, name, n in ((preds, "preds", int(po[-1])), (targets, "targets", int(to[-1]))):
+        L.require_cuda(t, name, torch.float64)
+        if t.dim() != 2 or tuple(t.shape) != (n, 3) or not t.is_contiguous():
+            raise L.HipExtensionError("%s must be a contiguous (%d, 3) tensor, got %s" % (name, n, tuple(t.shape)))
+    dev = preds.device
+    p2t = torch.empty(int(po[-1]), dtype=torch.int32, device=dev)
+    dist = torch.empty(int(po[-1]), dtype=torch.float64, device=dev)
+    total = torch.empty(n_img, dtype=torch.float64, device=dev)
+    if n_img == 0:
+        return p2t, dist, total
+    max_p, max_t = int(np.diff(po).max()), int(np.diff(to).max())
+    what = "mi_match_coordinates(%d images, at most %d picks x %d targets)" % (n_img, max_p, max_t)
+    nbytes = L.lib().mi_match_workspace_bytes(n_img, max_p, max_t)
+    if nbytes == 0:
+        L.check(-3, what + ": more than %d picks or targets in one image" % MATCH_MAX_POINTS)
+    ws = L.workspace(nbytes, dev, "match")
+    po32, to32 = po.astype(np.int32), to.astype(np.int32)
+    L.check(L.lib().mi_match_coordinates(L.ptr(preds), L.ptr(targets), po32.ctypes.data_as(ctypes.c_void_p),
+                                         to32.ctypes.data_as(ctypes.c_void_p), n_img, float(radius), L.ptr(p2t), L.ptr(dist),
+                                         L.ptr(total), L.ptr(ws), ws.numel(), L.stream()), what)
+    return p2t, dist, total

@@ -1072,6 +1072,27 @@ int mi_dbgvis_render(const float* tomo, const float* hm_pred, const float* hm_gt
                      int nz, const float* minmax, const float* pred_dets, long n_pred, const float* gt_dets, long n_gt,
                      float conf_thresh, int radius, uint8_t* out, void* ws, size_t ws_bytes, mi_stream_t stream);
 
+/* Scoring the picks: the optimal matching of picks to target centres (reference evaluation/algorithms.py:6-21
+ * `match_coordinates`, there a dense float64 matrix handed to scipy.optimize.linear_sum_assignment), DESIGN.md 4.21.
+ *   mi_match_coordinates  preds (sumP, 3) and targets (sumT, 3) float64, the images of a split one after the other; image i
+ *                         owns the rows [pred_off[i], pred_off[i + 1]) and [targ_off[i], targ_off[i + 1]).  pred_off and
+ *                         targ_off (n_img + 1 each, ascending) are HOST arrays: the entry checks the sizes on the host and
+ *                         copies both tables into the workspace on the stream before the launch.
+ *                         Per image, in float64: d2[i][j] = |pred_i - target_j|^2, cost = min(d2 - radius^3, 0) (the CUBE of
+ *                         the radius is the reference's), and the result is a rectangular assignment of minimum total cost
+ *                         (shortest augmenting paths with dual variables: exact, no epsilon).  A pick counts as matched
+ *                         only where its assigned cost is < 0: pred_to_target (sumP) = the target's index inside its image,
+ *                         -1 otherwise; dist (sumP) = sqrt(d2) of the matched pair, 0 where unmatched; total_cost (n_img) =
+ *                         the sum of the matched costs.  total_cost is unique; the assignment is not where sums tie (any
+ *                         optimum may be returned, the same one for the same input).  The cost matrix is never stored.
+ *                         One workgroup per image.  At most 4096 picks and 4096 targets per image: MI_E_UNSUPPORTED above,
+ *                         returned before anything is enqueued - an input is never truncated.
+ *   mi_match_workspace_bytes  for images of at most max_P picks and max_T targets; 0 beyond the limit.  Needs no device. */
+size_t mi_match_workspace_bytes(int n_img, int max_P, int max_T);
+int mi_match_coordinates(const double* preds, const double* targets, const int* pred_off, const int* targ_off, int n_img,
+                         double radius, int* pred_to_target, double* dist, double* total_cost, void* workspace,
+                         size_t workspace_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
