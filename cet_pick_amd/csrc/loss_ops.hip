@@ -3,6 +3,7 @@
 //   _neg_loss      :378-411   CornerNet focal loss (FocalLoss)
 //   ConsistencyLoss:701-712   mean squared error between the two views' heat-maps
 //   UnbiasedConLoss:571-699   debiased contrastive regulariser over a (2N x 2N) similarity matrix
+//   SupConLossV2_more:759-818 supervised contrastive term of --pn: the same row sums + an O(N) row pass (supcon_pn_*)
 // The voxel losses are one streaming pass (fp64 partial sums, deterministic two-level tree) plus a
 // one-thread finalize that also takes the data-dependent branch of the PU risk on the device, and an
 // elementwise backward.  The contrastive loss never materialises the (2N)^2 matrix (2.4 GB at N = 12,288):
@@ -659,6 +660,166 @@ __global__ __launch_bounds__(256, (DIM == 64 || TRANS == 2) ? 2 : 3) void ucl_bw
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// supervised contrastive loss of the fully annotated trainer (--pn): SupConLossV2_more, loss.py:759-818, around the row sums above.
+// With m_i = rowmax, Z_i = s_all (the diagonal's 1 included), P2 = #pos rows, U = #un rows (cls bit 0 / bit 1), G = sum_{j pos} f_j:
+//   pos row:  t_i = [f_i.G / T - f_i.f_i / T - (P2 - 1) m_i] / P2 - log Z_i        (= sum_{j pos} log E_ij / P2 - log Z_i)
+//   un row:   t_i = f_i.f_pair(i) / T - m_i - log Z_i                              (= log E_i,pair(i) - log Z_i)
+//   loss = -sum_pos t_i / P2 - sum_un t_i / U
+// The linear terms never pass through exp / log.  All sums are doubles, two levels, with a work split that depends on n2 alone; a
+// row is owned by 16 lanes whatever the width (lane s: columns s, s + 16, ...), so zero columns on the right change no bit.
+// ------------------------------------------------------------------------------------------------
+constexpr int SPN_RP = 16;             // rows per pass of a 256-thread workgroup (16 lanes per row)
+constexpr int SPN_GB = 64;             // most first-level blocks of G: every block of the row pass adds them up again, in order
+constexpr int SPN_RB = 1024;           // most first-level blocks of the row pass
+constexpr int SPN_REC = 8 + 64;        // a G record: [0] P2, [1] U, [8 + c] G[c]
+int spn_gblocks(int n2) { return std::max(1, std::min(SPN_GB, (n2 + SPN_RP - 1) / SPN_RP)); }
+int spn_rblocks(int n2) { return std::max(1, std::min(SPN_RB, (n2 + SPN_RP - 1) / SPN_RP)); }
+
+template <int DIM>
+__global__ __launch_bounds__(256) void supcon_pn_gsum_kernel(const float* feat, const uint8_t* cls, int n2, double* gpart) {
+    constexpr int KC = DIM / 16;
+    __shared__ double red[SPN_RP][DIM];
+    __shared__ double cnt[SPN_RP][2];
+    const int sub = threadIdx.x & 15, slot = threadIdx.x >> 4;
+    double g[KC], np = 0, nu = 0;
+#pragma unroll
+    for (int k = 0; k < KC; ++k) g[k] = 0.0;
+    for (long r = (long)blockIdx.x * SPN_RP + slot; r < n2; r += (long)gridDim.x * SPN_RP) {
+        const uint8_t c = cls[r];
+        if (c & 1) {
+            np += 1.0;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) g[k] += (double)feat[r * DIM + sub + 16 * k];
+        }
+        if (c & 2) nu += 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k) red[slot][sub + 16 * k] = g[k];
+    if (sub == 0) { cnt[slot][0] = np; cnt[slot][1] = nu; }
+    __syncthreads();
+    double* rec = gpart + (long)blockIdx.x * SPN_REC;
+    if (threadIdx.x < DIM) {
+        double s = 0;
+        for (int q = 0; q < SPN_RP; ++q) s += red[q][threadIdx.x];
+        rec[8 + threadIdx.x] = s;
+    } else if (threadIdx.x < DIM + 2) {
+        const int w = threadIdx.x - DIM;
+        double s = 0;
+        for (int q = 0; q < SPN_RP; ++q) s += cnt[q][w];
+        rec[w] = s;
+    }
+}
+
+// the G records of the first level -> sg[0] = P2, sg[1] = U, sg[8 + c] = G[c] in LDS (the same additions in every workgroup)
+__device__ __forceinline__ void spn_load_g(const double* gpart, int n_gpart, int dim, double* sg) {
+    if (threadIdx.x < dim + 2) {
+        const int w = threadIdx.x < dim ? 8 + threadIdx.x : threadIdx.x - dim;
+        double s = 0;
+        for (int b = 0; b < n_gpart; ++b) s += gpart[(long)b * SPN_REC + w];
+        sg[w] = s;
+    }
+    __syncthreads();
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void supcon_pn_rows_kernel(const float* feat, const uint8_t* cls, int n2, int n_half, float inv_T,
+                                                             const float* rowmax, const float* s_all, const double* gpart,
+                                                             int n_gpart, float* g_all, double* rpart) {
+    constexpr int KC = DIM / 16;
+    __shared__ double sg[SPN_REC];
+    __shared__ double red[SPN_RP][2];
+    spn_load_g(gpart, n_gpart, DIM, sg);
+    const int sub = threadIdx.x & 15, slot = threadIdx.x >> 4;
+    const double P2 = sg[0], U = sg[1], iT = (double)inv_T;
+    double G[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) G[k] = sg[8 + sub + 16 * k];
+    double qp = 0, qu = 0;
+    for (long r = (long)blockIdx.x * SPN_RP + slot; r < n2; r += (long)gridDim.x * SPN_RP) {
+        const long pr = r < n_half ? r + n_half : r - n_half;
+        double a = 0, b = 0, c = 0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const double f = (double)feat[r * DIM + sub + 16 * k], fp = (double)feat[pr * DIM + sub + 16 * k];
+            a += f * G[k]; b += f * f; c += f * fp;
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
+        if (sub == 0) {
+            const uint8_t cc = cls[r];
+            const double m = (double)rowmax[r], Z = (double)s_all[r], lz = log(Z);
+            float w = 0.f;
+            if (cc & 1) { qp += ((a - b) * iT - (P2 - 1.0) * m) / P2 - lz; w = (float)(1.0 / (P2 * Z)); }
+            else if (cc & 2) { qu += c * iT - m - lz; w = (float)(1.0 / (U * Z)); }
+            g_all[r] = w;
+        }
+    }
+    if (sub == 0) { red[slot][0] = qp; red[slot][1] = qu; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double s = 0;
+        for (int q = 0; q < SPN_RP; ++q) s += red[q][threadIdx.x];
+        rpart[(long)blockIdx.x * 2 + threadIdx.x] = s;
+    }
+}
+
+// sums: [0] P2  [1] U  [2] sum_pos t_i  [3] sum_un t_i  [4] loss  [8 + c] G[c]
+__global__ __launch_bounds__(256) void supcon_pn_final_kernel(const double* gpart, int n_gpart, int dim, const double* rpart,
+                                                              int n_rpart, double* sums, float* loss) {
+    __shared__ double sg[SPN_REC];
+    __shared__ double red[256];
+    __shared__ double q[2];
+    spn_load_g(gpart, n_gpart, dim, sg);
+    for (int k = 0; k < 2; ++k) {
+        double s = 0;
+        for (int b = threadIdx.x; b < n_rpart; b += 256) s += rpart[(long)b * 2 + k];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) q[k] = red[0];
+        __syncthreads();
+    }
+    if (threadIdx.x < 64) sums[8 + threadIdx.x] = threadIdx.x < dim ? sg[8 + threadIdx.x] : 0.0;
+    if (threadIdx.x) return;
+    const double L = -q[0] / sg[0] - q[1] / sg[1];
+    sums[0] = sg[0]; sums[1] = sg[1]; sums[2] = q[0]; sums[3] = q[1]; sums[4] = L; sums[5] = 0; sums[6] = 0; sums[7] = 0;
+    *loss = (float)L;
+}
+
+// dfeat = dloss * (dfeat + the gradient of the two linear terms); dfeat comes in as the log Z part (ucl_bwd_kernel with g_all)
+//   pos row k: -(2 G - 2 f_k) / (T P2^2)        un row k: -2 f_pair(k) / (T U)
+template <int DIM>
+__global__ __launch_bounds__(256) void supcon_pn_rows_bwd_kernel(const float* feat, const uint8_t* cls, int n2, int n_half, float inv_T,
+                                                                 const double* sums, const float* dloss, float* dfeat) {
+    const float up = *dloss;
+    const double P2 = sums[0], U = sums[1];
+    const double cp = -2.0 * (double)inv_T / (P2 * P2), cu = -2.0 * (double)inv_T / U;
+    const long total = (long)n2 * (DIM / 4);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long r = i / (DIM / 4);
+        const int c4 = (int)(i % (DIM / 4)) * 4;
+        const uint8_t cc = cls[r];
+        float4 d = ld4(dfeat + r * DIM + c4);
+        float lin[4] = {0.f, 0.f, 0.f, 0.f};
+        if (cc & 1) {
+            const float4 f = ld4(feat + r * DIM + c4);
+            lin[0] = (float)(cp * (sums[8 + c4] - (double)f.x)); lin[1] = (float)(cp * (sums[8 + c4 + 1] - (double)f.y));
+            lin[2] = (float)(cp * (sums[8 + c4 + 2] - (double)f.z)); lin[3] = (float)(cp * (sums[8 + c4 + 3] - (double)f.w));
+        } else if (cc & 2) {
+            const long pr = r < n_half ? r + n_half : r - n_half;
+            const float4 f = ld4(feat + pr * DIM + c4);
+            lin[0] = (float)(cu * (double)f.x); lin[1] = (float)(cu * (double)f.y);
+            lin[2] = (float)(cu * (double)f.z); lin[3] = (float)(cu * (double)f.w);
+        }
+        d.x = up * (d.x + lin[0]); d.y = up * (d.y + lin[1]); d.z = up * (d.z + lin[2]); d.w = up * (d.w + lin[3]);
+        *reinterpret_cast<float4*>(dfeat + r * DIM + c4) = d;
+    }
+}
+
 }  // namespace
 
 // ---- C ABI ---------------------------------------------------------------------------------------
@@ -786,6 +947,48 @@ extern "C" int mi_ucl_rowsums_bwd_ranged(const float* feat, const uint8_t* cls, 
                        0, (const float*)range);
     hipLaunchKernelGGL((ucl_bwd_kernel<32, 2>), grid, block, 0, s, feat, cls, n2, n2 / 2, inv_T, rowmax, g_all, g_pos, g_other, g_pair, dfeat,
                        0, (const float*)range);
+    MI_RETURN_IF_LAUNCH_FAILED();
+    return MI_OK;
+}
+
+extern "C" size_t mi_supcon_pn_rows_workspace_bytes(int n2) {
+    return n2 > 0 ? sizeof(double) * ((size_t)spn_gblocks(n2) * SPN_REC + (size_t)spn_rblocks(n2) * 2) : 0;
+}
+
+extern "C" int mi_supcon_pn_rows_fwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const float* rowmax,
+                                     const float* s_all, float* g_all, double* sums, float* loss, void* ws, size_t ws_bytes,
+                                     mi_stream_t stream) {
+    if (!feat || !cls || !rowmax || !s_all || !g_all || !sums || !loss || n2 <= 0 || (n2 & 1)) return MI_E_ARG;
+    if (dim != 32 && dim != 64) return MI_E_UNSUPPORTED;
+    if (!ws || ws_bytes < mi_supcon_pn_rows_workspace_bytes(n2)) return MI_E_WORKSPACE;
+    const int gb = spn_gblocks(n2), rb = spn_rblocks(n2);
+    double* gpart = (double*)ws;
+    double* rpart = gpart + (size_t)gb * SPN_REC;
+    hipStream_t s = (hipStream_t)stream;
+    if (dim == 32) {
+        hipLaunchKernelGGL((supcon_pn_gsum_kernel<32>), dim3(gb), dim3(256), 0, s, feat, cls, n2, gpart);
+        hipLaunchKernelGGL((supcon_pn_rows_kernel<32>), dim3(rb), dim3(256), 0, s, feat, cls, n2, n2 / 2, inv_T, rowmax, s_all,
+                           (const double*)gpart, gb, g_all, rpart);
+    } else {
+        hipLaunchKernelGGL((supcon_pn_gsum_kernel<64>), dim3(gb), dim3(256), 0, s, feat, cls, n2, gpart);
+        hipLaunchKernelGGL((supcon_pn_rows_kernel<64>), dim3(rb), dim3(256), 0, s, feat, cls, n2, n2 / 2, inv_T, rowmax, s_all,
+                           (const double*)gpart, gb, g_all, rpart);
+    }
+    MI_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(supcon_pn_final_kernel, dim3(1), dim3(256), 0, s, (const double*)gpart, gb, dim, (const double*)rpart, rb, sums,
+                       loss);
+    MI_RETURN_IF_LAUNCH_FAILED();
+    return MI_OK;
+}
+
+extern "C" int mi_supcon_pn_rows_bwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const double* sums,
+                                     const float* dloss, float* dfeat, mi_stream_t stream) {
+    if (!feat || !cls || !sums || !dloss || !dfeat || n2 <= 0 || (n2 & 1)) return MI_E_ARG;
+    if (dim != 32 && dim != 64) return MI_E_UNSUPPORTED;
+    const int blocks = (int)std::max<long>(1, std::min<long>(((long)n2 * (dim / 4) + 255) / 256, 4096));
+    hipStream_t s = (hipStream_t)stream;
+    if (dim == 32) hipLaunchKernelGGL((supcon_pn_rows_bwd_kernel<32>), dim3(blocks), dim3(256), 0, s, feat, cls, n2, n2 / 2, inv_T, sums, dloss, dfeat);
+    else hipLaunchKernelGGL((supcon_pn_rows_bwd_kernel<64>), dim3(blocks), dim3(256), 0, s, feat, cls, n2, n2 / 2, inv_T, sums, dloss, dfeat);
     MI_RETURN_IF_LAUNCH_FAILED();
     return MI_OK;
 }

@@ -1,5 +1,5 @@
 """File-backed dataset of the refinement (detector) training, task 'semi' with `--dataset semi`: the reference's `TOMOMoco`
-(datasets/tomo_moco.py) + `ParticleMocoDataset` (datasets/particle_moco.py, the non `--pn` branch) on the device.
+(datasets/tomo_moco.py) + `ParticleMocoDataset` (datasets/particle_moco.py) on the device.
 
     image list (`read_image_list`) -> utils.loader.load_tomos_from_list (order, compress, gauss)
     coordinate table (`read_coord_list`: image_name, x_coord, y_coord, z_coord) -> particles downscaled to (x//2, y//2, z)
@@ -14,7 +14,11 @@
          meta['gt_det']: the tomogram's downscaled (x, y, z) centres shifted into that window and filtered to it (`window_gt_det`;
          the reference leaves them unshifted)
 
-Out of scope: --pn, the unused batch keys (hm_aug, ind, pair_*), a CPU path.  (--ge changes the loss alone,
+    --pn (fully annotated tomograms) is `TomoFileSupervisedDataset`: the training labels keep their zeros (no -1) and the partner
+        crop is a random place of the partner's tomogram or a wider neighbourhood of its annotation (`draw_pairs(pn=True)`); the
+        kernels are the same.  Each class refuses the other's option set.
+
+Out of scope: the unused batch keys (hm_aug, ind, pair_*), a CPU path.  (--ge changes the loss alone,
 trains/tomo_cr_semi_trainer.py: the batches are these.)
 """
 import math
@@ -145,8 +149,8 @@ def clip_centres(c, shapes):
                      np.clip(c[:, 2], EDGE_Z, s[:, 0] - EDGE_Z)], 1)
 
 
-def draw_pairs(anns, shapes, bbox, translation_ratio, seed, epoch, rank=0, world=1, batch_size=1, return_index=False):
-    """One epoch of training pairs for one rank (particle_moco.py:34-131, the non --pn branch).
+def draw_pairs(anns, shapes, bbox, translation_ratio, seed, epoch, rank=0, world=1, batch_size=1, return_index=False, pn=False):
+    """One epoch of training pairs for one rank (particle_moco.py:34-131).
 
     anns: (n, 4) downscaled (x, y, z, tomogram); shapes: (T, 3) tomogram extents (D, H, W).  With a Generator seeded from
     (seed, epoch), for every annotation a: own offsets x, y uniform in [-4, 4] (a z offset is drawn and, as in the reference,
@@ -154,7 +158,13 @@ def draw_pairs(anns, shapes, bbox, translation_ratio, seed, epoch, rank=0, world
     otherwise x, y in [-tp, tp), tp = int(bbox * translation_ratio), z in [-2, 2).  Both centres are clipped (`clip_centres`).
     The permutation of the annotations is split over the ranks as DistributedSampler does with drop_last, and cut to whole
     batches.  -> owner (2m,) int32, centres (2m, 3) int32 ordered [own_0, partner_0, own_1, ...], flip_prob (m // batch_size,)
-    (+ the own and partner annotation indices (m,) with return_index)"""
+    (+ the own and partner annotation indices (m,) with return_index)
+
+    pn (--pn, :55-86): the partner's centre is instead, with q = random(): q <= 0.5 -> a random place of the partner's tomogram, x
+    uniform in [0, W), y in [0, H), z in [0, D) - the FULL-resolution extents against the downscaled clip window, as in the
+    reference, so about half of these draws end on the upper clip; otherwise the partner's annotation + x, y in [-tp, tp), z in
+    [-5, 5).  Its numbers are drawn after all of the above: the own crops, the partners and the permutation are those of pn=False.
+    (return_index then also gives, per pair, whether the partner took the random-place branch)"""
     anns = np.asarray(anns, dtype=np.int64).reshape(-1, 4)
     shapes = np.asarray(shapes, dtype=np.int64).reshape(-1, 3)
     n = len(anns)
@@ -175,18 +185,27 @@ def draw_pairs(anns, shapes, bbox, translation_ratio, seed, epoch, rank=0, world
     part_z = rng.integers(-2, 2, size=n)
     part_off = np.concatenate([np.where((p <= 0.8)[:, None], near_xy, far_xy), part_z[:, None]], 1)
     own_off = np.concatenate([own_xy, np.zeros((n, 1), np.int64)], 1)
+    part_pos = anns[partner, :3] + part_off                           # unclipped partner centre of every annotation
+    if pn:
+        q = rng.random(n)
+        ext = shapes[anns[partner, 3]]                                # (D, H, W) of every annotation's partner tomogram
+        anywhere = np.stack([rng.integers(0, ext[:, 2]), rng.integers(0, ext[:, 1]), rng.integers(0, ext[:, 0])], 1)
+        near = np.concatenate([rng.integers(-tp, tp, size=(n, 2)), rng.integers(-5, 5, size=(n, 1))], 1)
+        part_pos = np.where((q <= 0.5)[:, None], anywhere, anns[partner, :3] + near)
 
     per = n // world
     count = (per // batch_size) * batch_size
     a = perm[:per * world][rank::world][:count]
     b = partner[a]
     own = clip_centres(anns[a, :3] + own_off[a], shapes[anns[a, 3]])
-    par = clip_centres(anns[b, :3] + part_off[a], shapes[anns[b, 3]])
+    par = clip_centres(part_pos[a], shapes[anns[b, 3]])
     owner = np.empty(2 * count, np.int32)
     centres = np.empty((2 * count, 3), np.int32)
     owner[0::2], owner[1::2] = anns[a, 3], anns[b, 3]
     centres[0::2], centres[1::2] = own, par
     flip = np.random.default_rng([int(seed), int(epoch), int(rank), 1]).random(count // batch_size)
+    if return_index and pn:                                           # + which partners took the random-place branch
+        return owner, centres, flip, a, b, (q <= 0.5)[a]
     return (owner, centres, flip, a, b) if return_index else (owner, centres, flip)
 
 
@@ -260,6 +279,7 @@ class TomoFileDetectorDataset:
     Tomograms and label volumes stay on the device."""
     num_classes = 1
     default_resolution = [64, 64]
+    pn = False                                  # positive-unlabeled labels and pairs; `TomoFileSupervisedDataset` is the --pn form
 
     def __init__(self, opt, split, device="cuda", rank=0, world=1):
         self._check_opt(opt, split)
@@ -283,15 +303,17 @@ class TomoFileDetectorDataset:
                     device, rank, world)
         return self
 
-    @staticmethod
-    def _check_opt(opt, split):
+    @classmethod
+    def _check_opt(cls, opt, split):
+        if bool(getattr(opt, "pn", False)) != cls.pn:
+            raise NotImplementedError("--pn %s: %s holds the %s labels and pairs; `detector_dataset(opt)` names the class for an "
+                                      "option set" % ("set" if not cls.pn else "not set", cls.__name__,
+                                                      "fully annotated" if cls.pn else "positive-unlabeled"))
         if split not in ("train", "val"):
             raise ValueError("TomoFileDetectorDataset splits are 'train' and 'val', got %r" % (split,))
         if int(opt.down_ratio) != 2:
             raise ValueError("--down_ratio %d: the detector's crops (6 x 64 x 64 in, 6 x 32 x 32 labels) need --down_ratio 2"
                              % int(opt.down_ratio))
-        if getattr(opt, "pn", False):
-            raise NotImplementedError("--pn loss variant of the reference is outside the MI355X hot path")
 
     def _setup(self, opt, split, tomos, coords, device, rank, world):
         self.opt, self.split, self.device = opt, split, torch.device(device)
@@ -311,7 +333,8 @@ class TomoFileDetectorDataset:
         for i, (n, t) in enumerate(zip(self.names, self.tomos)):
             D, H, W = self.shapes[i]
             c = downscale(coords.get(n, np.zeros((0, 3), np.int32)), compress=bool(getattr(opt, "compress", False)))
-            self.labels.append(render_labels((D, H // 2, W // 2), c, self.stencil, split == "train", self.device))
+            # (--pn: fully annotated, the training labels keep their zeros, tomo_moco.py:122-124)
+            self.labels.append(render_labels((D, H // 2, W // 2), c, self.stencil, split == "train" and not self.pn, self.device))
             anns.append(np.concatenate([c.astype(np.int64), np.full((len(c), 1), i, np.int64)], 1))
         self.anns = np.concatenate(anns, 0) if anns else np.zeros((0, 4), np.int64)
         self._table_epoch = None
@@ -347,7 +370,7 @@ class TomoFileDetectorDataset:
         if self.split != "train":
             return
         owner, centres, flip = draw_pairs(self.anns, self.shapes, self.bbox, self.translation_ratio, self.seed, epoch,
-                                          self.rank, self.world, self.batch_size)
+                                          self.rank, self.world, self.batch_size, pn=self.pn)
         check_windows(owner, centres, self.shapes)
         self.owner = torch.as_tensor(owner).to(self.device)
         self.centres = torch.as_tensor(centres).to(self.device)
@@ -374,3 +397,14 @@ class TomoFileDetectorDataset:
             inp, aug, hm = semi_pairs(self.tomo_desc, self.label_desc, len(self.tomos), self.owner, self.centres, 2 * k * B,
                                       2 * B, flip > 0.5)
             yield {"input": inp, "input_aug": aug, "hm": hm, "flip_prob": flip, "meta": {}}
+
+
+class TomoFileSupervisedDataset(TomoFileDetectorDataset):
+    """The same for fully annotated tomograms (--pn): the training labels keep their exact zeros (tomo_moco.py:122-124, no -1) and
+    the partner crops are drawn by `draw_pairs(pn=True)` (particle_moco.py:55-86).  Validation samples are the parent's."""
+    pn = True
+
+
+def detector_dataset(opt):
+    """the file-backed dataset class of an option set"""
+    return TomoFileSupervisedDataset if getattr(opt, "pn", False) else TomoFileDetectorDataset

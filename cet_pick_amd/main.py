@@ -7,8 +7,8 @@ ranks draw different crop pairs and exchange gradients over RCCL (hipops.GradExc
 (main.py:34-56).
 
 Data: with `--dataset semi` (any dataset but 'synthetic') and an image list at `--train_img_txt`, the listed tomograms and the
-coordinate table `--train_coord_txt` (datasets/semi_files.py `TomoFileDetectorDataset`: the reference's TOMOMoco +
-ParticleMocoDataset); validation then runs on `--val_img_txt` / `--val_coord_txt` (default: the train files).  Without a list,
+coordinate table `--train_coord_txt` (datasets/semi_files.py `TomoFileDetectorDataset`, under `--pn` `TomoFileSupervisedDataset`:
+the reference's TOMOMoco + ParticleMocoDataset); validation then runs on `--val_img_txt` / `--val_coord_txt` (default: the train files).  Without a list,
 or with `--dataset synthetic`, labelled synthetic tomograms (datasets/synthetic_datasets.py), same batch contract.
 """
 import os
@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from . import hipops as H
 from .datasets import tomo_files
-from .datasets.semi_files import TomoFileDetectorDataset
+from .datasets.semi_files import detector_dataset
 from .datasets.synthetic_datasets import SyntheticDetectorDataset
 from .models.model import create_model, load_model, save_model
 from .opts import opts
@@ -31,7 +31,7 @@ def main(opt):
     torch.manual_seed(opt.seed)
     rank, world = init_distributed(opt)
     files = tomo_files.use_files(opt)
-    Dataset = TomoFileDetectorDataset if files else SyntheticDetectorDataset
+    Dataset = detector_dataset(opt) if files else SyntheticDetectorDataset
     coord_path = os.path.join(opt.data_dir, opt.train_coord_txt)
     if files and not os.path.isfile(coord_path):
         raise FileNotFoundError("coordinate file %s not found: training on the listed tomograms needs --train_coord_txt"

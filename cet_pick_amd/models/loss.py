@@ -1,7 +1,7 @@
 """Detector-training losses on the MI355X: mirror of the reference's `cet_pick/models/loss.py` for the classes the
 semi-supervised trainer uses (trains/tomo_cr_semi_trainer.py:23-41): `_neg_loss` / `FocalLoss` (:378-411),
 `_pu_neg_loss` / `PULoss` (:255-324), `_pu_ge_loss` / `PUGELoss` (:215-253, :327-337, the trainer's --ge),
-`ConsistencyLoss` (:701-712), `UnbiasedConLoss` (:571-699).
+`ConsistencyLoss` (:701-712), `UnbiasedConLoss` (:571-699), `SupConLossV2_more` (:759-818, the trainer's --pn).
 
 The voxel losses are single fused reductions (csrc/loss_ops.hip, csrc/loss_ge.hip) with hand-written backward kernels; the
 data-dependent branch of the PU risk is taken on the device, and so is the count sum of the GE penalty.  `UnbiasedConLoss` never builds the (2N)^2 similarity
@@ -201,6 +201,93 @@ class _UclRowSumsFn(torch.autograd.Function):
         return dfeat, None, None
 
 
+def _pad_features(feat):
+    """(2N, dim) -> contiguous (2N, 32) or (2N, 64): the kernel widths; zero columns do not change any inner product"""
+    dim = feat.shape[1]
+    if dim not in (32, 64):
+        pad = (32 if dim < 32 else 64) - dim
+        if pad < 0:
+            raise L.HipExtensionError("feature dim %d > 64 is not supported by mi_ucl_rowsums" % dim)
+        feat = torch.nn.functional.pad(feat, (0, pad))
+    return L.require_cuda(feat, "features").contiguous()
+
+
+class _SupConPNFn(torch.autograd.Function):
+    """The scalar of `SupConLossV2_more` from (2N, 32 | 64) features and one class byte per row: mi_ucl_rowsums_fwd (m_i, Z_i), then
+    mi_supcon_pn_rows_fwd (the linear terms, log Z, the two masked means).  Backward: mi_ucl_rowsums_bwd_ranged with
+    g_all = d loss / d Z alone, then mi_supcon_pn_rows_bwd.  `grad_fn.sums` is the 72-double record of include/cetpick_hip.h."""
+
+    @staticmethod
+    def forward(ctx, feat, cls, inv_T):
+        if feat.dim() != 2 or feat.shape[0] < 2 or feat.shape[0] % 2 or feat.shape[1] not in (32, 64):
+            raise L.HipExtensionError("mi_supcon_pn_rows takes (2N, 32) or (2N, 64) features with N >= 1, got %s" % (tuple(feat.shape),))
+        L.require_cuda(feat, "features")
+        L.require_cuda(cls, "class bytes", dtype=torch.uint8)
+        if not feat.is_contiguous() or not cls.is_contiguous() or tuple(cls.shape) != (feat.shape[0],):
+            raise L.HipExtensionError("mi_supcon_pn_rows takes contiguous features %s and one contiguous class byte per row, got %s"
+                                      % (tuple(feat.shape), tuple(cls.shape)))
+        n2, dim = feat.shape
+        dev, lib = feat.device, L.lib()
+        rowmax, s_all, s_pos, s_other, e_pair, g_all = (torch.empty(n2, dtype=torch.float32, device=dev) for _ in range(6))
+        L.check(lib.mi_ucl_rowsums_fwd(L.ptr(feat), L.ptr(cls), n2, dim, float(inv_T), L.ptr(rowmax), L.ptr(s_all), L.ptr(s_pos),
+                                       L.ptr(s_other), L.ptr(e_pair), L.stream()), "mi_ucl_rowsums_fwd")
+        ws = L.workspace(lib.mi_supcon_pn_rows_workspace_bytes(n2), dev, "supconpn")
+        sums = torch.empty(72, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        L.check(lib.mi_supcon_pn_rows_fwd(L.ptr(feat), L.ptr(cls), n2, dim, float(inv_T), L.ptr(rowmax), L.ptr(s_all), L.ptr(g_all),
+                                          L.ptr(sums), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream()), "mi_supcon_pn_rows_fwd")
+        ctx.save_for_backward(feat, cls, rowmax, g_all, sums)
+        ctx.inv_T = float(inv_T)
+        ctx.sums = sums
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        feat, cls, rowmax, g_all, sums = ctx.saved_tensors
+        n2, dim = feat.shape
+        lib = L.lib()
+        dl = dloss.contiguous().float()
+        zero = torch.zeros(n2, dtype=torch.float32, device=feat.device)
+        dfeat = torch.empty_like(feat)
+        rng = torch.empty(2, dtype=torch.float32, device=feat.device)
+        L.check(lib.mi_ucl_rowsums_bwd_ranged(L.ptr(feat), L.ptr(cls), n2, dim, ctx.inv_T, L.ptr(rowmax), L.ptr(g_all), L.ptr(zero),
+                                              L.ptr(zero), L.ptr(zero), L.ptr(dfeat), L.ptr(rng), L.stream()),
+                "mi_ucl_rowsums_bwd_ranged")
+        L.check(lib.mi_supcon_pn_rows_bwd(L.ptr(feat), L.ptr(cls), n2, dim, ctx.inv_T, L.ptr(sums), L.ptr(dl), L.ptr(dfeat), L.stream()),
+                "mi_supcon_pn_rows_bwd")
+        return dfeat, None, None
+
+
+class SupConLossV2_more(nn.Module):
+    """loss.py:759-818, the contrastive term of the fully annotated trainer (--pn): ONE scalar over the 2N stacked rows,
+
+        -mean_{i pos} [sum_{j pos} log E_ij / P2 - log Z_i]  -  mean_{i un} [log E_i,pair(i) - log Z_i]
+
+    with E, Z as in `UnbiasedConLoss`, pos = label > thresh, un = label < thresh (a label equal to thresh is in neither), P2 = |pos|.
+    log E is linear in the similarities, so only Z needs the (2N)^2 walk.  The heat-map arguments are unused, as in the
+    reference.  No positive row: the package's "no positives" ValueError; no un row: a ValueError (the reference returns NaN)."""
+
+    def __init__(self, base_temperature, contrast_mode="all"):
+        super().__init__()
+        self.base_temperature = base_temperature
+        self.contrast_mode = contrast_mode
+
+    def forward(self, labels, out_labels, out_labels_cr, all_features, all_features_cr, opt):
+        labels = labels.reshape(-1)
+        all_labels = torch.cat([labels, labels], dim=0)
+        pos = all_labels.gt(opt.thresh)
+        un = all_labels.lt(opt.thresh)
+        n_pos, n_un = (int(v) for v in torch.stack([pos.sum(), un.sum()]).tolist())      # one host read, as the reference's checks
+        if n_pos == 0:
+            raise ValueError(_NO_POS)
+        if n_un == 0:
+            raise ValueError("SupConLossV2_more: no label lies below --thresh %g, the mean over the negative rows is empty"
+                             % opt.thresh)
+        feat = _pad_features(torch.cat([all_features, all_features_cr], dim=0).float())
+        cls = (pos.to(torch.uint8) | (un.to(torch.uint8) << 1)).contiguous()
+        return _SupConPNFn.apply(feat, cls, 1.0 / self.base_temperature)
+
+
 class UnbiasedConLoss(nn.Module):
     """loss.py:571-699: debiased contrastive regularisation; returns (supervised, unsupervised) terms."""
 
@@ -221,14 +308,7 @@ class UnbiasedConLoss(nn.Module):
         if num_of_positives == 0:            # the reference's host-side check (loss.py:607-608)
             raise ValueError(_NO_POS)
         num_of_negatives = 2 * (n - num_of_positives)
-        feat = torch.cat([all_features, all_features_cr], dim=0).float()
-        dim = feat.shape[1]
-        if dim not in (32, 64):              # kernel widths; zero columns do not change any inner product
-            pad = (32 if dim < 32 else 64) - dim
-            if pad < 0:
-                raise L.HipExtensionError("feature dim %d > 64 is not supported by mi_ucl_rowsums" % dim)
-            feat = torch.nn.functional.pad(feat, (0, pad))
-        feat = L.require_cuda(feat, "features").contiguous()
+        feat = _pad_features(torch.cat([all_features, all_features_cr], dim=0).float())
         all_labels = torch.cat([labels, labels], dim=0)
         all_out_preds = torch.cat([out_labels.reshape(-1), out_labels_cr.reshape(-1)], dim=0)
         pos = all_labels.gt(opt.thresh) if opt.thresh < 1 else all_labels.eq(1)

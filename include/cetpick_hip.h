@@ -821,6 +821,21 @@ int mi_ucl_rowsums_fwd(const float* feat, const uint8_t* cls, int n2, int dim, f
 int mi_ucl_rowsums_bwd_ranged(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const float* rowmax,
                               const float* g_all, const float* g_pos, const float* g_other, const float* g_pair, float* dfeat,
                               float* range, mi_stream_t stream);
+/* `SupConLossV2_more.forward` loss.py:759-818 (the trainer's --pn) around the row sums above: the O(N) part, doubles throughout.
+ * cls bit 0: pos (label > thresh), bit 1: un (label < thresh); P2 = #pos, U = #un over the n2 rows, G = sum_{j pos} feat_j,
+ * m_i = rowmax, Z_i = s_all of mi_ucl_rowsums_fwd on the same feat / cls / inv_T:
+ *   loss = -1/P2 sum_{i pos} [(f_i.G - f_i.f_i) inv_T - (P2 - 1) m_i] / P2 - log Z_i   -  1/U sum_{i un} f_i.f_pair(i) inv_T - m_i - log Z_i
+ * The forward writes loss (device float), g_all[i] = d loss / d Z_i (1 / (P2 Z_i) on pos rows, 1 / (U Z_i) on un rows, 0 elsewhere)
+ * and `sums`, 72 doubles: [0] P2  [1] U  [2] sum over pos rows  [3] sum over un rows  [4] loss  [8 + c] G[c].  P2 = 0 or U = 0: the
+ * loss is not finite (the caller checks its labels).  The backward takes dfeat = mi_ucl_rowsums_bwd_ranged(g_all, 0, 0, 0) and leaves
+ *   dfeat = *dloss (dfeat - [pos k] 2 (G - f_k) inv_T / P2^2 - [un k] 2 f_pair(k) inv_T / U).
+ * Nothing synchronises.  ws: mi_supcon_pn_rows_workspace_bytes(n2). */
+size_t mi_supcon_pn_rows_workspace_bytes(int n2);
+int mi_supcon_pn_rows_fwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const float* rowmax,
+                          const float* s_all, float* g_all, double* sums, float* loss, void* ws, size_t ws_bytes,
+                          mi_stream_t stream);
+int mi_supcon_pn_rows_bwd(const float* feat, const uint8_t* cls, int n2, int dim, float inv_T, const double* sums,
+                          const float* dloss, float* dfeat, mi_stream_t stream);
 
 /* k-means over embeddings (reference plot_2d.py: faiss.Kmeans(d, 256, niter=300)), DESIGN.md 4.9.  x (n, d) fp32 rows,
  * centroids (k, d) fp32, 1 <= d <= 512, 2 <= k <= 1024, k <= n < 2^31 (MI_E_UNSUPPORTED outside; the size entries return 0).
