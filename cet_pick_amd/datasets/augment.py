@@ -54,10 +54,9 @@ def draw_params(sample_ids, seed, epoch, view, bbox, ranges=None):
     ids = _ids(sample_ids)
     rg = ranges if ranges is not None else {STRONG: STRONG_RANGES, WEAK: WEAK_RANGES}[view]
     table = torch.empty((ids.numel(), RECORD_WORDS), dtype=torch.int32, device=ids.device)
-    L.check(L.lib().mi_aug2d_params(L.ptr(ids), ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(view), int(bbox),
-                                    float(rg["flip_p"]), float(rg["brightness"][0]), float(rg["brightness"][1]),
-                                    float(rg["contrast"][0]), float(rg["contrast"][1]), float(rg["area"][0]),
-                                    float(rg["area"][1]), L.ptr(table), L.stream()), "mi_aug2d_params")
+    L.call("mi_aug2d_params", ids, ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(view), int(bbox), float(rg["flip_p"]),
+           float(rg["brightness"][0]), float(rg["brightness"][1]), float(rg["contrast"][0]), float(rg["contrast"][1]), float(rg["area"][0]),
+           float(rg["area"][1]), table)
     return table
 
 
@@ -80,8 +79,7 @@ def apply(bank, sample_ids, table, mean, std, neighbours=False):
     if tuple(table.shape) != (B, RECORD_WORDS):
         raise L.HipExtensionError("table must be (%d, %d), got %s" % (B, RECORD_WORDS, tuple(table.shape)))
     out = torch.empty((B, 1, bbox, bbox), dtype=torch.float32, device=bank.device)
-    L.check(L.lib().mi_aug2d_apply(L.ptr(bank), n_samples, n_banks, L.ptr(ids), L.ptr(table), B, bbox, float(mean), float(std),
-                                   L.ptr(out), L.stream()), "mi_aug2d_apply")
+    L.call("mi_aug2d_apply", bank, n_samples, n_banks, ids, table, B, bbox, float(mean), float(std), out)
     return out
 
 
@@ -121,8 +119,7 @@ def draw_params_2d3d(sample_ids, seed, epoch, bbox, strong=None, weak=None):
     rs = _ranges_2d3d(STRONG_RANGES_2D3D if strong is None else strong)
     rw = _ranges_2d3d(WEAK_RANGES_2D3D if weak is None else weak)
     table = torch.empty((2, ids.numel(), RECORD_WORDS_2D3D), dtype=torch.int32, device=ids.device)
-    L.check(L.lib().mi_aug2d3d_params(L.ptr(ids), ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(bbox), rs, rw,
-                                      L.ptr(table), L.stream()), "mi_aug2d3d_params")
+    L.call("mi_aug2d3d_params", ids, ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(bbox), rs, rw, table)
     return table
 
 
@@ -153,9 +150,8 @@ def apply_2d3d(patches_2d, patches_3d, sample_ids, variants, table, means, stds)
                                   "records), got %s" % (B, RECORD_WORDS_2D3D, tuple(table.shape)))
     n_samples, n_variants, bbox = int(p2.shape[0]), int(p2.shape[1]), int(p2.shape[-1])
     out = torch.empty((4, B, 1, bbox, bbox), dtype=torch.float32, device=p2.device)
-    L.check(L.lib().mi_aug2d3d_apply(L.ptr(p2), L.ptr(p3), n_samples, n_variants, L.ptr(ids), L.ptr(variants), L.ptr(table[0]),
-                                     L.ptr(table[1]), B, bbox, float(means[0]), float(stds[0]), float(means[1]), float(stds[1]),
-                                     L.ptr(out), L.stream()), "mi_aug2d3d_apply")
+    L.call("mi_aug2d3d_apply", p2, p3, n_samples, n_variants, ids, variants, table[0], table[1], B, bbox, float(means[0]), float(stds[0]),
+           float(means[1]), float(stds[1]), out)
     return out
 
 
@@ -224,9 +220,8 @@ def _draw_3d(sample_ids, seed, epoch, view, n_views, crop, ranges):
     ids = _ids(sample_ids)
     erase_corners_3d(crop)
     table = torch.empty((n_views, ids.numel(), RECORD_WORDS_3D), dtype=torch.int32, device=ids.device)
-    L.check(L.lib().mi_aug3d_params(L.ptr(ids), ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(view), int(n_views),
-                                    int(crop), _ranges_3d(RANGES_3D if ranges is None else ranges), L.ptr(table), L.stream()),
-            "mi_aug3d_params")
+    L.call("mi_aug3d_params", ids, ids.numel(), int(seed) & (2 ** 64 - 1), int(epoch), int(view), int(n_views), int(crop),
+           _ranges_3d(RANGES_3D if ranges is None else ranges), table)
     return table
 
 
@@ -258,9 +253,7 @@ def apply_3d(crop_table, sample_ids, table, crop):
     lib = L.lib()
     # (scratch of this call alone, from the allocator of the current stream: a loader cuts on a stream of its own)
     ws = torch.empty(max(int(lib.mi_aug3d_workspace_bytes(B, V, c)), 16), dtype=torch.uint8, device=dev)
-    L.check(lib.mi_aug3d_apply(L.ptr(crop_table.desc), L.ptr(crop_table.owner), L.ptr(crop_table.centres), crop_table.n,
-                               L.ptr(ids), L.ptr(table), B, V, c, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_aug3d_apply")
+    L.call("mi_aug3d_apply", crop_table.desc, crop_table.owner, crop_table.centres, crop_table.n, ids, table, B, V, c, out, ws, ws.numel())
     return out if stacked else out[0]
 
 

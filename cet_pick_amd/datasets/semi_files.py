@@ -94,8 +94,7 @@ def render_labels(shape, centres, stencil, fill_unlabeled, device="cuda"):
     L.require_cuda(hm, "hm")
     st_d = torch.as_tensor(st).to(device)
     c_d = torch.as_tensor(c).to(device)
-    L.check(L.lib().mi_semi_labels(L.ptr(hm), D, H, W, L.ptr(c_d), len(c), L.ptr(st_d), r, int(bool(fill_unlabeled)),
-                                   L.stream()), "mi_semi_labels")
+    L.call("mi_semi_labels", hm, D, H, W, c_d, len(c), st_d, r, int(bool(fill_unlabeled)))
     return hm
 
 
@@ -241,8 +240,7 @@ def semi_pairs(tomo_desc, label_desc, n_tomos, owner, centres, first, n, flip_y,
     if first < 0 or n < 0 or first + n > int(owner.numel()) or int(centres.numel()) != 3 * int(owner.numel()):
         raise L.HipExtensionError("semi_pairs: crops [%d, %d) outside a table of %d" % (first, first + n, int(owner.numel())))
     inp, aug, hm = out
-    L.check(L.lib().mi_semi_pairs(L.ptr(tomo_desc), L.ptr(label_desc), int(n_tomos), L.ptr(owner), L.ptr(centres), int(first),
-                                  int(n), int(bool(flip_y)), L.ptr(inp), L.ptr(aug), L.ptr(hm), L.stream()), "mi_semi_pairs")
+    L.call("mi_semi_pairs", tomo_desc, label_desc, int(n_tomos), owner, centres, int(first), int(n), int(bool(flip_y)), inp, aug, hm)
     return inp, aug, hm
 
 

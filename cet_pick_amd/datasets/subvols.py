@@ -30,8 +30,7 @@ def _crop(vol, centres, size, mode, flip_x=False):
     n = c.shape[0]
     shape = (n, cy, cx) if mode == SUMZ_MINMAX else (n, cz, cy, cx)
     out = torch.empty(shape, dtype=torch.float32, device=vol.device)
-    L.check(L.lib().mi_crop_normalize(L.ptr(vol), d, h, w, L.ptr(c), n, cz, cy, cx, mode, int(bool(flip_x)),
-                                      L.ptr(out), L.stream()), "mi_crop_normalize")
+    L.call("mi_crop_normalize", vol, d, h, w, c, n, cz, cy, cx, mode, int(bool(flip_x)), out)
     return out
 
 
@@ -87,10 +86,8 @@ class CropTable:
             out = torch.empty(shape, dtype=torch.float32, device=self.desc.device)
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise L.HipExtensionError("CropTable.cut: `out` must be a contiguous float32 %s tensor" % (shape,))
-        L.check(L.lib().mi_crop_normalize_table(L.ptr(self.desc), L.ptr(self.owner), L.ptr(self.centres),
-                                                L.ptr(self.shift if shifted else None), L.ptr(order), int(first), int(n),
-                                                cz, cy, cx, int(mode), int(bool(flip_x)), L.ptr(out), L.stream()),
-                "mi_crop_normalize_table")
+        L.call("mi_crop_normalize_table", self.desc, self.owner, self.centres, self.shift if shifted else None, order, int(first), int(n),
+               cz, cy, cx, int(mode), int(bool(flip_x)), out)
         return out
 
 
@@ -127,7 +124,7 @@ def subvol_mean_std(subvols):
     lib = L.lib()
     ws = L.workspace(lib.mi_vol_stats_workspace_bytes(1, n), x.device, "stats")
     st = torch.empty(4, dtype=torch.float64, device=x.device)
-    L.check(lib.mi_vol_stats(L.ptr(x), 1, n, L.ptr(st), L.ptr(ws), ws.numel(), L.stream()), "mi_vol_stats")
+    L.call("mi_vol_stats", x, 1, n, st, ws, ws.numel())
     mean, std0 = float(st[0]), float(st[1])
     return mean, std0 * (n / (n - 1.0)) ** 0.5
 
@@ -138,8 +135,7 @@ def to_uint8_normalize(subvols, mean, std):
     L.require_cuda(subvols, "subvols")
     x = subvols.contiguous()
     y = torch.empty_like(x)
-    L.check(L.lib().mi_u8_roundtrip_normalize(L.ptr(x), L.ptr(y), x.numel(), float(mean), float(std), L.stream()),
-            "mi_u8_roundtrip_normalize")
+    L.call("mi_u8_roundtrip_normalize", x, y, x.numel(), float(mean), float(std))
     return y
 
 
@@ -228,9 +224,8 @@ class TiltStacks:
                 raise L.HipExtensionError("TiltStacks.patches: %d owners for %d centres" % (int(own.numel()), n))
         out = torch.empty((n, 1, cy, cx), dtype=torch.float32, device=dev)
         valid = torch.empty((n,), dtype=torch.uint8, device=dev)
-        L.check(L.lib().mi_tilt_patches(L.ptr(self.desc), len(self.shapes), L.ptr(own), L.ptr(c), n, cy, cx,
-                                        float(tilt_border(cx)), float(tilt_border(cy)), L.ptr(out), L.ptr(valid), L.stream()),
-                "mi_tilt_patches")
+        L.call("mi_tilt_patches", self.desc, len(self.shapes), own, c, n, cy, cx, float(tilt_border(cx)), float(tilt_border(cy)), out,
+               valid)
         return out, valid.bool()
 
 

@@ -51,7 +51,7 @@ def stamp(name):
     buf, names = STAMPS
     if len(names) >= buf.numel():
         raise L.HipExtensionError("stamp buffer full")
-    L.check(L.lib().mi_debug_stamp(buf.data_ptr() + 8 * len(names), L.stream()), "mi_debug_stamp")
+    L.call("mi_debug_stamp", buf.data_ptr() + 8 * len(names))
     names.append(STAMP_TAG + name)
 
 
@@ -343,7 +343,7 @@ def _prep_images(family, items):
                 ints([int(it[0].shape[1]) for it in items]), co, dgrad)
     else:
         args = (w, img, dgrad, co)
-    L.check(getattr(L.lib(), fn)(*args, len(items), L.stream()), fn)
+    L.call(fn, *args, len(items))
 
 
 class WeightImages:
@@ -442,7 +442,7 @@ def _smallk_image(w, owner, K, co):
     lib = L.lib()
     def cut(_):
         img = torch.empty(int(lib.mi_smallk_image_bytes(K, co)), dtype=torch.uint8, device=w.device)
-        L.check(lib.mi_smallk_prep(L.ptr(w), L.ptr(img), K, co, L.stream()), "mi_smallk_prep")
+        L.call("mi_smallk_prep", w, img, K, co)
         return img
     return _kept_image(owner if owner is not None else w, "_mi_smallk", w, (K, co), cut)
 
@@ -485,23 +485,21 @@ def _d32_launch(route, x, w, bias, relu, owner=None, out=None, pool=False):
     def cut(_):
         if kind == 3 or (kind == 4 and co >= 64):
             img = torch.empty((co // 64) * int(lib.mi_conv_d64_image_bytes(ci, ntap)), dtype=torch.uint8, device=w.device)
-            L.check(lib.mi_conv_d64_prep_co(L.ptr(w), L.ptr(img), ci, co, ntap, L.stream()), "mi_conv_d64_prep_co")
+            L.call("mi_conv_d64_prep_co", w, img, ci, co, ntap)
         else:
             img = torch.empty(int(lib.mi_conv_d32_image_bytes(ci, ntap)), dtype=torch.uint8, device=w.device)
-            L.check(lib.mi_conv_d32_prep(L.ptr(w), L.ptr(img), ci, ntap, L.stream()), "mi_conv_d32_prep")
+            L.call("mi_conv_d32_prep", w, img, ci, ntap)
         return img
     wimg = _kept_image(owner if owner is not None else w, "_mi_d32", w, (ci, ntap, co), cut)
     out, cstride = _out_tensor(out, tuple(x.shape[:-1]) + (co,), x, sliced=pool)
     if pool:                                          # kinds 1 / 3: the 2 x 2 max-pool of the result as a second output
         pooled = torch.empty(tuple(x.shape[:-3]) + (h // 2, wd // 2, co), dtype=torch.float32, device=x.device)
-        L.check(lib.mi_conv_d32_fwd_pool_strided_f32(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), cstride, L.ptr(pooled),
-                                                     int(relu), n, d, h, wd, ci, co, L.stream()), "mi_conv_d32_fwd_pool_strided_f32")
+        L.call("mi_conv_d32_fwd_pool_strided_f32", x, wimg, bias, out, cstride, pooled, int(relu), n, d, h, wd, ci, co)
         return out, pooled
     # kind 4: 1 x 1, tile-resident; 3: 3 x 3 per plane to 64-column blocks; 1 / 2: to 32 channels (2: the dilated 3-D head)
     fn = {4: "mi_conv_d32_1x1_fwd_f32", 3: "mi_conv_d64_fwd_f32"}.get(kind, "mi_conv_d32_fwd_f32")
     def call():
-        return L.check(getattr(lib, fn)(L.ptr(x), L.ptr(wimg), L.ptr(bias), L.ptr(out), int(relu), n, d, h, wd, ci,
-                                        co if kind in (3, 4) else kind, L.stream()), fn)
+        return L.call(fn, x, wimg, bias, out, int(relu), n, d, h, wd, ci, co if kind in (3, 4) else kind)
     _prof_run("fwd", 2.0 * n * d * h * wd * co * ci * ntap, call)
     return out
 
@@ -527,8 +525,7 @@ def detector_heads_fused(v, proj, hm):
     m = n * d * h * wd
     y = torch.empty((n, d, h, wd, 32), dtype=torch.float32, device=v.device)
     yh = torch.empty((n, d, h, wd, hm.k_out), dtype=torch.float32, device=v.device)
-    L.check(L.lib().mi_smallk_heads_fwd_f32(L.ptr(v), L.ptr(img), L.ptr(y), L.ptr(hm.weight), L.ptr(yh), hm.k_out, m, c, h * wd, d,
-                                            L.stream()), "mi_smallk_heads_fwd_f32")
+    L.call("mi_smallk_heads_fwd_f32", v, img, y, hm.weight, yh, hm.k_out, m, c, h * wd, d)
     return y, yh
 
 
@@ -540,10 +537,8 @@ def _smallk_launch(route, x, w, bias, relu, owner=None, out=None):
     out, _ = _out_tensor(out, tuple(x.shape[:-1]) + (co,), x)
     img = _smallk_image(w, owner, ntaps * ci, co)
     plane, d = (x.shape[2] * x.shape[3], x.shape[1]) if ntaps == 3 else (1, 1)
-    lib = L.lib()
     def call():
-        return L.check(lib.mi_smallk_fwd_f32(L.ptr(x), L.ptr(img), L.ptr(bias), L.ptr(out), int(relu), m, ci, co, ntaps, plane, d,
-                                             L.stream()), "mi_smallk_fwd_f32")
+        return L.call("mi_smallk_fwd_f32", x, img, bias, out, int(relu), m, ci, co, ntaps, plane, d)
     _prof_run("fwd", 2.0 * m * co * ci * ntaps, call)
     return out
 
@@ -672,10 +667,8 @@ def _p2d_launch(route, a, w, dgrad, res, mask, relu, tag, held):
     n, h, wd, c = a.shape
     out = torch.empty_like(a)
     img = _p2d_image(w, dgrad, held if route.param else None)
-    lib = L.lib()
     def call():
-        return L.check(lib.mi_conv2d_p2d_f32(L.ptr(a), L.ptr(img), L.ptr(out), L.ptr(res), L.ptr(mask), int(relu), n, h, wd, c,
-                                             L.stream()), "mi_conv2d_p2d_f32")
+        return L.call("mi_conv2d_p2d_f32", a, img, out, res, mask, int(relu), n, h, wd, c)
     _prof_run(tag, 2.0 * a.numel() * c * 9, call)
     return out
 
@@ -684,11 +677,11 @@ def _cube2_launch(lib, a, w, out, res, mask, relu, dgrad, n, c):
     # arrival counters in front of the partial sums: zero at allocation, left zero by every call; one buffer per stream
     ws = L.workspace(lib.mi_conv3d_cube2_workspace_bytes(n, c), a.device, "cube2", init=lambda b: b.zero_())
     def call():
-        rc = lib.mi_conv3d_cube2_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), L.ptr(mask), relu, dgrad, n, c, L.ptr(ws),
-                                     ws.numel(), L.stream())
-        if rc:
+        try:
+            L.call("mi_conv3d_cube2_f32", a, w, out, res, mask, relu, dgrad, n, c, ws, ws.numel())
+        except L.HipExtensionError:
             L.drop_workspace(a.device, "cube2")         # its counters can no longer be trusted
-        return L.check(rc, "mi_conv3d_cube2_f32")
+            raise
     return call
 
 
@@ -700,25 +693,21 @@ def _dense_launch(route, tag, g, a, w, out, res, mask, relu, held, flops, res_is
     dgrad = int(tag == "dgrad")
     if route.family == "direct":                          # (the engine keeps the image current: no image build, never under PROFILE)
         ws = _ws(lib.mi_conv3d_direct_workspace_bytes(n, ci), a.device, "conv")
-        L.check(lib.mi_conv3d_direct_f32(L.ptr(a), L.ptr(held), L.ptr(out), L.ptr(res), L.ptr(mask), relu, n, d, h, wd, ci,
-                                         L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_direct_f32")
+        L.call("mi_conv3d_direct_f32", a, held, out, res, mask, relu, n, d, h, wd, ci, ws, ws.numel())
         return out
     if route.family == "cube2":
         call = _cube2_launch(lib, a, w, out, res, mask, relu, dgrad, n, ci)
     elif route.family == "stem2d":
         def call():
-            return L.check(lib.mi_stem2d_fwd_bias_f32(L.ptr(a), L.ptr(w), L.ptr(res), L.ptr(out), relu, n, h, wd, L.stream()),
-                           "mi_stem2d_fwd_bias_f32")
+            return L.call("mi_stem2d_fwd_bias_f32", a, w, res, out, relu, n, h, wd)
     else:
         ws = g.workspace(a.device)
         if dgrad:
             def call():
-                return L.check(lib.mi_conv_dgrad_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), L.ptr(mask), g.ref, L.ptr(ws), ws.numel(),
-                                                     L.stream()), "mi_conv_dgrad_f32")
+                return L.call("mi_conv_dgrad_f32", a, w, out, res, mask, g.ref, ws, ws.numel())
         else:
             def call():
-                return L.check(lib.mi_conv_fwd_f32(L.ptr(a), L.ptr(w), L.ptr(out), L.ptr(res), res_is_bias, relu, g.ref, L.ptr(ws),
-                                                   ws.numel(), L.stream()), "mi_conv_fwd_f32")
+                return L.call("mi_conv_fwd_f32", a, w, out, res, res_is_bias, relu, g.ref, ws, ws.numel())
     _prof_run(tag, flops, call)
     return out
 
@@ -745,9 +734,8 @@ def _conv_forward(x, w, k, stride, pad, res, bias, relu, dil, owner, inference, 
     if route.family == "stem3":
         n, h, wd, _ = x.shape
         y = torch.empty((n, h, wd, co), dtype=torch.float32, device=x.device)
-        lib = L.lib()
         def call():
-            return L.check(lib.mi_conv2d_stem3_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(y), n, h, wd, co, L.stream()), "mi_conv2d_stem3_fwd_f32")
+            return L.call("mi_conv2d_stem3_fwd_f32", x, w, y, n, h, wd, co)
         _prof_run("fwd", 2.0 * y.numel() * 9, call)
         return y
     if route.family == "p2d":
@@ -802,13 +790,11 @@ def conv_fwd_s2_block(x, w, w_ds):
     hmid = torch.empty((n, g // 2, g // 2, g // 2, co), dtype=torch.float32, device=x.device)
     r = torch.empty_like(hmid)
     if route.param:                                       # the engine keeps the image current: no image build here
-        L.check(lib.mi_conv3d_s2_fwd_img_f32(L.ptr(x), L.ptr(img), L.ptr(hmid), L.ptr(r), n, g, ci, co, L.stream()),
-                "mi_conv3d_s2_fwd_img_f32")
+        L.call("mi_conv3d_s2_fwd_img_f32", x, img, hmid, r, n, g, ci, co)
         return hmid, r
     ws = _ws(lib.mi_conv3d_s2_fwd_workspace_bytes(ci, co), x.device, "conv_s2f")
     def call():
-        return L.check(lib.mi_conv3d_s2_fwd_f32(L.ptr(x), L.ptr(w), L.ptr(w_ds), L.ptr(hmid), L.ptr(r), n, g, ci, co, L.ptr(ws),
-                                                ws.numel(), L.stream()), "mi_conv3d_s2_fwd_f32")
+        return L.call("mi_conv3d_s2_fwd_f32", x, w, w_ds, hmid, r, n, g, ci, co, ws, ws.numel())
     # algorithmic FLOPs of both convolutions the launch replaces (27 taps + the 1x1 shortcut)
     _prof_run("fwd", 2.0 * hmid.numel() * ci * 28, call)
     return hmid, r
@@ -833,13 +819,11 @@ def conv_dgrad_s2_block(dh, d2, w, w_ds, in_shape, res=None, mask=None):
     lib = L.lib()
     dx = torch.empty(tuple(in_shape), dtype=torch.float32, device=dh.device)
     if route.param:                                       # the engine keeps the images current: no image build here
-        L.check(lib.mi_conv3d_s2_dgrad_img_f32(L.ptr(dh), L.ptr(d2), L.ptr(img), L.ptr(dx), L.ptr(res), L.ptr(mask), n, g, ci, co,
-                                               L.stream()), "mi_conv3d_s2_dgrad_img_f32")
+        L.call("mi_conv3d_s2_dgrad_img_f32", dh, d2, img, dx, res, mask, n, g, ci, co)
         return dx
     ws = _ws(lib.mi_conv3d_s2_dgrad_workspace_bytes(ci, co), dh.device, "conv_s2")
     def call():
-        return L.check(lib.mi_conv3d_s2_dgrad_f32(L.ptr(dh), L.ptr(d2), L.ptr(w), L.ptr(w_ds), L.ptr(dx), L.ptr(res), L.ptr(mask), n, g,
-                                                  ci, co, L.ptr(ws), ws.numel(), L.stream()), "mi_conv3d_s2_dgrad_f32")
+        return L.call("mi_conv3d_s2_dgrad_f32", dh, d2, w, w_ds, dx, res, mask, n, g, ci, co, ws, ws.numel())
     # algorithmic FLOPs of both convolutions the launch replaces (27 taps + the 1x1 shortcut)
     _prof_run("dgrad", 2.0 * dh.numel() * ci * (27 + (1 if d2 is not None else 0)), call)
     return dx
@@ -857,10 +841,8 @@ def flush_wgrad_reduces():
     items = DEFERRED_WGRADS
     if not items:
         return
-    L.check(L.lib().mi_splitk_reduce_batch(L.host_array([it[0].data_ptr() for it in items]), L.host_array([it[1].data_ptr() for it in items]),
-                                           L.host_array([it[2] for it in items], ctypes.c_int),
-                                           L.host_array([it[3] for it in items], ctypes.c_long), len(items), L.stream()),
-            "mi_splitk_reduce_batch")
+    L.call("mi_splitk_reduce_batch", L.host_array([it[0].data_ptr() for it in items]), L.host_array([it[1].data_ptr() for it in items]),
+           L.host_array([it[2] for it in items], ctypes.c_int), L.host_array([it[3] for it in items], ctypes.c_long), len(items))
     del items[:]
 
 
@@ -895,8 +877,7 @@ class _WgradJob:
 
     def __call__(self):
         splits = ctypes.c_int(0)
-        L.check(L.lib().mi_conv_wgrad_f32(L.ptr(self.x), L.ptr(self.dy), L.ptr(self.tgt), self.geom.ref, L.ptr(self.slab),
-                                          self.slab.numel(), ctypes.addressof(splits), L.stream()), "mi_conv_wgrad_f32")
+        L.call("mi_conv_wgrad_f32", self.x, self.dy, self.tgt, self.geom.ref, self.slab, self.slab.numel(), ctypes.addressof(splits))
         if splits.value > 1:
             DEFERRED_WGRADS.append((self.slab, self.tgt, int(splits.value), self.tgt.numel()))
 
@@ -953,20 +934,19 @@ def _flush_backward_end():
 def _launch_wgrad_group(jobs):
     """Up to WGRAD_BATCH_MAX jobs of one geometry and slab size: ONE batched launch or - a single job, or a geometry the library has no
     batched kernel for - one launch each; split launches leave their slabs registered in DEFERRED_WGRADS."""
-    rc = -3
+    batched = False
     if len(jobs) > 1:
         splits = ctypes.c_int(0)
-        rc = L.lib().mi_conv_wgrad_batch_f32(L.host_array([j.x.data_ptr() for j in jobs]), L.host_array([j.dy.data_ptr() for j in jobs]),
-                                             L.host_array([j.tgt.data_ptr() for j in jobs]), L.host_array([j.slab.data_ptr() for j in jobs]),
-                                             len(jobs), jobs[0].geom.ref, jobs[0].slab.numel(), ctypes.addressof(splits), L.stream())
-        if rc == 0 and splits.value > 1:
+        batched = L.call("mi_conv_wgrad_batch_f32", L.host_array([j.x.data_ptr() for j in jobs]),
+                         L.host_array([j.dy.data_ptr() for j in jobs]), L.host_array([j.tgt.data_ptr() for j in jobs]),
+                         L.host_array([j.slab.data_ptr() for j in jobs]), len(jobs), jobs[0].geom.ref, jobs[0].slab.numel(),
+                         ctypes.addressof(splits), may_decline=True)
+        if batched and splits.value > 1:
             for j in jobs:
                 DEFERRED_WGRADS.append((j.slab, j.tgt, int(splits.value), j.tgt.numel()))
-    if rc == -3:                                           # MI_E_UNSUPPORTED (or a single job): one launch each
+    if not batched:                                        # MI_E_UNSUPPORTED (or a single job): one launch each
         for j in jobs:
             j()
-    else:
-        L.check(rc, "mi_conv_wgrad_batch_f32")
 
 
 def run_wgrad_jobs(items):
@@ -1061,26 +1041,22 @@ def conv_wgrad_into(x, dy, param, k, stride, pad, dil=None):
     if route.family == "stem3":
         ws = _ws(lib.mi_conv2d_stem3_workspace_bytes(co), x.device, "stem3")
         def call():
-            return L.check(lib.mi_conv2d_stem3_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, co, L.ptr(ws), ws.numel(),
-                                                         L.stream()), "mi_conv2d_stem3_wgrad_f32")
+            return L.call("mi_conv2d_stem3_wgrad_f32", x, dy, tgt, n, h, wd, co, ws, ws.numel())
     elif route.family == "p2d":
         ws = _ws(int(lib.mi_conv2d_p2d_wgrad_workspace_bytes(n, h, wd, ci)), x.device, "p2d_wgrad")
         def call():
-            return L.check(lib.mi_conv2d_p2d_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), n, h, wd, ci, L.ptr(ws), ws.numel(), L.stream()),
-                           "mi_conv2d_p2d_wgrad_f32")
+            return L.call("mi_conv2d_p2d_wgrad_f32", x, dy, tgt, n, h, wd, ci, ws, ws.numel())
     else:
         ws = geom.workspace(x.device)
         def call():
-            return L.check(lib.mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
-                           "mi_conv_wgrad_f32")
+            return L.call("mi_conv_wgrad_f32", x, dy, tgt, geom.ref, ws, ws.numel(), None)
     with dest:
         _prof_run("wgrad", flops, call)
 
 
 def relu_mask(dy, y, add=None):
     out = torch.empty_like(dy)
-    L.check(L.lib().mi_relu_mask(L.ptr(dy), L.ptr(y), L.ptr(add), L.ptr(out), dy.numel(), L.stream()),
-            "mi_relu_mask")
+    L.call("mi_relu_mask", dy, y, add, out, dy.numel())
     return out
 
 
@@ -1101,11 +1077,8 @@ def _stem_fwd_with_stats(x, w, mod):
     y = torch.empty((n, do, ho, wo, co), dtype=torch.float32, device=x.device)
     sums = torch.empty(2 * co, dtype=torch.float64, device=x.device)
     ws = _ws(nbytes, x.device, "stem_stats")
-    rc = lib.mi_conv3d_stem_stats_f32(L.ptr(x), L.ptr(w), L.ptr(y), n, d, h, wd, co, L.ptr(sums), L.ptr(ws), ws.numel(),
-                                      L.stream())
-    if rc == -3:
+    if not L.call("mi_conv3d_stem_stats_f32", x, w, y, n, d, h, wd, co, sums, ws, ws.numel(), may_decline=True):
         return None
-    L.check(rc, "mi_conv3d_stem_stats_f32")
     mod.bn_sums = sums
     return y
 
@@ -1261,7 +1234,7 @@ def _d32_up_image(up, ci, co):
     lib = L.lib()
     def cut(_):
         img = torch.empty((4 * co // 64) * int(lib.mi_conv_d64_image_bytes(ci, 1)), dtype=torch.uint8, device=wv.device)
-        L.check(lib.mi_conv_d64_prep_co(L.ptr(wv), L.ptr(img), ci, 4 * co, 1, L.stream()), "mi_conv_d64_prep_co")
+        L.call("mi_conv_d64_prep_co", wv, img, ci, 4 * co, 1)
         return img
     return _kept_image(up.weight, "_mi_d32_up", wv, (ci, co, "up"), cut)
 
@@ -1295,15 +1268,13 @@ def upconv_bn_relu_concat(up, bn, dec, enc, cat=None):
         _f32c(enc, "enc")                                # (with `cat`, enc is a channel slice of it: checked below)
     n, h, w, _ = dec.shape
     co, ce = up.co, enc.shape[-1]
-    lib = L.lib()
     ci = dec.shape[-1]
     if cat is not None:
         # `enc` IS cat[..., co:] (the down-convolution block wrote it there: skip_into_concat_ok): only the first co channels are missing
         if (tuple(cat.shape) != (n, ho, wo, co + ce) or not cat.is_contiguous() or enc.data_ptr() != cat.data_ptr() + 4 * co):
             raise L.HipExtensionError("upconv_bn_relu_concat: `cat` is not the buffer `enc` is a channel slice of")
         wimg = _d32_up_image(up, ci, co)
-        L.check(lib.mi_conv_d32_upconv_fwd_f32(L.ptr(dec), L.ptr(wimg), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(cat), n, h, w, ci, co,
-                                               ho, wo, co + ce, L.stream()), "mi_conv_d32_upconv_fwd_f32")
+        L.call("mi_conv_d32_upconv_fwd_f32", dec, wimg, cache[1], cache[2], cat, n, h, w, ci, co, ho, wo, co + ce)
         return cat
     out = torch.empty((n, ho, wo, co + ce), dtype=torch.float32, device=dec.device)
     if (UPCONV_FUSED and _arith_bf16x3() and PROFILE is None and ci in (32, 64, 128) and co % 32 == 0 and 64 <= 4 * co <= 512
@@ -1311,16 +1282,11 @@ def upconv_bn_relu_concat(up, bn, dec, enc, cat=None):
         # the product, the pixel shuffle, the folded BatchNorm and the ReLU in ONE launch (conv_d32.hip, 1 x 1 form with the
         # up-convolution epilogue) straight into the concatenation; the encoder feature goes into the other channels
         wimg = _d32_up_image(up, ci, co)
-        rc = lib.mi_conv_d32_upconv_fwd_f32(L.ptr(dec), L.ptr(wimg), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(out), n, h, w, ci, co,
-                                            ho, wo, co + ce, L.stream())
-        if rc == 0:
-            L.check(lib.mi_copy_channels_into(L.ptr(enc), ce, L.ptr(out), co + ce, co, n * ho * wo, L.stream()), "mi_copy_channels_into")
+        if L.call("mi_conv_d32_upconv_fwd_f32", dec, wimg, cache[1], cache[2], out, n, h, w, ci, co, ho, wo, co + ce, may_decline=True):
+            L.call("mi_copy_channels_into", enc, ce, out, co + ce, co, n * ho * wo)
             return out
-        if rc != -3:
-            L.check(rc, "mi_conv_d32_upconv_fwd_f32")
     t = conv_fwd(dec, up.gemm_view(), 1, 1, 0, owner=up.weight, inference=True)      # (`folded` above: no gradient)
-    L.check(L.lib().mi_upconv_tail_fwd(L.ptr(t), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(enc), L.ptr(out), n, h, w, co, ce, ho, wo,
-                                       L.stream()), "mi_upconv_tail_fwd")
+    L.call("mi_upconv_tail_fwd", t, cache[1], cache[2], enc, out, n, h, w, co, ce, ho, wo)
     return out
 
 
@@ -1402,42 +1368,35 @@ class _LinearFn(torch.autograd.Function):
             # one launch with an epilogue: the fused entry `fuse` asks for, then - no request, or the entry declined (-3,
             # MI_E_UNSUPPORTED: rows, arithmetic switch) - the product with the bias in it, then the generic path below
             _f32c(x, "x")
-            lib = L.lib()
             co = w5.shape[0]
             y = torch.empty((m, co), dtype=torch.float32, device=x.device)
-            rc, what = -3, None
+            fused = False
             if fuse is not None and fuse.stats_only:
                 # this rank's column sums come out of the product's epilogue; the BatchNorm node all-reduces them and applies
-                what = "mi_linear_stats_fwd_f32"
                 sums = torch.empty(2 * co, dtype=torch.float64, device=x.device)
-                rc = lib.mi_linear_stats_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), L.ptr(sums), m, ci, co, L.stream())
-                if rc == 0:
+                fused = L.call("mi_linear_stats_fwd_f32", x, w5, b, y, sums, m, ci, co, may_decline=True)
+                if fused:
                     fuse.sums = sums
             elif fuse is not None:
                 # Linear + BatchNorm1d (+ ReLU) in one launch: the BatchNorm's output and saved statistics go back to linear_bn
                 # for the BatchNorm node; this node's own output is the Linear's, as always
-                what = "mi_linear_bn_fwd_f32"
                 bn = fuse.bn
                 yb = torch.empty((m, co), dtype=torch.float32, device=x.device)
                 save = torch.empty(2 * co, dtype=torch.float32, device=x.device)
-                rc = lib.mi_linear_bn_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), L.ptr(yb), m, ci, co, L.ptr(bn.weight),
-                                              L.ptr(bn.bias), bn.eps, bn.momentum,
-                                              *_bn_running_ptrs(bn, bn.track_running_stats and bn.training),
-                                              L.ptr(save), int(fuse.relu), L.stream())
-                if rc == 0:
+                fused = L.call("mi_linear_bn_fwd_f32", x, w5, b, y, yb, m, ci, co, bn.weight, bn.bias, bn.eps, bn.momentum,
+                               *_bn_running_ptrs(bn, bn.track_running_stats and bn.training), save, int(fuse.relu), may_decline=True)
+                if fused:
                     fuse.applied = (yb, save)
-            if rc == -3 and b is not None:
+            if not fused and b is not None:
                 # the bias rides in the epilogue of the GEMM launch (or of its split-K reduce)
-                what = "mi_linear_fwd_f32"
                 ws = _linear_geom(m, ci, co).workspace(x.device)
-                rc = lib.mi_linear_fwd_f32(L.ptr(x), L.ptr(w5), L.ptr(b), L.ptr(y), m, ci, co, L.ptr(ws), ws.numel(), L.stream())
-            elif rc == -3:
-                y, rc = None, 0
-            L.check(rc, what)
+                L.call("mi_linear_fwd_f32", x, w5, b, y, m, ci, co, ws, ws.numel())
+            elif not fused:
+                y = None
         if y is None:
             y = conv_fwd(x.view(m, 1, 1, 1, ci), w5, 1, 1, 0, owner=w, inference=inference).view(m, -1)
             if b is not None:
-                L.check(L.lib().mi_bias_add(L.ptr(y), L.ptr(b), m, y.shape[1], L.stream()), "mi_bias_add")
+                L.call("mi_bias_add", y, b, m, y.shape[1])
         ctx.mod = mod
         ctx.save_for_backward(x)
         ctx.x_needs_grad = x.requires_grad
@@ -1456,8 +1415,7 @@ class _LinearFn(torch.autograd.Function):
                 geom = _linear_geom(m, ci, co)
                 ws = geom.workspace(x.device)
                 with dest as tgt:
-                    L.check(L.lib().mi_conv_wgrad_f32(L.ptr(x), L.ptr(dy), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None,
-                                                      L.stream()), "mi_conv_wgrad_f32")
+                    L.call("mi_conv_wgrad_f32", x, dy, tgt, geom.ref, ws, ws.numel(), None)
             _side_or_now(launch, m)
         if mod.bias is not None and mod.bias.requires_grad:
             _side_or_now(_colsum_job(dy, mod.bias), m)  # the bias gradient is a parameter gradient too: same side-stream batch
@@ -1538,7 +1496,7 @@ def _bn_stats(x, m, c):
     lib = L.lib()
     ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), x.device, "colreduce")
     sums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
-    L.check(lib.mi_bn_stats(L.ptr(x), m, c, L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_bn_stats")
+    L.call("mi_bn_stats", x, m, c, sums, ws, ws.numel())
     return sums
 
 
@@ -1589,8 +1547,8 @@ def _bn_batch_sums(x, m, c, mod, sums=None, reduced=False):
 def _bn_running_ptrs(mod, track):
     """The (running_mean, running_var, num_batches_tracked) arguments of a BatchNorm launch: null unless `track`."""
     if not track:
-        return L.ptr(None), L.ptr(None), L.ptr(None)
-    return L.ptr(mod.running_mean), L.ptr(mod.running_var), L.ptr(mod.num_batches_tracked)
+        return None, None, None
+    return mod.running_mean, mod.running_var, mod.num_batches_tracked
 
 
 def _bn_affine_grads(mod):
@@ -1606,11 +1564,11 @@ def _bn_sync_bwd_sums(sums, c, dg, db, distributed):
     does the same; the data-parallel gradient averaging then treats them like every other parameter), the sums are all-reduced
     for dx and the apply launch gets null pointers."""
     if not distributed:
-        return L.ptr(dg), L.ptr(db)
+        return dg, db
     if dg is not None:
-        L.check(L.lib().mi_bn_param_grads(L.ptr(sums), c, L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_param_grads")
+        L.call("mi_bn_param_grads", sums, c, dg, db)
     dist_all_reduce(sums)
-    return L.ptr(None), L.ptr(None)
+    return None, None
 
 
 class _BNFn(torch.autograd.Function):
@@ -1621,7 +1579,6 @@ class _BNFn(torch.autograd.Function):
         ctx.res_slot = res_slot if res is not None else None
         c = x.shape[-1]
         m = x.numel() // c
-        lib = L.lib()
         train = mod.training or not mod.track_running_stats
         ctx.small = train and m <= BN_SMALL_MAX_ROWS and not (mod.sync and _distributed())
         ctx.count = float(m)
@@ -1637,18 +1594,14 @@ class _BNFn(torch.autograd.Function):
             save = torch.empty(2 * c, dtype=torch.float32, device=x.device)
             if ctx.small:
                 # one launch: statistics, running statistics, affine (+res, ReLU)
-                L.check(lib.mi_bn_small_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(gamma), L.ptr(beta), mod.eps, mod.momentum,
-                                            *_bn_running_ptrs(mod, track), L.ptr(save), L.ptr(res), int(relu), L.stream()),
-                        "mi_bn_small_fwd")
+                L.call("mi_bn_small_fwd", x, y, m, c, gamma, beta, mod.eps, mod.momentum, *_bn_running_ptrs(mod, track), save, res,
+                       int(relu))
             elif train:
                 sums, ctx.count = _bn_batch_sums(x, m, c, mod, sums, reduced)
-                L.check(lib.mi_bn_apply_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(sums), ctx.count, L.ptr(gamma), L.ptr(beta),
-                                            mod.eps, mod.momentum, *_bn_running_ptrs(mod, track),
-                                            L.ptr(save), L.ptr(res), int(relu), L.stream()), "mi_bn_apply_fwd")
+                L.call("mi_bn_apply_fwd", x, y, m, c, sums, ctx.count, gamma, beta, mod.eps, mod.momentum, *_bn_running_ptrs(mod, track),
+                       save, res, int(relu))
             else:
-                L.check(lib.mi_bn_eval_fwd(L.ptr(x), L.ptr(y), m, c, L.ptr(mod.running_mean), L.ptr(mod.running_var),
-                                           L.ptr(gamma), L.ptr(beta), mod.eps, L.ptr(save), L.ptr(res), int(relu),
-                                           L.stream()), "mi_bn_eval_fwd")
+                L.call("mi_bn_eval_fwd", x, y, m, c, mod.running_mean, mod.running_var, gamma, beta, mod.eps, save, res, int(relu))
         ctx.mod, ctx.relu, ctx.m, ctx.c = mod, relu, m, c
         ctx.has_res = res is not None
         ctx.save_for_backward(x, y if relu else None, save)
@@ -1678,23 +1631,19 @@ class _BNFn(torch.autograd.Function):
         if ctx.small:
             dgamma, dbeta = _bn_affine_grads(mod)
             with dgamma as dg, dbeta as db:
-                L.check(lib.mi_bn_small_bwd(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma),
-                                            int(relu), L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_small_bwd")
+                L.call("mi_bn_small_bwd", dy, x, y, dx, m, c, save, gamma, int(relu), dg, db)
         else:
             ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), x.device, "colreduce")
             sums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
-            L.check(lib.mi_bn_bwd_reduce(L.ptr(dy), L.ptr(x), L.ptr(y), m, c, L.ptr(save), int(relu), L.ptr(sums),
-                                         L.ptr(ws), ws.numel(), L.stream()), "mi_bn_bwd_reduce")
+            L.call("mi_bn_bwd_reduce", dy, x, y, m, c, save, int(relu), sums, ws, ws.numel())
             dgamma, dbeta = _bn_affine_grads(mod)
             with dgamma as dg, dbeta as db:
                 pg, pb = _bn_sync_bwd_sums(sums, c, dg, db, mod.sync and _distributed())
                 if want_dres:
                     dres = torch.empty_like(dy)
-                    L.check(lib.mi_bn_bwd_apply_res(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), L.ptr(dres), m, c, L.ptr(save),
-                                                    L.ptr(gamma), L.ptr(sums), ctx.count, pg, pb, L.stream()), "mi_bn_bwd_apply_res")
+                    L.call("mi_bn_bwd_apply_res", dy, x, y, dx, dres, m, c, save, gamma, sums, ctx.count, pg, pb)
                 else:
-                    L.check(lib.mi_bn_bwd_apply(L.ptr(dy), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma),
-                                                L.ptr(sums), ctx.count, int(relu), pg, pb, L.stream()), "mi_bn_bwd_apply")
+                    L.call("mi_bn_bwd_apply", dy, x, y, dx, m, c, save, gamma, sums, ctx.count, int(relu), pg, pb)
         if ctx.res_slot is not None and dres is not None:
             # through the block's GradSlot when its first convolution adds the residual gradient in its own epilogue
             ctx.res_slot.tensor = dres
@@ -1708,7 +1657,6 @@ class _BNReluPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, mod, k, stride, pad, sums=None, reduced=False):
         n, d, h, w, c = x.shape
-        lib = L.lib()
         dev = x.device
         do, ho, wo = [(v + 2 * pad - k) // stride + 1 for v in (d, h, w)]
         y = torch.empty((n, do, ho, wo, c), dtype=torch.float32, device=dev)
@@ -1719,10 +1667,8 @@ class _BNReluPoolFn(torch.autograd.Function):
         sums, count = _bn_batch_sums(x, m, c, mod, sums, reduced) if train else (None, float(m))
         track = mod.track_running_stats and mod.training
         running_mean, running_var, _ = _bn_running_ptrs(mod, track or not train)     # (eval mode READS the running statistics)
-        L.check(lib.mi_bn_relu_maxpool3d_fwd(
-            L.ptr(x), L.ptr(y), L.ptr(arg), n, d, h, w, c, k, stride, pad, L.ptr(sums), count, L.ptr(gamma), L.ptr(beta),
-            mod.eps, mod.momentum, running_mean, running_var, L.ptr(mod.num_batches_tracked if track else None),
-            L.ptr(save), L.stream()), "mi_bn_relu_maxpool3d_fwd")
+        L.call("mi_bn_relu_maxpool3d_fwd", x, y, arg, n, d, h, w, c, k, stride, pad, sums, count, gamma, beta, mod.eps, mod.momentum,
+               running_mean, running_var, mod.num_batches_tracked if track else None, save)
         ctx.mod, ctx.geom, ctx.count, ctx.train = mod, (n, d, h, w, c, k, stride, pad), count, train
         ctx.save_for_backward(x, save, arg)
         return y
@@ -1742,17 +1688,14 @@ class _BNReluPoolFn(torch.autograd.Function):
         gamma, beta = mod.weight, mod.bias
         # the pool's backward materialised once, then BatchNorm's two halves with the ReLU mask recomputed from x
         dy = torch.empty_like(x)
-        L.check(lib.mi_maxpool3d_bwd(L.ptr(dp), L.ptr(arg), L.ptr(dy), n, d, h, w, c, k, stride, pad, L.stream()),
-                "mi_maxpool3d_bwd")
+        L.call("mi_maxpool3d_bwd", dp, arg, dy, n, d, h, w, c, k, stride, pad)
         ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dev, "colreduce")
-        L.check(lib.mi_bn_relu_bwd_reduce_x(L.ptr(dy), L.ptr(x), m, c, L.ptr(save), L.ptr(gamma), L.ptr(beta), L.ptr(sums),
-                                            L.ptr(ws), ws.numel(), L.stream()), "mi_bn_relu_bwd_reduce_x")
+        L.call("mi_bn_relu_bwd_reduce_x", dy, x, m, c, save, gamma, beta, sums, ws, ws.numel())
         dx = dy                                            # in place: each element is read, then written, by one thread
         dgamma, dbeta = _bn_affine_grads(mod)
         with dgamma as dg, dbeta as db:
             pg, pb = _bn_sync_bwd_sums(sums, c, dg, db, mod.sync and _distributed())
-            L.check(lib.mi_bn_relu_bwd_apply_x(L.ptr(dy), L.ptr(x), L.ptr(dx), m, c, L.ptr(save), L.ptr(gamma), L.ptr(beta),
-                                               L.ptr(sums), ctx.count, pg, pb, L.stream()), "mi_bn_relu_bwd_apply_x")
+            L.call("mi_bn_relu_bwd_apply_x", dy, x, dx, m, c, save, gamma, beta, sums, ctx.count, pg, pb)
         return dx, None, None, None, None, None, None, None, None
 
 
@@ -1832,8 +1775,7 @@ class _MaxPoolFn(torch.autograd.Function):
         do, ho, wo = [(v + 2 * pad - k) // stride + 1 for v in (d, h, w)]
         y = torch.empty((n, do, ho, wo, c), dtype=torch.float32, device=x.device)
         arg = torch.empty((n, do, ho, wo, c), dtype=torch.uint8, device=x.device)
-        L.check(L.lib().mi_maxpool3d_fwd(L.ptr(x), L.ptr(y), L.ptr(arg), n, d, h, w, c, k, stride, pad, L.stream()),
-                "mi_maxpool3d_fwd")
+        L.call("mi_maxpool3d_fwd", x, y, arg, n, d, h, w, c, k, stride, pad)
         ctx.save_for_backward(arg)
         ctx.geom = (x.shape, k, stride, pad)
         return y
@@ -1844,8 +1786,7 @@ class _MaxPoolFn(torch.autograd.Function):
         shape, k, stride, pad = ctx.geom
         n, d, h, w, c = shape
         dx = torch.empty(shape, dtype=torch.float32, device=dy.device)
-        L.check(L.lib().mi_maxpool3d_bwd(L.ptr(dy.contiguous()), L.ptr(arg), L.ptr(dx), n, d, h, w, c, k, stride,
-                                         pad, L.stream()), "mi_maxpool3d_bwd")
+        L.call("mi_maxpool3d_bwd", dy.contiguous(), arg, dx, n, d, h, w, c, k, stride, pad)
         return dx, None, None, None
 
 
@@ -1860,7 +1801,7 @@ class _AvgPoolFn(torch.autograd.Function):
         c = x.shape[-1]
         s = x.numel() // (n * c)
         y = torch.empty((n, c), dtype=torch.float32, device=x.device)
-        L.check(L.lib().mi_avgpool_fwd(L.ptr(x), L.ptr(y), n, s, c, L.stream()), "mi_avgpool_fwd")
+        L.call("mi_avgpool_fwd", x, y, n, s, c)
         ctx.shape = x.shape
         return y
 
@@ -1872,7 +1813,7 @@ class _AvgPoolFn(torch.autograd.Function):
         for v in shape[1:-1]:
             s *= v
         dx = torch.empty(shape, dtype=torch.float32, device=dy.device)
-        L.check(L.lib().mi_avgpool_bwd(L.ptr(dy.contiguous()), L.ptr(dx), n, s, c, L.stream()), "mi_avgpool_bwd")
+        L.call("mi_avgpool_bwd", dy.contiguous(), dx, n, s, c)
         return dx
 
 
@@ -1888,13 +1829,11 @@ class _BNReluAvgPoolFn(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, mod, v):
         c = x.shape[-1]
         m = x.numel() // c
-        lib = L.lib()
         y = torch.empty_like(x)
         pooled = torch.empty((x.shape[0], c), dtype=torch.float32, device=x.device)
         save = torch.empty(2 * c, dtype=torch.float32, device=x.device)
-        L.check(lib.mi_bn_small_pool_fwd(L.ptr(x), L.ptr(y), L.ptr(pooled), m, c, v, L.ptr(gamma), L.ptr(beta), mod.eps,
-                                         mod.momentum, *_bn_running_ptrs(mod, mod.track_running_stats and mod.training),
-                                         L.ptr(save), L.stream()), "mi_bn_small_pool_fwd")
+        L.call("mi_bn_small_pool_fwd", x, y, pooled, m, c, v, gamma, beta, mod.eps, mod.momentum,
+               *_bn_running_ptrs(mod, mod.track_running_stats and mod.training), save)
         ctx.mod, ctx.m, ctx.c, ctx.v = mod, m, c, v
         ctx.save_for_backward(x, y, save)
         return pooled
@@ -1906,8 +1845,7 @@ class _BNReluAvgPoolFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma, dbeta = _bn_affine_grads(mod)
         with dgamma as dg, dbeta as db:
-            L.check(L.lib().mi_bn_small_pool_bwd(L.ptr(dp.contiguous()), L.ptr(x), L.ptr(y), L.ptr(dx), m, c, v, L.ptr(save),
-                                                 L.ptr(mod.weight), L.ptr(dg), L.ptr(db), L.stream()), "mi_bn_small_pool_bwd")
+            L.call("mi_bn_small_pool_bwd", dp.contiguous(), x, y, dx, m, c, v, save, mod.weight, dg, db)
         return dx, None, None, None, None
 
 
@@ -2001,7 +1939,7 @@ class _L2NormFn(torch.autograd.Function):
         b, c = x.shape
         y = torch.empty_like(x)
         inv = torch.empty(b, dtype=torch.float32, device=x.device)
-        L.check(L.lib().mi_l2norm_fwd(L.ptr(x), L.ptr(y), L.ptr(inv), b, c, L.stream()), "mi_l2norm_fwd")
+        L.call("mi_l2norm_fwd", x, y, inv, b, c)
         ctx.save_for_backward(y, inv)
         return y
 
@@ -2010,8 +1948,7 @@ class _L2NormFn(torch.autograd.Function):
         y, inv = ctx.saved_tensors
         b, c = y.shape
         dx = torch.empty_like(y)
-        L.check(L.lib().mi_l2norm_bwd(L.ptr(dy.contiguous()), L.ptr(y), L.ptr(inv), L.ptr(dx), b, c, L.stream()),
-                "mi_l2norm_bwd")
+        L.call("mi_l2norm_bwd", dy.contiguous(), y, inv, dx, b, c)
         return dx
 
 
@@ -2027,8 +1964,7 @@ class _MocoLogitsFn(torch.autograd.Function):
         b, c = q.shape
         r = queue.shape[1]
         logits = torch.empty((b, r + 1), dtype=torch.float32, device=q.device)
-        L.check(L.lib().mi_moco_logits_fwd(L.ptr(q), L.ptr(k), L.ptr(queue), L.ptr(logits), b, c, r, float(T),
-                                           L.stream()), "mi_moco_logits_fwd")
+        L.call("mi_moco_logits_fwd", q, k, queue, logits, b, c, r, float(T))
         ctx.save_for_backward(k, queue.clone())      # the queue is overwritten by the enqueue below
         ctx.T = float(T)
         return logits
@@ -2039,8 +1975,7 @@ class _MocoLogitsFn(torch.autograd.Function):
         b, c = k.shape
         r = queue.shape[1]
         dq = torch.empty_like(k)
-        L.check(L.lib().mi_moco_logits_bwd(L.ptr(dl.contiguous()), L.ptr(k), L.ptr(queue), L.ptr(dq), b, c, r,
-                                           ctx.T, L.stream()), "mi_moco_logits_bwd")
+        L.call("mi_moco_logits_bwd", dl.contiguous(), k, queue, dq, b, c, r, ctx.T)
         return dq, None, None, None
 
 
@@ -2062,9 +1997,7 @@ class _MocoLogitsNormFn(torch.autograd.Function):
         q_hat = torch.empty_like(q_raw)
         k_hat = torch.empty_like(q_raw)
         q_inv = torch.empty(b, dtype=torch.float32, device=dev)
-        L.check(L.lib().mi_moco_logits_norm_fwd(L.ptr(q_raw), L.ptr(k_raw), L.ptr(queue), L.ptr(logits), L.ptr(q_hat),
-                                                L.ptr(q_inv), L.ptr(k_hat), b, c, r, float(T), L.stream()),
-                "mi_moco_logits_norm_fwd")
+        L.call("mi_moco_logits_norm_fwd", q_raw, k_raw, queue, logits, q_hat, q_inv, k_hat, b, c, r, float(T))
         ctx.save_for_backward(k_hat, queue if queue_stable else queue.clone(), q_hat, q_inv)
         ctx.T = float(T)
         ctx.mark_non_differentiable(k_hat)
@@ -2078,12 +2011,10 @@ class _MocoLogitsNormFn(torch.autograd.Function):
         k_hat, queue, q_hat, q_inv = ctx.saved_tensors
         b, c = k_hat.shape
         r = queue.shape[1]
-        lib = L.lib()
         dq = torch.empty_like(k_hat)
-        L.check(lib.mi_moco_logits_bwd(L.ptr(dl.contiguous()), L.ptr(k_hat), L.ptr(queue), L.ptr(dq), b, c, r, ctx.T,
-                                       L.stream()), "mi_moco_logits_bwd")
+        L.call("mi_moco_logits_bwd", dl.contiguous(), k_hat, queue, dq, b, c, r, ctx.T)
         dx = torch.empty_like(dq)
-        L.check(lib.mi_l2norm_bwd(L.ptr(dq), L.ptr(q_hat), L.ptr(q_inv), L.ptr(dx), b, c, L.stream()), "mi_l2norm_bwd")
+        L.call("mi_l2norm_bwd", dq, q_hat, q_inv, dx, b, c)
         return dx, None, None, None, None
 
 
@@ -2136,11 +2067,12 @@ class _CELabel0Fn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         rows = torch.empty(3 * b, dtype=torch.float32, device=logits.device)          # row losses | row maxima | log row sums
         word = _ce0_counter(logits.device)
-        rc = L.lib().mi_ce_label0_fwd(L.ptr(logits), L.ptr(loss), L.ptr(out), L.ptr(rows), L.ptr(rows[b:]), b, n,
-                                      L.ptr(word), L.stream())
-        if rc != 0 and not torch.cuda.is_current_stream_capturing():
-            word[:1].zero_()                           # a launch that failed midway must not leave its tickets behind
-        L.check(rc, "mi_ce_label0_fwd")
+        try:
+            L.call("mi_ce_label0_fwd", logits, loss, out, rows, rows[b:], b, n, word)
+        except L.HipExtensionError:
+            if not torch.cuda.is_current_stream_capturing():
+                word[:1].zero_()                       # a launch that failed midway must not leave its tickets behind
+            raise
         ctx.save_for_backward(logits, rows)
         return loss
 
@@ -2149,8 +2081,7 @@ class _CELabel0Fn(torch.autograd.Function):
         logits, rows = ctx.saved_tensors
         b, n = logits.shape
         dl = torch.empty_like(logits)
-        L.check(L.lib().mi_ce_label0_bwd(L.ptr(logits), L.ptr(rows[b:]), L.ptr(g.contiguous()), L.ptr(dl), b, n, L.stream()),
-                "mi_ce_label0_bwd")
+        L.call("mi_ce_label0_bwd", logits, rows[b:], g.contiguous(), dl, b, n)
         return dl, None
 
 
@@ -2167,7 +2098,7 @@ class _RowDotMeanFn(torch.autograd.Function):
     def forward(ctx, a, b):
         bsz, c = a.shape
         out = torch.empty((), dtype=torch.float32, device=a.device)
-        L.check(L.lib().mi_rowdot_mean_fwd(L.ptr(a), L.ptr(b), L.ptr(out), bsz, c, L.stream()), "mi_rowdot_mean_fwd")
+        L.call("mi_rowdot_mean_fwd", a, b, out, bsz, c)
         ctx.save_for_backward(b)
         return out
 
@@ -2175,8 +2106,7 @@ class _RowDotMeanFn(torch.autograd.Function):
     def backward(ctx, g):
         (b,) = ctx.saved_tensors
         da = torch.empty_like(b)
-        L.check(L.lib().mi_rowdot_mean_bwd(L.ptr(b), L.ptr(g.contiguous()), L.ptr(da), b.shape[0], b.shape[1],
-                                           L.stream()), "mi_rowdot_mean_bwd")
+        L.call("mi_rowdot_mean_bwd", b, g.contiguous(), da, b.shape[0], b.shape[1])
         return da, None
 
 
@@ -2188,8 +2118,7 @@ def column_std_mean(x):
     """torch.std(x, 0).mean() (the SimSiam `output_std` monitor).  A single row (B = 1) has no spread: the result is 0,
     where torch.std gives NaN; a column whose variance rounds below zero counts as 0."""
     out = torch.empty((), dtype=torch.float32, device=x.device)
-    L.check(L.lib().mi_column_std_mean(L.ptr(_f32c(x, "x")), L.ptr(out), x.shape[0], x.shape[1], L.stream()),
-            "mi_column_std_mean")
+    L.call("mi_column_std_mean", _f32c(x, "x"), out, x.shape[0], x.shape[1])
     return out
 
 
@@ -2198,30 +2127,26 @@ def column_std_mean(x):
 # ------------------------------------------------------------------------------------------------
 def ema_update_(k_flat, q_flat, m):
     _bump_weight_epoch()                 # a raw-pointer write: torch's version counters do not see it
-    L.check(L.lib().mi_ema_update(L.ptr(k_flat), L.ptr(q_flat), float(m), k_flat.numel(), L.stream()),
-            "mi_ema_update")
+    L.call("mi_ema_update", k_flat, q_flat, float(m), k_flat.numel())
 
 
 def sgd_step_(p_flat, g_flat, lr, weight_decay=0.0, lr_dev=None, grad_scale=1.0):
     """p -= lr * (grad_scale * g + wd * p); grad_scale = 1 / world when g is the SUM of the ranks' gradients."""
     _bump_weight_epoch()
-    L.check(L.lib().mi_sgd_step(L.ptr(p_flat), L.ptr(g_flat), L.ptr(lr_dev), float(lr), float(weight_decay),
-                                float(grad_scale), p_flat.numel(), L.stream()), "mi_sgd_step")
+    L.call("mi_sgd_step", p_flat, g_flat, lr_dev, float(lr), float(weight_decay), float(grad_scale), p_flat.numel())
 
 
 def sgd_step2_(p_flat, g_flat, g2_flat, lr, weight_decay=0.0, lr_dev=None, grad_scale=1.0):
     """p -= lr * (grad_scale * (g + g2) + wd * p): two gradient arenas (one per view of a two-view model)."""
     _bump_weight_epoch()
-    L.check(L.lib().mi_sgd_step2(L.ptr(p_flat), L.ptr(g_flat), L.ptr(g2_flat), L.ptr(lr_dev), float(lr), float(weight_decay),
-                                 float(grad_scale), p_flat.numel(), L.stream()), "mi_sgd_step2")
+    L.call("mi_sgd_step2", p_flat, g_flat, g2_flat, lr_dev, float(lr), float(weight_decay), float(grad_scale), p_flat.numel())
 
 
 def scalar_accumulate_(sums, *scalars):
     """sums[i] += scalars[i] (0-d / 1-element f32 device tensors, at most four) in one launch."""
     if len(scalars) > 4 or sums.numel() < len(scalars):
         raise L.HipExtensionError("scalar_accumulate_: at most four scalars, sums at least as long")
-    ptrs = [L.ptr(_f32c(t, "scalar")) for t in scalars] + [None] * (4 - len(scalars))
-    L.check(L.lib().mi_scalar_accumulate(L.ptr(sums), *ptrs, L.stream()), "mi_scalar_accumulate")
+    L.call("mi_scalar_accumulate", sums, *[_f32c(t, "scalar") for t in scalars], *[None] * (4 - len(scalars)))
 
 
 def copy_pair_(dst0, src0, dst1, src1):
@@ -2230,8 +2155,7 @@ def copy_pair_(dst0, src0, dst1, src1):
     if (all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts) and src0.shape == dst0.shape
             and src1.shape == dst1.shape and dst0.numel() == dst1.numel() and dst0.numel() % 4 == 0
             and all(t.data_ptr() % 16 == 0 for t in ts)):
-        L.check(L.lib().mi_copy_pair_f32(L.ptr(dst0), L.ptr(src0), L.ptr(dst1), L.ptr(src1), dst0.numel(), L.stream()),
-                "mi_copy_pair_f32")
+        L.call("mi_copy_pair_f32", dst0, src0, dst1, src1, dst0.numel())
         return
     dst0.copy_(src0)
     dst1.copy_(src1)
@@ -2242,8 +2166,7 @@ def queue_enqueue_(queue, queue_ptr, keys):
     b = keys.shape[0]
     if r % b != 0:
         raise AssertionError("queue size must be a multiple of the batch (models/moco.py:47)")
-    L.check(L.lib().mi_queue_enqueue(L.ptr(queue), L.ptr(queue_ptr), L.ptr(keys), b, c, r, L.stream()),
-            "mi_queue_enqueue")
+    L.call("mi_queue_enqueue", queue, queue_ptr, keys, b, c, r)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2256,8 +2179,7 @@ class _MaxPool2dCeilFn(torch.autograd.Function):
         ho, wo = (h + k - 1) // k, (w + k - 1) // k
         y = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
         arg = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device) if x.requires_grad else None
-        L.check(L.lib().mi_maxpool2d_ceil_fwd(L.ptr(x), L.ptr(y), L.ptr(arg), n, h, w, c, k, L.stream()),
-                "mi_maxpool2d_ceil_fwd")
+        L.call("mi_maxpool2d_ceil_fwd", x, y, arg, n, h, w, c, k)
         ctx.save_for_backward(arg)
         ctx.geom = (x.shape, k)
         return y
@@ -2268,8 +2190,7 @@ class _MaxPool2dCeilFn(torch.autograd.Function):
         shape, k = ctx.geom
         n, h, w, c = shape
         dx = torch.empty(shape, dtype=torch.float32, device=dy.device)
-        L.check(L.lib().mi_maxpool2d_ceil_bwd(L.ptr(dy.contiguous()), L.ptr(arg), L.ptr(dx), n, h, w, c, k, L.stream()),
-                "mi_maxpool2d_ceil_bwd")
+        L.call("mi_maxpool2d_ceil_bwd", dy.contiguous(), arg, dx, n, h, w, c, k)
         return dx, None
 
 
@@ -2288,7 +2209,7 @@ def _colsum_job(dy2d, param):
         ws = _ws(lib.mi_colreduce_workspace_bytes(m, c), dy2d.device, "colreduce")
         sums = torch.empty(2 * c, dtype=torch.float64, device=dy2d.device)
         with dest as tgt:
-            L.check(lib.mi_colsum(L.ptr(dy2d), m, c, L.ptr(tgt), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream()), "mi_colsum")
+            L.call("mi_colsum", dy2d, m, c, tgt, sums, ws, ws.numel())
     return launch
 
 
@@ -2306,8 +2227,7 @@ class _ConvT2x2Fn(torch.autograd.Function):
         co = mod.co
         t = conv_fwd(x, mod.gemm_view(), 1, 1, 0, owner=mod.weight, inference=inference)
         y = torch.empty((n, ho, wo, co), dtype=torch.float32, device=x.device)
-        L.check(L.lib().mi_shuffle2x2_fwd(L.ptr(t), L.ptr(bias), L.ptr(y), n, h, wd, co, ho, wo, L.stream()),
-                "mi_shuffle2x2_fwd")
+        L.call("mi_shuffle2x2_fwd", t, bias, y, n, h, wd, co, ho, wo)
         ctx.save_for_backward(x)
         ctx.mod, ctx.out_hw = mod, (ho, wo)
         ctx.x_needs_grad = x.requires_grad
@@ -2322,7 +2242,7 @@ class _ConvT2x2Fn(torch.autograd.Function):
         ho, wo = ctx.out_hw
         dy = dy.contiguous()
         dt = torch.empty((n, h, wd, 4 * co), dtype=torch.float32, device=dy.device)
-        L.check(L.lib().mi_shuffle2x2_bwd(L.ptr(dy), L.ptr(dt), n, h, wd, co, ho, wo, L.stream()), "mi_shuffle2x2_bwd")
+        L.call("mi_shuffle2x2_bwd", dy, dt, n, h, wd, co, ho, wo)
         if mod.bias is not None and mod.bias.requires_grad:
             _colsum_into(dy.view(-1, co), mod.bias)
         if mod.weight.requires_grad:
@@ -2330,8 +2250,7 @@ class _ConvT2x2Fn(torch.autograd.Function):
             geom = _Geom((n, 1, h, wd, ci), 4 * co, (1, 1, 1), 1, (0, 0, 0))
             ws = geom.workspace(x.device)
             with _GradInto(mod.weight) as tgt:
-                L.check(L.lib().mi_conv_wgrad_f32(L.ptr(x), L.ptr(dt), L.ptr(tgt), geom.ref, L.ptr(ws), ws.numel(), None, L.stream()),
-                        "mi_conv_wgrad_f32")
+                L.call("mi_conv_wgrad_f32", x, dt, tgt, geom.ref, ws, ws.numel(), None)
         dx = conv_dgrad(dt, mod.gemm_view(), x.shape, 1, 1, 0) if ctx.x_needs_grad else None
         return dx, None, None, None, None, None, None
 
@@ -2366,7 +2285,7 @@ class _ConcatFn(torch.autograd.Function):
         ca, cb = a.shape[-1], b.shape[-1]
         m = a.numel() // ca
         out = torch.empty(a.shape[:-1] + (ca + cb,), dtype=torch.float32, device=a.device)
-        L.check(L.lib().mi_concat_channels(L.ptr(a), ca, L.ptr(b), cb, L.ptr(out), m, L.stream()), "mi_concat_channels")
+        L.call("mi_concat_channels", a, ca, b, cb, out, m)
         ctx.shapes = (a.shape, b.shape)
         return out
 
@@ -2375,8 +2294,7 @@ class _ConcatFn(torch.autograd.Function):
         sa, sb = ctx.shapes
         da = torch.empty(sa, dtype=torch.float32, device=dout.device)
         db = torch.empty(sb, dtype=torch.float32, device=dout.device)
-        L.check(L.lib().mi_split_channels(L.ptr(dout.contiguous()), L.ptr(da), sa[-1], L.ptr(db), sb[-1],
-                                          da.numel() // sa[-1], L.stream()), "mi_split_channels")
+        L.call("mi_split_channels", dout.contiguous(), da, sa[-1], db, sb[-1], da.numel() // sa[-1])
         return da, db
 
 
@@ -2390,7 +2308,7 @@ class _BiasAddFn(torch.autograd.Function):
     def forward(ctx, x, bias, holder):
         y = x.clone()
         c = x.shape[-1]
-        L.check(L.lib().mi_bias_add(L.ptr(y), L.ptr(bias), y.numel() // c, c, L.stream()), "mi_bias_add")
+        L.call("mi_bias_add", y, bias, y.numel() // c, c)
         ctx.holder = holder
         return y
 
@@ -2415,7 +2333,7 @@ class _ZHeadFn(torch.autograd.Function):
         n, d, h, wd, c = x.shape
         k = mod.k_out
         y = torch.empty((n, d, h, wd, k), dtype=torch.float32, device=x.device)
-        L.check(L.lib().mi_zhead_fwd(L.ptr(x), L.ptr(w), L.ptr(y), n, d, h * wd, c, k, L.stream()), "mi_zhead_fwd")
+        L.call("mi_zhead_fwd", x, w, y, n, d, h * wd, c, k)
         ctx.save_for_backward(x)
         ctx.mod = mod
         ctx.x_needs_grad = x.requires_grad
@@ -2432,8 +2350,7 @@ class _ZHeadFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.x_needs_grad else None
         ws = _ws(lib.mi_zhead_bwd_workspace_bytes(n, d, h * wd, c, k), x.device, "zhead")
         with _GradInto(mod.weight if mod.weight.requires_grad else None) as tgt:
-            L.check(lib.mi_zhead_bwd(L.ptr(x), L.ptr(mod.weight), L.ptr(dy), L.ptr(dx), L.ptr(tgt), n, d, h * wd, c, k,
-                                     L.ptr(ws), ws.numel(), L.stream()), "mi_zhead_bwd")
+            L.call("mi_zhead_bwd", x, mod.weight, dy, dx, tgt, n, d, h * wd, c, k, ws, ws.numel())
         return dx, None, None
 
 
@@ -2482,7 +2399,7 @@ def kmeans_prep(centroids, image=None):
         L.check(-3, "mi_kmeans_image_bytes(d=%d, k=%d)" % (d, k))
     if image is None:
         image = torch.empty(nbytes, dtype=torch.uint8, device=c.device)
-    L.check(L.lib().mi_kmeans_prep(L.ptr(c), d, k, L.ptr(image), L.stream()), "mi_kmeans_prep")
+    L.call("mi_kmeans_prep", c, d, k, image)
     return image
 
 
@@ -2490,7 +2407,7 @@ def kmeans_xnorm(x, out=None):
     x = _km_x(x)
     if out is None:
         out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    L.check(L.lib().mi_kmeans_xnorm(L.ptr(x), x.shape[0], x.shape[1], L.ptr(out), L.stream()), "mi_kmeans_xnorm")
+    L.call("mi_kmeans_xnorm", x, x.shape[0], x.shape[1], out)
     return out
 
 
@@ -2506,8 +2423,7 @@ def kmeans_assign(x, xnorm, image, k, labels=None, dist=None, ws=None):
         labels = torch.empty(n, dtype=torch.int32, device=x.device)
     if dist is None:
         dist = torch.empty(n, dtype=torch.float32, device=x.device)
-    L.check(L.lib().mi_kmeans_assign(L.ptr(x), L.ptr(xnorm), L.ptr(image), n, d, k, L.ptr(labels), L.ptr(dist), L.ptr(ws),
-                                     ws.numel(), L.stream()), "mi_kmeans_assign")
+    L.call("mi_kmeans_assign", x, xnorm, image, n, d, k, labels, dist, ws, ws.numel())
     return labels, dist
 
 
@@ -2526,8 +2442,7 @@ def kmeans_update(x, labels, centroids, counts=None, obj=None, nsplit=None, ws=N
         ws = kmeans_workspace(n, d, k, x.device)
     if counts is None:
         counts = torch.empty(k, dtype=torch.int32, device=x.device)
-    L.check(L.lib().mi_kmeans_update(L.ptr(x), L.ptr(labels), n, d, k, L.ptr(c), L.ptr(counts), L.ptr(obj), L.ptr(nsplit),
-                                     L.ptr(ws), ws.numel(), L.stream()), "mi_kmeans_update")
+    L.call("mi_kmeans_update", x, labels, n, d, k, c, counts, obj, nsplit, ws, ws.numel())
     return counts
 
 
@@ -2558,8 +2473,7 @@ def knn_search(q, x, k, metric="ip", exclude_self=False, n_split=0, out=None):
     if tuple(index.shape) != (m, k) or tuple(value.shape) != (m, k) or not index.is_contiguous() or not value.is_contiguous():
         raise L.HipExtensionError("out must be contiguous (%d, %d) tensors" % (m, k))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-    L.check(L.lib().mi_knn_search(L.ptr(q), L.ptr(x), m, n, d, k, KNN_METRICS[metric], excl, n_split, L.ptr(index), L.ptr(value),
-                                  L.ptr(ws), ws.numel(), L.stream()), "mi_knn_search" + what)
+    L.call("mi_knn_search", q, x, m, n, d, k, KNN_METRICS[metric], excl, n_split, index, value, ws, ws.numel())
     return index, value
 
 
@@ -2599,8 +2513,7 @@ def tsne_affinities(dist, perplexity):
     n, k = dist.shape
     p = torch.empty(n, k, dtype=torch.float32, device=dist.device)
     beta = torch.empty(n, dtype=torch.float32, device=dist.device)
-    L.check(L.lib().mi_tsne_affinities(L.ptr(dist), n, k, float(perplexity), L.ptr(p), L.ptr(beta), L.stream()),
-            "mi_tsne_affinities(N=%d, K=%d, perplexity=%g)" % (n, k, perplexity))
+    L.call("mi_tsne_affinities", dist, n, k, float(perplexity), p, beta)
     return p, beta
 
 
@@ -2629,9 +2542,7 @@ def tsne_gradient(y, index, p, rev_ptr, rev_edge, exaggeration=1.0, n_split=0, k
     grad, z, klt = _table(out[0], "out[0]", (n, 2)), _table(out[1], "out[1]", (1,)), out[2] if kl else None
     if klt is not None:
         _table(klt, "out[2]", (1,))
-    L.check(L.lib().mi_tsne_gradient(L.ptr(y), L.ptr(index), L.ptr(p), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, float(exaggeration),
-                                     n_split, L.ptr(grad), L.ptr(z), L.ptr(klt), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_tsne_gradient(N=%d, K=%d, n_split=%d)" % (n, k, n_split))
+    L.call("mi_tsne_gradient", y, index, p, rev_ptr, rev_edge, n, k, float(exaggeration), n_split, grad, z, klt, ws, ws.numel())
     return grad, z, klt
 
 
@@ -2642,8 +2553,7 @@ def tsne_update(y, grad, velocity, gains, momentum, lr, min_gain=0.01):
         _table(t, name, tuple(y.shape))
     if y.shape[1] != 2:
         raise L.HipExtensionError("y must be (N, 2), got %s" % (tuple(y.shape),))
-    L.check(L.lib().mi_tsne_update(L.ptr(y), L.ptr(grad), L.ptr(velocity), L.ptr(gains), y.shape[0], float(momentum), float(lr),
-                                   float(min_gain), L.stream()), "mi_tsne_update(N=%d)" % y.shape[0])
+    L.call("mi_tsne_update", y, grad, velocity, gains, y.shape[0], float(momentum), float(lr), float(min_gain))
     return y
 
 
@@ -2656,8 +2566,7 @@ def umap_smooth_knn(dist2, mean_all):
     n, k = dist2.shape
     rho = torch.empty(n, dtype=torch.float32, device=dist2.device)
     sigma, w = torch.empty_like(rho), torch.empty_like(dist2)
-    L.check(L.lib().mi_umap_smooth_knn(L.ptr(dist2), n, k, float(mean_all), L.ptr(rho), L.ptr(sigma), L.ptr(w), L.stream()),
-            "mi_umap_smooth_knn(N=%d, k=%d)" % (n, k))
+    L.call("mi_umap_smooth_knn", dist2, n, k, float(mean_all), rho, sigma, w)
     return rho, sigma, w
 
 
@@ -2673,8 +2582,7 @@ def umap_union(index, w, rev_ptr, rev_edge, n_epochs, wmax=None, out=None):
                torch.empty(n, k, dtype=torch.float64, device=w.device))
     wsym, mutual, eps = _table(out[0], "out[0]", (n, k)), _table(out[1], "out[1]", (n, k), torch.uint8), \
         _table(out[2], "out[2]", (n, k), torch.float64)
-    L.check(L.lib().mi_umap_union(L.ptr(index), L.ptr(w), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, L.ptr(wmax), int(n_epochs),
-                                  L.ptr(wsym), L.ptr(mutual), L.ptr(eps), L.stream()), "mi_umap_union(N=%d, k=%d)" % (n, k))
+    L.call("mi_umap_union", index, w, rev_ptr, rev_edge, n, k, wmax, int(n_epochs), wsym, mutual, eps)
     return wsym, mutual, eps
 
 
@@ -2684,8 +2592,7 @@ def umap_rowmax(index, wsym, label, rev_ptr, rev_edge, f_far, f_unknown):
     n, k = _graph_tables(index, rev_ptr, rev_edge, wsym=(wsym, torch.float32))
     _table(label, "label", (n,), torch.int32)
     rowmax = torch.empty(n, dtype=torch.float64, device=wsym.device)
-    L.check(L.lib().mi_umap_rowmax(L.ptr(index), L.ptr(wsym), L.ptr(label), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, float(f_far),
-                                   float(f_unknown), L.ptr(rowmax), L.stream()), "mi_umap_rowmax(N=%d, k=%d)" % (n, k))
+    L.call("mi_umap_rowmax", index, wsym, label, rev_ptr, rev_edge, n, k, float(f_far), float(f_unknown), rowmax)
     return rowmax
 
 
@@ -2701,9 +2608,7 @@ def umap_supervise(index, wsym, label, rowmax, f_far, f_unknown, n_epochs, wmax=
     if out is None:
         out = (torch.empty(n, k, dtype=torch.float32, device=wsym.device), torch.empty(n, k, dtype=torch.float64, device=wsym.device))
     wsup, eps = _table(out[0], "out[0]", (n, k)), _table(out[1], "out[1]", (n, k), torch.float64)
-    L.check(L.lib().mi_umap_supervise(L.ptr(index), L.ptr(wsym), L.ptr(label), L.ptr(rowmax), n, k, float(f_far), float(f_unknown),
-                                      L.ptr(wmax), int(n_epochs), L.ptr(wsup), L.ptr(eps), L.stream()),
-            "mi_umap_supervise(N=%d, k=%d)" % (n, k))
+    L.call("mi_umap_supervise", index, wsym, label, rowmax, n, k, float(f_far), float(f_unknown), wmax, int(n_epochs), wsup, eps)
     return wsup, eps
 
 
@@ -2718,9 +2623,8 @@ def umap_epoch(y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, epoch, n_epoc
     if y_out.data_ptr() == y_in.data_ptr():
         raise L.HipExtensionError("y_out may not alias y_in")
     n, k = _graph_tables(index, rev_ptr, rev_edge, n=n, mutual=(mutual, torch.uint8), eps=(eps, torch.float64))
-    L.check(L.lib().mi_umap_epoch(L.ptr(y_in), L.ptr(y_out), L.ptr(index), L.ptr(rev_ptr), L.ptr(rev_edge), L.ptr(mutual), L.ptr(eps),
-                                  n, k, int(epoch), int(n_epochs), float(a), float(b), int(seed) & (2 ** 64 - 1), L.stream()),
-            "mi_umap_epoch(N=%d, k=%d, epoch %d of %d)" % (n, k, epoch, n_epochs))
+    L.call("mi_umap_epoch", y_in, y_out, index, rev_ptr, rev_edge, mutual, eps, n, k, int(epoch), int(n_epochs), float(a), float(b),
+           int(seed) & (2 ** 64 - 1))
     return y_out
 
 
@@ -2735,8 +2639,7 @@ def graph_components(index, eps, mutual, rev_ptr, rev_edge):
     sweeps = 0
     while True:
         flag.zero_()
-        L.check(L.lib().mi_graph_components(L.ptr(index), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k, L.ptr(a),
-                                            L.ptr(b), L.ptr(flag), L.stream()), "mi_graph_components(N=%d, k=%d)" % (n, k))
+        L.call("mi_graph_components", index, eps, mutual, rev_ptr, rev_edge, n, k, a, b, flag)
         a, b = b, a
         sweeps += 1
         if int(flag.item()) == 0:
@@ -2749,8 +2652,7 @@ def spectral_degree(index, wsym, eps, mutual, rev_ptr, rev_edge):
                          wsym=(wsym, torch.float32))
     deg = torch.empty(n, dtype=torch.float64, device=index.device)
     dis = torch.empty_like(deg)
-    L.check(L.lib().mi_spectral_degree(L.ptr(index), L.ptr(wsym), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k,
-                                       L.ptr(deg), L.ptr(dis), L.stream()), "mi_spectral_degree(N=%d, k=%d)" % (n, k))
+    L.call("mi_spectral_degree", index, wsym, eps, mutual, rev_ptr, rev_edge, n, k, deg, dis)
     return deg, dis
 
 
@@ -2768,9 +2670,7 @@ def spectral_spmv(index, wsym, eps, mutual, rev_ptr, rev_edge, dis, x, y=None, r
     _table(y, "y", (nrows,), torch.float64)
     if y.data_ptr() == x.data_ptr():
         raise L.HipExtensionError("y may not alias x")
-    L.check(L.lib().mi_spectral_spmv(L.ptr(index), L.ptr(wsym), L.ptr(eps), L.ptr(mutual), L.ptr(rev_ptr), L.ptr(rev_edge), n, k,
-                                     L.ptr(dis), L.ptr(x), L.ptr(y), int(row0), nrows, L.stream()),
-            "mi_spectral_spmv(N=%d, k=%d, rows %d..%d)" % (n, k, row0, row0 + nrows))
+    L.call("mi_spectral_spmv", index, wsym, eps, mutual, rev_ptr, rev_edge, n, k, dis, x, y, int(row0), nrows)
     return y
 
 
@@ -2797,8 +2697,7 @@ def spectral_dots(Q, w, c=None):
     """c = Q^T w (m,) float64 for the m rows of Q (m, n); a fixed summation order (a norm: Q = w[None])."""
     m, n, ldq, c = _sp_basis(Q, w, c)
     ws = _sp_ws(m, n, Q.device)
-    L.check(L.lib().mi_spectral_dots(L.ptr(Q), ldq, m, n, L.ptr(w), L.ptr(c), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_spectral_dots(m=%d, n=%d)" % (m, n))
+    L.call("mi_spectral_dots", Q, ldq, m, n, w, c, ws, ws.numel())
     return c
 
 
@@ -2806,16 +2705,14 @@ def spectral_orth(Q, w, c=None):
     """c = Q^T w, then w -= Q c in place (one Gram-Schmidt pass against the rows of Q; two passes are `twice is enough`)."""
     m, n, ldq, c = _sp_basis(Q, w, c)
     ws = _sp_ws(m, n, Q.device)
-    L.check(L.lib().mi_spectral_orth(L.ptr(Q), ldq, m, n, L.ptr(w), L.ptr(c), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_spectral_orth(m=%d, n=%d)" % (m, n))
+    L.call("mi_spectral_orth", Q, ldq, m, n, w, c, ws, ws.numel())
     return c
 
 
 def spectral_combine(Q, c, w, beta=0.0):
     """w = beta w - Q c in place (beta = 0: w is only written), the rows of Q taken in order."""
     m, n, ldq, c = _sp_basis(Q, w, c)
-    L.check(L.lib().mi_spectral_combine(L.ptr(Q), ldq, m, n, L.ptr(c), L.ptr(w), float(beta), L.stream()),
-            "mi_spectral_combine(m=%d, n=%d)" % (m, n))
+    L.call("mi_spectral_combine", Q, ldq, m, n, c, w, float(beta))
     return w
 
 
@@ -2855,7 +2752,6 @@ def match_coordinates(preds, targets, pred_off, targ_off, radius):
         L.check(-3, what + ": more than %d picks or targets in one image" % MATCH_MAX_POINTS)
     ws = L.workspace(nbytes, dev, "match")
     po32, to32 = po.astype(np.int32), to.astype(np.int32)
-    L.check(L.lib().mi_match_coordinates(L.ptr(preds), L.ptr(targets), po32.ctypes.data_as(ctypes.c_void_p),
-                                         to32.ctypes.data_as(ctypes.c_void_p), n_img, float(radius), L.ptr(p2t), L.ptr(dist),
-                                         L.ptr(total), L.ptr(ws), ws.numel(), L.stream()), what)
+    L.call("mi_match_coordinates", preds, targets, po32.ctypes.data_as(ctypes.c_void_p), to32.ctypes.data_as(ctypes.c_void_p), n_img,
+           float(radius), p2t, dist, total, ws, ws.numel())
     return p2t, dist, total

@@ -17,11 +17,10 @@ def _nms_generic(heat, kd, kh):
     heat = heat.contiguous()
     out = torch.empty_like(heat)
     b, c, d, h, w = heat.shape
-    fn = L.lib().mi_nms3d
     for i in range(b * c):
         src = heat.view(b * c, d, h, w)[i]
         dst = out.view(b * c, d, h, w)[i]
-        L.check(fn(L.ptr(src), L.ptr(dst), d, h, w, kd, kh, L.stream()), "mi_nms3d")
+        L.call("mi_nms3d", src, dst, d, h, w, kd, kh)
     return out
 
 
@@ -53,18 +52,20 @@ def _decode_fused(vol, kernel, K, fiber, apply_sigmoid, heat_out, dets=None):
     """One volume through mi_sigmoid_nms_topk; `dets` (K,5) is written in place when given (a row of the batch's
     output: no stack / copy kernel afterwards)."""
     d, h, w = vol.shape
-    lib = L.lib()
-    ws = _decode_workspace(lib.mi_decode_workspace_bytes(d, h, w, K), vol.device)
+    ws = _decode_workspace(L.lib().mi_decode_workspace_bytes(d, h, w, K), vol.device)
     if dets is None:
         dets = torch.empty((K, 5), dtype=torch.float32, device=vol.device)
     nvalid = torch.empty((1,), dtype=torch.int32, device=vol.device)
-    rc = lib.mi_sigmoid_nms_topk(L.ptr(vol), L.ptr(heat_out), d, h, w, kernel, int(bool(fiber)),
-                                 int(bool(apply_sigmoid)) | _WS_CLEAN, K, L.ptr(dets), L.ptr(nvalid),
-                                 L.ptr(ws), ws.numel(), L.stream())
-    if rc:
-        L.drop_workspace(vol.device, "decode")
-    L.check(rc, "mi_sigmoid_nms_topk")
+    _nms_topk(vol, heat_out, d, h, w, kernel, int(bool(fiber)), int(bool(apply_sigmoid)) | _WS_CLEAN, K, dets, nvalid, ws, ws.numel())
     return dets, nvalid
+
+
+def _nms_topk(vol, *args):
+    try:
+        L.call("mi_sigmoid_nms_topk", vol, *args)
+    except L.HipExtensionError:
+        L.drop_workspace(vol.device, "decode")          # the header of the workspace may no longer be clean
+        raise
 
 
 _WS_CLEAN = 2       # include/cetpick_hip.h: bit 1 of `apply_sigmoid` - the header of this workspace is kept clean
@@ -74,7 +75,7 @@ def _decode_workspace(nbytes, device):
     """The decode workspace, its header zeroed once per allocation (mi_decode_workspace_init); every call made with
     _WS_CLEAN leaves it zeroed again, so a decode is march + filter + final and no clearing pass."""
     def init(buf):
-        L.check(L.lib().mi_decode_workspace_init(L.ptr(buf), buf.numel(), L.stream()), "mi_decode_workspace_init")
+        L.call("mi_decode_workspace_init", buf, buf.numel())
     return L.workspace(nbytes, device, "decode", init=init)
 
 
@@ -124,13 +125,11 @@ def _topk(scores, K=900):
     s_l, z_l, y_l, x_l, i_l = [], [], [], [], []
     for b in range(batch):
         d, h, w = depth, height, width
-        lib = L.lib()
-        ws = _decode_workspace(lib.mi_decode_workspace_bytes(d, h, w, K), scores.device)
+        ws = _decode_workspace(L.lib().mi_decode_workspace_bytes(d, h, w, K), scores.device)
         dets = torch.empty((K, 5), dtype=torch.float32, device=scores.device)
-        # window (1,1,1): every positive voxel is its own maximum -> plain top-K
-        vol = scores[b, 0]
-        rc = _topk_plain(vol, K, dets, ws)
-        L.check(rc, "mi_sigmoid_nms_topk")
+        # window (1,1,1): every positive voxel is its own maximum -> plain top-K;
+        # fiber mode with k=1 pools nothing (windows (1,1,1) then (1,1,1))
+        _nms_topk(scores[b, 0], None, d, h, w, 1, 1, _WS_CLEAN, K, dets, None, ws, ws.numel())
         xs = (dets[:, 0] - 0.25).int()
         ys = dets[:, 1] - 0.25
         zs = dets[:, 2].int()
@@ -138,16 +137,6 @@ def _topk(scores, K=900):
         i_l.append((zs.long() * h + ys.long()) * w + xs.long())
     return (torch.stack(s_l).view(batch, 1, K), torch.stack(z_l), torch.stack(y_l),
             torch.stack(x_l), torch.stack(i_l))
-
-
-def _topk_plain(vol, K, dets, ws):
-    d, h, w = vol.shape
-    # fiber mode with k=1 pools nothing (windows (1,1,1) then (1,1,1))
-    rc = L.lib().mi_sigmoid_nms_topk(L.ptr(vol), None, d, h, w, 1, 1, _WS_CLEAN, K, L.ptr(dets), None,
-                                     L.ptr(ws), ws.numel(), L.stream())
-    if rc:
-        L.drop_workspace(vol.device, "decode")
-    return rc
 
 
 def non_maximum_suppression_3d(x, d, scale=1.0, threshold=-np.inf):

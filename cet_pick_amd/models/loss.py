@@ -31,18 +31,15 @@ class _VoxelLossFn(torch.autograd.Function):
         n = p.numel()
         if n == 0:
             raise ValueError("voxel loss of an empty tensor: pred %s, gt %s" % (tuple(pred.shape), tuple(gt.shape)))
-        lib = L.lib()
-        ws = L.workspace(lib.mi_voxel_loss_workspace_bytes(n), p.device, "voxloss")
+        ws = L.workspace(L.lib().mi_voxel_loss_workspace_bytes(n), p.device, "voxloss")
         sums = torch.empty(11, dtype=torch.float64, device=p.device)
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         if mode == "pu":
-            rc = lib.mi_pu_focal_loss_fwd(L.ptr(p), L.ptr(g), n, float(tau), float(beta), L.ptr(sums), L.ptr(loss),
-                                          L.ptr(ws), ws.numel(), L.stream())
+            L.call("mi_pu_focal_loss_fwd", p, g, n, float(tau), float(beta), sums, loss, ws, ws.numel())
         elif mode == "focal":
-            rc = lib.mi_focal_loss_fwd(L.ptr(p), L.ptr(g), n, L.ptr(sums), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream())
+            L.call("mi_focal_loss_fwd", p, g, n, sums, loss, ws, ws.numel())
         else:
-            rc = lib.mi_mse_loss_fwd(L.ptr(p), L.ptr(g), n, L.ptr(sums), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream())
-        L.check(rc, "voxel loss fwd")
+            L.call("mi_mse_loss_fwd", p, g, n, sums, loss, ws, ws.numel())
         ctx.save_for_backward(p, g, sums)
         ctx.mode, ctx.tau, ctx.shape_p, ctx.shape_g = mode, float(tau), pred.shape, gt.shape
         ctx.g_needs = gt.requires_grad
@@ -53,18 +50,16 @@ class _VoxelLossFn(torch.autograd.Function):
     def backward(ctx, dloss):
         p, g, sums = ctx.saved_tensors
         n = p.numel()
-        lib = L.lib()
         dl = dloss.contiguous().float()
         dp = torch.empty_like(p)
         dg = None
         if ctx.mode == "pu":
-            rc = lib.mi_pu_focal_loss_bwd(L.ptr(p), L.ptr(g), n, ctx.tau, L.ptr(sums), L.ptr(dl), L.ptr(dp), L.stream())
+            L.call("mi_pu_focal_loss_bwd", p, g, n, ctx.tau, sums, dl, dp)
         elif ctx.mode == "focal":
-            rc = lib.mi_focal_loss_bwd(L.ptr(p), L.ptr(g), n, L.ptr(sums), L.ptr(dl), L.ptr(dp), L.stream())
+            L.call("mi_focal_loss_bwd", p, g, n, sums, dl, dp)
         else:
             dg = torch.empty_like(g) if ctx.g_needs else None
-            rc = lib.mi_mse_loss_bwd(L.ptr(p), L.ptr(g), n, L.ptr(sums), L.ptr(dl), L.ptr(dp), L.ptr(dg), L.stream())
-        L.check(rc, "voxel loss bwd")
+            L.call("mi_mse_loss_bwd", p, g, n, sums, dl, dp, dg)
         return dp.view(ctx.shape_p), (dg.view(ctx.shape_g) if dg is not None else None), None, None, None
 
 
@@ -120,12 +115,10 @@ class _PUGELossFn(torch.autograd.Function):
         n = p.numel()
         if n == 0:
             raise ValueError("voxel loss of an empty tensor: pred %s, gt %s" % (tuple(pred.shape), tuple(gt.shape)))
-        lib = L.lib()
-        ws = L.workspace(lib.mi_pu_ge_loss_workspace_bytes(n), p.device, "geloss")
+        ws = L.workspace(L.lib().mi_pu_ge_loss_workspace_bytes(n), p.device, "geloss")
         sums = torch.empty(16, dtype=torch.float64, device=p.device)
         loss = torch.empty((), dtype=torch.float32, device=p.device)
-        L.check(lib.mi_pu_ge_loss_fwd(L.ptr(p), L.ptr(g), n, float(tau), float(slack), float(entropy_penalty), L.ptr(sums),
-                                      L.ptr(loss), L.ptr(ws), ws.numel(), L.stream()), "mi_pu_ge_loss_fwd")
+        L.call("mi_pu_ge_loss_fwd", p, g, n, float(tau), float(slack), float(entropy_penalty), sums, loss, ws, ws.numel())
         ctx.save_for_backward(p, g, sums)
         ctx.slack, ctx.shape_p = float(slack), pred.shape
         ctx.sums = sums
@@ -136,8 +129,7 @@ class _PUGELossFn(torch.autograd.Function):
         p, g, sums = ctx.saved_tensors
         dl = dloss.contiguous().float()
         dp = torch.empty_like(p)
-        L.check(L.lib().mi_pu_ge_loss_bwd(L.ptr(p), L.ptr(g), p.numel(), ctx.slack, L.ptr(sums), L.ptr(dl), L.ptr(dp), L.stream()),
-                "mi_pu_ge_loss_bwd")
+        L.call("mi_pu_ge_loss_bwd", p, g, p.numel(), ctx.slack, sums, dl, dp)
         return dp.view(ctx.shape_p), None, None, None, None
 
 
@@ -180,8 +172,7 @@ class _UclRowSumsFn(torch.autograd.Function):
         n2, dim = feat.shape
         dev = feat.device
         outs = [torch.empty(n2, dtype=torch.float32, device=dev) for _ in range(5)]
-        L.check(L.lib().mi_ucl_rowsums_fwd(L.ptr(feat), L.ptr(cls), n2, dim, float(inv_T), *[L.ptr(o) for o in outs],
-                                           L.stream()), "mi_ucl_rowsums_fwd")
+        L.call("mi_ucl_rowsums_fwd", feat, cls, n2, dim, float(inv_T), *outs)
         ctx.save_for_backward(feat, cls, outs[0])
         ctx.inv_T = float(inv_T)
         ctx.mark_non_differentiable(outs[0])
@@ -195,9 +186,7 @@ class _UclRowSumsFn(torch.autograd.Function):
         g_all, g_pos, g_other, g_pair = z(g_all), z(g_pos), z(g_other), z(g_pair)
         dfeat = torch.empty_like(feat)
         rng = torch.empty(2, dtype=torch.float32, device=feat.device)      # (largest row maximum, fast-path flag): decided on the device
-        L.check(L.lib().mi_ucl_rowsums_bwd_ranged(L.ptr(feat), L.ptr(cls), n2, dim, ctx.inv_T, L.ptr(rowmax), L.ptr(g_all),
-                                                  L.ptr(g_pos), L.ptr(g_other), L.ptr(g_pair), L.ptr(dfeat), L.ptr(rng), L.stream()),
-                "mi_ucl_rowsums_bwd_ranged")
+        L.call("mi_ucl_rowsums_bwd_ranged", feat, cls, n2, dim, ctx.inv_T, rowmax, g_all, g_pos, g_other, g_pair, dfeat, rng)
         return dfeat, None, None
 
 
@@ -227,15 +216,13 @@ class _SupConPNFn(torch.autograd.Function):
             raise L.HipExtensionError("mi_supcon_pn_rows takes contiguous features %s and one contiguous class byte per row, got %s"
                                       % (tuple(feat.shape), tuple(cls.shape)))
         n2, dim = feat.shape
-        dev, lib = feat.device, L.lib()
+        dev = feat.device
         rowmax, s_all, s_pos, s_other, e_pair, g_all = (torch.empty(n2, dtype=torch.float32, device=dev) for _ in range(6))
-        L.check(lib.mi_ucl_rowsums_fwd(L.ptr(feat), L.ptr(cls), n2, dim, float(inv_T), L.ptr(rowmax), L.ptr(s_all), L.ptr(s_pos),
-                                       L.ptr(s_other), L.ptr(e_pair), L.stream()), "mi_ucl_rowsums_fwd")
-        ws = L.workspace(lib.mi_supcon_pn_rows_workspace_bytes(n2), dev, "supconpn")
+        L.call("mi_ucl_rowsums_fwd", feat, cls, n2, dim, float(inv_T), rowmax, s_all, s_pos, s_other, e_pair)
+        ws = L.workspace(L.lib().mi_supcon_pn_rows_workspace_bytes(n2), dev, "supconpn")
         sums = torch.empty(72, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        L.check(lib.mi_supcon_pn_rows_fwd(L.ptr(feat), L.ptr(cls), n2, dim, float(inv_T), L.ptr(rowmax), L.ptr(s_all), L.ptr(g_all),
-                                          L.ptr(sums), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream()), "mi_supcon_pn_rows_fwd")
+        L.call("mi_supcon_pn_rows_fwd", feat, cls, n2, dim, float(inv_T), rowmax, s_all, g_all, sums, loss, ws, ws.numel())
         ctx.save_for_backward(feat, cls, rowmax, g_all, sums)
         ctx.inv_T = float(inv_T)
         ctx.sums = sums
@@ -245,16 +232,12 @@ class _SupConPNFn(torch.autograd.Function):
     def backward(ctx, dloss):
         feat, cls, rowmax, g_all, sums = ctx.saved_tensors
         n2, dim = feat.shape
-        lib = L.lib()
         dl = dloss.contiguous().float()
         zero = torch.zeros(n2, dtype=torch.float32, device=feat.device)
         dfeat = torch.empty_like(feat)
         rng = torch.empty(2, dtype=torch.float32, device=feat.device)
-        L.check(lib.mi_ucl_rowsums_bwd_ranged(L.ptr(feat), L.ptr(cls), n2, dim, ctx.inv_T, L.ptr(rowmax), L.ptr(g_all), L.ptr(zero),
-                                              L.ptr(zero), L.ptr(zero), L.ptr(dfeat), L.ptr(rng), L.stream()),
-                "mi_ucl_rowsums_bwd_ranged")
-        L.check(lib.mi_supcon_pn_rows_bwd(L.ptr(feat), L.ptr(cls), n2, dim, ctx.inv_T, L.ptr(sums), L.ptr(dl), L.ptr(dfeat), L.stream()),
-                "mi_supcon_pn_rows_bwd")
+        L.call("mi_ucl_rowsums_bwd_ranged", feat, cls, n2, dim, ctx.inv_T, rowmax, g_all, zero, zero, zero, dfeat, rng)
+        L.call("mi_supcon_pn_rows_bwd", feat, cls, n2, dim, ctx.inv_T, sums, dl, dfeat)
         return dfeat, None, None
 
 

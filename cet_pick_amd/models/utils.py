@@ -12,7 +12,7 @@ class _SigmoidClampFn(torch.autograd.Function):
     def forward(ctx, x):
         xs = x.detach().clone().contiguous()
         y = torch.empty_like(xs)
-        L.check(L.lib().mi_sigmoid_clamp(L.ptr(xs), L.ptr(y), xs.numel(), L.stream()), "mi_sigmoid_clamp")
+        L.call("mi_sigmoid_clamp", xs, y, xs.numel())
         ctx.save_for_backward(y)
         return y
 
@@ -33,7 +33,7 @@ def _sigmoid(x):
     if not x.is_contiguous():
         raise L.HipExtensionError("_sigmoid needs a contiguous tensor (it works in place)")
     y = torch.empty_like(x)
-    L.check(L.lib().mi_sigmoid_clamp(L.ptr(x), L.ptr(y), x.numel(), L.stream()), "mi_sigmoid_clamp")
+    L.call("mi_sigmoid_clamp", x, y, x.numel())
     return y
 
 

@@ -191,8 +191,7 @@ class StepGraph:
         if self._graph is None:
             return None
         counts = (ctypes.c_int * 4)()
-        L.check(L.lib().mi_graph_node_counts(ctypes.c_void_p(self._graph.raw_cuda_graph()), ctypes.cast(counts, ctypes.c_void_p)),
-                "mi_graph_node_counts")
+        L.call("mi_graph_node_counts", ctypes.c_void_p(self._graph.raw_cuda_graph()), ctypes.cast(counts, ctypes.c_void_p))
         return dict(zip(("kernel", "memcpy", "memset", "other"), [int(c) for c in counts]))
 
     def close(self):

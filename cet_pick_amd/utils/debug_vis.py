@@ -51,7 +51,7 @@ def slice_minmax(vol, z0=0, nz=None):
     D, H, W = vol.shape
     nz = D - z0 if nz is None else nz
     out = torch.empty((max(int(nz), 0), 2), dtype=torch.float32, device=vol.device)
-    L.check(L.lib().mi_dbgvis_minmax(L.ptr(vol), D, H, W, int(z0), int(nz), L.ptr(out), L.stream()), "mi_dbgvis_minmax")
+    L.call("mi_dbgvis_minmax", vol, D, H, W, int(z0), int(nz), out)
     return out
 
 
@@ -78,9 +78,8 @@ def render(tomo, hm_pred, hm_gt, z0, nz, pred_dets, gt_dets, conf_thresh=CONF_TH
     elif out.dtype != torch.uint8 or not out.is_cuda or out.numel() < nbytes or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 device buffer of at least %d bytes" % nbytes)
     ws = L.workspace(max(lib.mi_dbgvis_workspace_bytes(nz, len(pred), len(gt)), 16), tomo.device, "debug_vis")
-    L.check(lib.mi_dbgvis_render(L.ptr(tomo), L.ptr(hm_pred), L.ptr(hm_gt), D, H, W, h, w, z0, nz, L.ptr(minmax), pred_p,
-                                 len(pred), gt_p, len(gt), float(conf_thresh), int(radius), L.ptr(out), L.ptr(ws), ws.numel(),
-                                 L.stream()), "mi_dbgvis_render")
+    L.call("mi_dbgvis_render", tomo, hm_pred, hm_gt, D, H, W, h, w, z0, nz, minmax, pred_p, len(pred), gt_p, len(gt), float(conf_thresh),
+           int(radius), out, ws, ws.numel())
     return out.reshape(-1)[:nbytes].view(4, nz, H, W, 3)
 
 

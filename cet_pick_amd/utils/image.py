@@ -32,8 +32,7 @@ def gaussian_filter(vol, sigma):
     d, h, w = v.shape
     out = torch.empty_like(v)
     tmp = torch.empty_like(v)
-    L.check(L.lib().mi_gauss3d_sep(L.ptr(v), L.ptr(out), L.ptr(tmp), d, h, w, float(sigma), L.stream()),
-            "mi_gauss3d_sep")
+    L.call("mi_gauss3d_sep", v, out, tmp, d, h, w, float(sigma))
     return out
 
 
@@ -52,9 +51,7 @@ def non_maximum_suppression_3d(x, d, scale=1.0, threshold=-np.inf, max_out=None)
     thr = float(threshold)
     if thr == -np.inf:
         thr = -3.4028234663852886e38  # every finite voxel passes, as in the reference
-    L.check(lib.mi_greedy_nms3d(L.ptr(v), D, H, W, float(d), float(scale), thr, L.ptr(scores),
-                                L.ptr(coords), L.ptr(n), max_out, L.ptr(ws), ws.numel(), L.stream()),
-            "mi_greedy_nms3d")
+    L.call("mi_greedy_nms3d", v, D, H, W, float(d), float(scale), thr, scores, coords, n, max_out, ws, ws.numel())
     k = int(n.item())
     if k < 0:
         raise L.HipExtensionError("greedy NMS overflow (code %d): raise max_out / too many candidates" % k)
@@ -105,10 +102,8 @@ def dog_pick(rec, sigmas, kernel=3, border_z=10, nms_d=14, max_out=None, return_
     cutoff = torch.empty((1,), dtype=torch.float32, device=v.device)   # count / overflow code and the threshold)
     heat = torch.empty_like(v) if return_heat else None
     sig = (ctypes.c_float * len(sigmas))(*[float(s) for s in sigmas])
-    L.check(lib.mi_dog_pick(L.ptr(v), D, H, W, ctypes.cast(sig, ctypes.c_void_p), len(sigmas),
-                            int(kernel), int(border_z), int(nms_d), L.ptr(heat), L.ptr(scores),
-                            L.ptr(coords), L.ptr(n), max_out, L.ptr(cutoff), L.ptr(ws), ws.numel(),
-                            L.stream()), "mi_dog_pick")
+    L.call("mi_dog_pick", v, D, H, W, ctypes.cast(sig, ctypes.c_void_p), len(sigmas), int(kernel), int(border_z), int(nms_d), heat, scores,
+           coords, n, max_out, cutoff, ws, ws.numel())
     return scores, coords, n, cutoff, heat
 
 

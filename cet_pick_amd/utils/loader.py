@@ -24,11 +24,9 @@ def _dev():
 
 
 def _stats(x, n_slices, slice_elems):
-    lib = L.lib()
     stats = torch.empty((n_slices, 4), dtype=torch.float64, device=x.device)
-    ws = L.workspace(lib.mi_vol_stats_workspace_bytes(n_slices, slice_elems), x.device, "volstats")
-    L.check(lib.mi_vol_stats(L.ptr(x), n_slices, slice_elems, L.ptr(stats), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_vol_stats")
+    ws = L.workspace(L.lib().mi_vol_stats_workspace_bytes(n_slices, slice_elems), x.device, "volstats")
+    L.call("mi_vol_stats", x, n_slices, slice_elems, stats, ws, ws.numel())
     return stats
 
 
@@ -61,8 +59,7 @@ def rec_to_device(rec, order="xyz", compress=False):
     dev = _dev()
     src = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev, non_blocking=False)
     dst = torch.empty((zout, a, b), dtype=torch.float32, device=dev)
-    L.check(L.lib().mi_rec_reorder(L.ptr(src), _MODE_OF[dt], d0, d1, d2, ORDERS[order], int(bool(compress)),
-                                   L.ptr(dst), L.stream()), "mi_rec_reorder")
+    L.call("mi_rec_reorder", src, _MODE_OF[dt], d0, d1, d2, ORDERS[order], int(bool(compress)), dst)
     return dst
 
 
@@ -71,7 +68,7 @@ def zscore(vol, per_slice=False):
     v = L.require_cuda(vol, "vol").contiguous()
     n, e = (v.shape[0], v[0].numel()) if per_slice else (1, v.numel())
     out = torch.empty_like(v)
-    L.check(L.lib().mi_zscore(L.ptr(v), L.ptr(out), n, e, L.ptr(_stats(v, n, e)), L.stream()), "mi_zscore")
+    L.call("mi_zscore", v, out, n, e, _stats(v, n, e))
     return out
 
 
@@ -85,19 +82,16 @@ def preprocess(mrc, denoise=0, is_tilt=False):
     """loader.py:90-121: (Gaussian denoise) -> z-score -> 8-bit quantise -> min-max to [0, 1]."""
     v = mrc if isinstance(mrc, torch.Tensor) else torch.as_tensor(np.asarray(mrc), dtype=torch.float32)
     v = v.to(_dev(), torch.float32).contiguous()
-    lib = L.lib()
     d, h, w = v.shape
     if denoise > 0:
         out, tmp = torch.empty_like(v), torch.empty_like(v)
-        fn = lib.mi_gauss2d_slices if is_tilt else lib.mi_gauss3d_sep
-        L.check(fn(L.ptr(v), L.ptr(out), L.ptr(tmp), d, h, w, float(denoise), L.stream()), "gauss")
+        L.call("mi_gauss2d_slices" if is_tilt else "mi_gauss3d_sep", v, out, tmp, d, h, w, float(denoise))
         v = out
     n, e = (d, h * w) if is_tilt else (1, v.numel())
     # quantize() defaults (-2.5, 2) everywhere except the denoised volume branch (loader.py:105: -3, 3)
     mi, ma = (-3.0, 3.0) if (denoise > 0 and not is_tilt) else (-2.5, 2.0)
     out = torch.empty_like(v)
-    L.check(lib.mi_zscore_quantize_minmax(L.ptr(v), L.ptr(out), n, e, L.ptr(_stats(v, n, e)), mi, ma,
-                                          int(bool(is_tilt)), L.stream()), "mi_zscore_quantize_minmax")
+    L.call("mi_zscore_quantize_minmax", v, out, n, e, _stats(v, n, e), mi, ma, int(bool(is_tilt)))
     return out
 
 

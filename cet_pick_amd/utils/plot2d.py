@@ -97,7 +97,7 @@ def select(y01, thr):
     if n and nbytes == 0:
         raise L.HipExtensionError("mi_plot_select failed: unsupported (%d picks)" % n)
     ws = L.workspace(nbytes, y01.device, "plot2d_select")
-    L.check(lib.mi_plot_select(L.ptr(y01), n, thr, L.ptr(shown), L.ptr(count), L.ptr(ws), ws.numel(), L.stream()), "mi_plot_select")
+    L.call("mi_plot_select", y01, n, thr, shown, count, ws, ws.numel())
     c = int(count.item())
     if c < 0:
         raise L.HipExtensionError("mi_plot_select failed: the cell lists of the selection were corrupted")
@@ -113,8 +113,7 @@ def thumbnails(patches, idx, T=THUMB, return_pre=False):
     m = idx.numel()
     out = torch.empty((m, int(T), int(T)), dtype=torch.uint8, device=patches.device)
     pre = torch.empty((m, c, b, b), dtype=torch.uint8, device=patches.device) if return_pre else None
-    L.check(L.lib().mi_plot_thumbs(L.ptr(patches), n, c, b, L.ptr(idx), m, int(T), L.ptr(out), L.ptr(pre), L.stream()),
-            "mi_plot_thumbs")
+    L.call("mi_plot_thumbs", patches, n, c, b, idx, m, int(T), out, pre)
     return (out, pre) if return_pre else out
 
 
@@ -135,14 +134,14 @@ def patch_bytes(patches, lut=GRAY_LUT, device=None, budget_bytes=PATCH_BUDGET_BY
                  for i in range(0, len(patches), per))
     else:
         slabs = (patches,)
-    lib, outs = L.lib(), []
+    outs = []
     for slab in slabs:
         slab = _patches(slab)
         n, c, b, _ = slab.shape
         with torch.cuda.device(slab.device):
             table = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.uint8).reshape(256)).to(slab.device)
             out = torch.empty((n, b, b), dtype=torch.uint8, device=slab.device)
-            L.check(lib.mi_plot_patch_bytes(L.ptr(slab), n, c, b, L.ptr(table), L.ptr(out), L.stream()), "mi_plot_patch_bytes")
+            L.call("mi_plot_patch_bytes", slab, n, c, b, table, out)
             outs.append(out.cpu().numpy())
     return np.concatenate(outs, 0)
 
@@ -160,7 +159,7 @@ def _draw(y01, idx, thumbs, P, mode, colours=None, labels=None, glyphs=None):
                                                     dtype=np.uint8)).to(dev)
         if tuple(side.shape) != (n, 3):
             raise ValueError("colours must be (%d, 3) uint8, got %s" % (n, tuple(side.shape)))
-        args = (L.ptr(side), None, None)
+        args = (side, None, None)
     else:
         lab = np.ascontiguousarray(labels.cpu().numpy() if isinstance(labels, torch.Tensor) else labels)
         if lab.shape != (n,) or (n and lab.min() < 0) or (n and lab.max() > 0x7fffffff):
@@ -170,13 +169,10 @@ def _draw(y01, idx, thumbs, P, mode, colours=None, labels=None, glyphs=None):
         if g.shape != (10, 7):
             raise ValueError("glyphs must be (10, 7) uint8, got %s" % (g.shape,))
         g = torch.from_numpy(g).to(dev)
-        args = (None, L.ptr(side), L.ptr(g))
-    lib = L.lib()
+        args = (None, side, g)
     out = torch.empty((lay["P"], lay["P"], 3), dtype=torch.uint8, device=dev)
-    ws = L.workspace(lib.mi_plot_raster_workspace_bytes(lay["P"]), dev, "plot2d_raster")
-    L.check(lib.mi_plot_raster(L.ptr(y01), n, L.ptr(idx), idx.numel(), L.ptr(thumbs), args[0], args[1], args[2],
-                               L._c.byref(L.PlotLayout(**lay)), mode, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_plot_raster")
+    ws = L.workspace(L.lib().mi_plot_raster_workspace_bytes(lay["P"]), dev, "plot2d_raster")
+    L.call("mi_plot_raster", y01, n, idx, idx.numel(), thumbs, *args, L._c.byref(L.PlotLayout(**lay)), mode, out, ws, ws.numel())
     return out
 
 

@@ -53,8 +53,7 @@ def sample_colours(y01, table):
     if table.ndim != 3 or table.shape[2] != 3:
         raise ValueError("table must be (W, H, 3) uint8, got %s" % (tuple(table.shape),))
     out = torch.empty((y01.shape[0], 3), dtype=torch.uint8, device=y01.device)
-    L.check(L.lib().mi_vis_sample_colours(L.ptr(y01), y01.shape[0], L.ptr(table), table.shape[0], table.shape[1], L.ptr(out),
-                                          L.stream()), "mi_vis_sample_colours")
+    L.call("mi_vis_sample_colours", y01, y01.shape[0], table, table.shape[0], table.shape[1], out)
     return out
 
 
@@ -75,8 +74,7 @@ def gaussian_u8(vol):
     out = torch.empty((z, r, c, 3), dtype=torch.uint8, device=vol.device)
     ws = L.workspace(lib.mi_vis_gauss_workspace_bytes(z, r, c), vol.device, "vis3d")
     w = (L._c.c_double * 7)(*gaussian_weights())
-    L.check(lib.mi_vis_gauss_u8(L.ptr(vol), z, r, c, L._c.cast(w, L._c.c_void_p), L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
-            "mi_vis_gauss_u8")
+    L.call("mi_vis_gauss_u8", vol, z, r, c, L._c.cast(w, L._c.c_void_p), out, ws, ws.numel())
     return out
 
 
@@ -111,14 +109,11 @@ def volume_bytes(vol):
     v = L.require_cuda(vol, "vol").contiguous()
     if v.ndim != 3 or 0 in v.shape:
         raise ValueError("vol must be a non-empty (Z, R, C) volume, got %s" % (tuple(v.shape),))
-    lib = L.lib()
     z, e = v.shape[0], v[0].numel()
     unit = torch.empty_like(v)
-    L.check(lib.mi_zscore_quantize_minmax(L.ptr(v), L.ptr(unit), z, e, L.ptr(Ld._stats(v, z, e)), QUANT_MI, QUANT_MA, 1, L.stream()),
-            "mi_zscore_quantize_minmax")
+    L.call("mi_zscore_quantize_minmax", v, unit, z, e, Ld._stats(v, z, e), QUANT_MI, QUANT_MA, 1)
     out = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
-    L.check(lib.mi_vis_slice_bytes(L.ptr(unit), z, e, L.ptr(Ld._stats(unit, z, e)), QUANT_MI, QUANT_MA, L.ptr(out), L.stream()),
-            "mi_vis_slice_bytes")
+    L.call("mi_vis_slice_bytes", unit, z, e, Ld._stats(unit, z, e), QUANT_MI, QUANT_MA, out)
     return out
 
 
@@ -158,7 +153,6 @@ def paint(picks, colours, shape, device=None, index_budget_bytes=INDEX_BUDGET_BY
     if len(picks) and (picks[:, 2].min() < 0 or picks[:, 2].max() >= z):
         raise ValueError("a pick lies outside the volume's %d slices" % z)
     dev = torch.device(device) if device is not None else Ld._dev()
-    lib = L.lib()
     with torch.cuda.device(dev):
         out = torch.empty((z, r, c, 3), dtype=torch.uint8, device=dev)
         d_picks, d_col = torch.from_numpy(picks).to(dev), torch.from_numpy(colours).to(dev)
@@ -174,7 +168,6 @@ def paint(picks, colours, shape, device=None, index_budget_bytes=INDEX_BUDGET_BY
             slot[mine] = np.arange(len(mine), dtype=np.int32)
             d_slot = torch.from_numpy(slot).to(dev)
             index = torch.empty((max(len(mine), 1), r, c), dtype=torch.int32, device=dev)
-            L.check(lib.mi_vis_paint(L.ptr(d_picks), L.ptr(d_col), len(picks), L.ptr(d_slot), len(mine), z, r, c, z0, nz,
-                                     L.ptr(index), L.ptr(out), L.stream()), "mi_vis_paint")
+            L.call("mi_vis_paint", d_picks, d_col, len(picks), d_slot, len(mine), z, r, c, z0, nz, index, out)
             z0 += nz
     return out

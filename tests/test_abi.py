@@ -26,6 +26,60 @@ def _header_geom_fields():
     return fields
 
 
+def _header_prototypes():
+    """[(return type, name, [parameter declarations])] of every `mi_*` prototype of the header, comments removed"""
+    txt = open(os.path.join(REPO, "include", "cetpick_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    protos = re.findall(r"([A-Za-z_][\w \*]*?)\b(mi_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt)
+    return [(" ".join(ret.split()).replace(" *", "*"), name, [] if params.strip() in ("", "void") else [" ".join(p.split()) for p in params.split(",")])
+            for ret, name, params in protos]
+
+
+def _param_class(decl, L):
+    """The class of one C parameter declaration: a POINTER(...) type for a pointer to a struct _lib mirrors, "ptr" for every other
+    pointer, "stream" for mi_stream_t, else "int" | "i64" | "u64" | "float" | "double"."""
+    import ctypes
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        mirrored = {"mi_conv_geom": L.ConvGeom, "mi_aug2d3d_ranges": L.Aug2d3dRanges, "mi_aug3d_ranges": L.Aug3dRanges,
+                    "mi_plot_layout": L.PlotLayout}
+        return ctypes.POINTER(mirrored[words[0]]) if words[0] in mirrored else "ptr"
+    assert len(words) == 2, "a scalar parameter is `type name`: %r" % decl
+    return {"mi_stream_t": "stream", "int": "int", "long": "i64", "int64_t": "i64", "size_t": "u64", "uint64_t": "u64",
+            "float": "float", "double": "double"}[words[0]]
+
+
+def _ctypes_class(t, L):
+    import ctypes
+    if t is L._S:
+        return "stream"
+    if t is ctypes.c_void_p:
+        return "ptr"
+    return {ctypes.c_int: "int", ctypes.c_long: "i64", ctypes.c_int64: "i64", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64",
+            ctypes.c_float: "float", ctypes.c_double: "double"}.get(t, t)          # (a POINTER(...) type stands for itself)
+
+
+def test_signatures_match_the_header_prototypes():
+    """Every prototype of the header against _lib.SIGNATURES: the number of parameters, the class of each, the return type, and the
+    stream marker exactly where the last parameter is mi_stream_t (it is never anywhere else)."""
+    import ctypes
+    from cet_pick_amd import _lib as L
+    protos = _header_prototypes()
+    assert len(protos) == len(L.SIGNATURES) == len(_header_symbols()) == len({name for _, name, _ in protos})
+    returns = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+    for ret, name, params in protos:
+        res, args = L.SIGNATURES[name]
+        assert res is returns[ret], name
+        want = [_param_class(p, L) for p in params]
+        assert [_ctypes_class(t, L) for t in args] == want, (name, params)
+        assert "stream" not in want[:-1], name
+        streamed, pointers = L._ENTRIES[name]
+        assert streamed == (want[-1:] == ["stream"]), name
+        assert list(pointers) == [i for i, c in enumerate(want) if c == "ptr"], name          # where call() takes a tensor
+    assert sum(s for s, _ in L._ENTRIES.values()) == sum(1 for _, _, params in protos if params and params[-1].startswith("mi_stream_t"))
+
+
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as ge
     ge.build()

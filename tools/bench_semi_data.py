@@ -56,7 +56,7 @@ def bench_labels(iters):
             st_d, c_d = torch.as_tensor(st).cuda(), torch.as_tensor(c).cuda()
 
             def run():
-                L.check(L.lib().mi_semi_labels(L.ptr(hm), *shape, L.ptr(c_d), n, L.ptr(st_d), r, 1, L.stream()), "mi_semi_labels")
+                L.call("mi_semi_labels", hm, *shape, c_d, n, st_d, r, 1)
             ms = _events(run, iters)
             t0 = time.perf_counter()
             ref = np_labels(shape, c, st, True)

@@ -34,10 +34,8 @@ dets = torch.empty((900, 5), device="cuda")
 for minz, dbg in ((8, 0), (4, 0), (2, 0), (16, 0)):
     os.environ["MI_PEAK3_MINZ"] = str(minz)
     os.environ["MI_PEAK3_WAVES"] = "8192"
-    t_nms = timeit(lambda: L.check(lib.mi_nms3d(L.ptr(heat), L.ptr(out), d, h, w, 3, 3, L.stream()), "nms"))
-    t_dec = timeit(lambda: L.check(lib.mi_sigmoid_nms_topk(L.ptr(heat), None, d, h, w, 3, 0, 0, 900, L.ptr(dets), None,
-                                                           L.ptr(ws), ws.numel(), L.stream()), "dec"))
-    t_sig = timeit(lambda: L.check(lib.mi_sigmoid_nms_topk(L.ptr(logits), L.ptr(out), d, h, w, 3, 0, 1, 900, L.ptr(dets), None,
-                                                           L.ptr(ws), ws.numel(), L.stream()), "dec"))
+    t_nms = timeit(lambda: L.call("mi_nms3d", heat, out, d, h, w, 3, 3))
+    t_dec = timeit(lambda: L.call("mi_sigmoid_nms_topk", heat, None, d, h, w, 3, 0, 0, 900, dets, None, ws, ws.numel()))
+    t_sig = timeit(lambda: L.call("mi_sigmoid_nms_topk", logits, out, d, h, w, 3, 0, 1, 900, dets, None, ws, ws.numel()))
     print("minz %d dbg %d: nms3d(dense out) %.1f us | decode no-sigmoid (cands only) %.1f us | fused sigmoid decode %.1f us"
           % (minz, dbg, t_nms, t_dec, t_sig))
