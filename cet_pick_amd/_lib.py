@@ -258,6 +258,10 @@ SIGNATURES = {
     # optimal matching of picks to target centres (csrc/match.hip)
     "mi_match_workspace_bytes": (_Z, [_I, _I, _I]),
     "mi_match_coordinates": (_I, [_P, _P, _P, _P, _I, _D, _P, _P, _P, _P, _Z, _S]),
+    # distance-graph components of the picks and the per-component quadratic fits, --spike / --fiber (csrc/pick_groups.hip)
+    "mi_pick_workspace_bytes": (_Z, [_I]),
+    "mi_pick_components": (_I, [_P, _I, _D, _P, _P, _P, _Z, _S]),
+    "mi_pick_fiber_fit": (_I, [_P, _I, _P, _P, _D, _D, _D, _P, _P, _I, _P, _P, _Z, _S]),
 }
 
 _lib = None

@@ -9,7 +9,7 @@ import torch
 
 from ..models.decode import sigmoid_tomo_decode
 from ..utils import mrc as mrcio
-from ..utils.post_process import tomo_fiber_postprocess, tomo_post_process
+from ..utils.post_process import tomo_fiber_postprocess_device, tomo_group_postprocess_device, tomo_post_process
 from .base_detector import BaseDetector
 
 
@@ -69,12 +69,16 @@ class TomodetDetector(BaseDetector):
         return self._hm_pin[:n].numpy().reshape(shape)                    # a view of the pinned buffer: no copy
 
     def save_detection(self, hm, dets, path, meta, prefix="", name=""):
+        opt = self.opt
+        spike = getattr(opt, "spike", False)
+        if opt.fiber and spike:
+            # the reference would hand rows without a score to the --spike writer (tomo_det_classify.py:196-216) and crash
+            raise ValueError("--fiber and --spike cannot be combined: choose one post-processing")
         if not os.path.exists(path):
             os.mkdir(path)
         max_z, max_y, max_x = hm.shape[2], hm.shape[3], hm.shape[4]
         max_x, max_y = max_x * 2, max_y * 2
         mrcio.write(os.path.join(path, "{}_hm.mrc".format(name)), self._hm_on_host(hm), is_vol=True)
-        opt = self.opt
         pre_coords = []
         with open(os.path.join(path, "{}.txt".format(name)), "w+") as out_detect:
             for _, v in dets.items():
@@ -86,17 +90,22 @@ class TomodetDetector(BaseDetector):
                             z = int(z) * 2
                         if opt.fiber:
                             pre_coords.append([x, y, z])
+                        elif spike:
+                            pre_coords.append([x, y, z, score])
                         elif not opt.with_score:
                             print(str(x) + "\t" + str(z) + "\t" + str(y), file=out_detect)
                         else:
                             print(str(x) + "\t" + str(z) + "\t" + str(y) + "\t" + str(score), file=out_detect)
             if opt.fiber:
-                for c in tomo_fiber_postprocess(pre_coords, distance_cutoff=opt.distance_cutoff, res_cutoff=opt.r2_cutoff,
-                                                curvature_cutoff=opt.curvature_cutoff, scale=opt.distance_scale):
+                for c in tomo_fiber_postprocess_device(pre_coords, distance_cutoff=opt.distance_cutoff, res_cutoff=opt.r2_cutoff,
+                                                       curvature_cutoff=opt.curvature_cutoff, scale=opt.distance_scale):
                     print(str(c[0]) + "\t" + str(c[1]) + "\t" + str(c[2]), file=out_detect)
-        if getattr(opt, "spike", False):
-            # tomo_det.py:89-95 calls tomo_group_postprocess without importing it (NameError in the reference)
-            raise NotImplementedError("--spike post-processing is not runnable in the reference (tomo_det.py:89-90)")
+            elif spike:
+                # tomo_det.py:89-95 forgets the import and would write every pick twice; this is the elif of
+                # tomo_det_classify.py:198-216: only the grouped picks are written
+                for c in tomo_group_postprocess_device(pre_coords, distance_cutoff=opt.distance_cutoff, min_per_group=5):
+                    line = str(int(c[0])) + "\t" + str(int(c[2])) + "\t" + str(int(c[1]))
+                    print(line + "\t" + str(float(c[3])) if opt.with_score else line, file=out_detect)
 
     def merge_outputs(self, detections):
         scores = detections[:, -1]

@@ -2755,3 +2755,60 @@ def match_coordinates(preds, targets, pred_off, targ_off, radius):
     L.call("mi_match_coordinates", preds, targets, po32.ctypes.data_as(ctypes.c_void_p), to32.ctypes.data_as(ctypes.c_void_p), n_img,
            float(radius), p2t, dist, total, ws, ws.numel())
     return p2t, dist, total
+
+
+# ---- grouping and tracing the picks, --spike / --fiber (csrc/pick_groups.hip) --------------------------------------------------
+
+PICK_MAX_POINTS = 4096       # points per call (mi_pick_components and mi_pick_fiber_fit refuse more)
+
+
+def _pick_points(pts, what):
+    """The checks both entries share; the size limit comes first and needs no device."""
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3:
+        raise L.HipExtensionError("%s: pts must be an (n, 3) tensor" % what)
+    n = int(pts.shape[0])
+    if n > PICK_MAX_POINTS or L.lib().mi_pick_workspace_bytes(n) == 0:
+        L.check(-3, "%s(%d points): more than %d points in one call" % (what, n, PICK_MAX_POINTS))
+    L.require_cuda(pts, "pts", torch.float64)
+    if not pts.is_contiguous():
+        raise L.HipExtensionError("%s: pts must be contiguous" % what)
+    return n
+
+
+def pick_components(pts, cutoff):
+    """Connected components of the graph that joins the rows i, j of pts (n, 3) float64 (device) where sqrt(d2) <= cutoff, d2 summed
+    as numpy sums it.  Returns (label (n,) int32: the smallest index of the row's component, size (n,) int32: its member count),
+    on the device.  Raises beyond PICK_MAX_POINTS rows."""
+    n = _pick_points(pts, "mi_pick_components")
+    label = torch.empty(n, dtype=torch.int32, device=pts.device)
+    size = torch.empty(n, dtype=torch.int32, device=pts.device)
+    if n == 0:
+        return label, size
+    ws = L.workspace(L.lib().mi_pick_workspace_bytes(n), pts.device, "pick")
+    L.call("mi_pick_components", pts, n, float(cutoff), label, size, ws, ws.numel())
+    return label, size
+
+
+def pick_fiber_fit(pts, label, size, res_cutoff, curvature_cutoff, scale, cap_rows):
+    """The quadratic fits u(t), v(t) (t, u, v = columns 0, 1, 2 of pts) of every component of more than 6 members and the resampled
+    rows of the accepted ones (include/cetpick_hip.h has the rules).  label, size as pick_components returned them for the same pts.
+    Returns (comp (n // 7, 16) float64: one record per such component in ascending label order, the rest zero; rows (cap_rows, 3)
+    int32 [int(y), int(v_fit), int(u_fit)]; n_rows (1,) int32), on the device.  Raises where the rows do not fit cap_rows."""
+    n = _pick_points(pts, "mi_pick_fiber_fit")
+    for t, name in ((label, "label"), (size, "size")):
+        L.require_cuda(t, name, torch.int32)
+        if tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise L.HipExtensionError("%s must be a contiguous (%d,) tensor, got %s" % (name, n, tuple(t.shape)))
+    cap_rows = int(cap_rows)
+    if cap_rows < 0 or cap_rows >= 2 ** 31 // 3:
+        raise L.HipExtensionError("cap_rows must be in [0, 2^31 / 3), got %d" % cap_rows)
+    dev = pts.device
+    comp = torch.zeros(n // 7, 16, dtype=torch.float64, device=dev)
+    rows = torch.empty(cap_rows, 3, dtype=torch.int32, device=dev)
+    n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return comp, rows, n_rows
+    ws = L.workspace(L.lib().mi_pick_workspace_bytes(n), dev, "pick")
+    L.call("mi_pick_fiber_fit", pts, n, label, size, float(res_cutoff), float(curvature_cutoff), float(scale), comp, rows, cap_rows,
+           n_rows, ws, ws.numel())
+    return comp, rows, n_rows

@@ -83,3 +83,44 @@ def tomo_fiber_postprocess(dets, distance_cutoff=15, res_cutoff=30, curvature_cu
             x_fit, z_fit = np.polyval(fit_x[0], y_out), np.polyval(fit_z[0], y_out)
             out.extend([int(y_out[j]), int(z_fit[j]), int(x_fit[j])] for j in range(x_fit.shape[0]))
     return out
+
+
+# ---- the same two steps on the device (csrc/pick_groups.hip through hipops): one upload, the launches, one download -------------
+
+def _upload_points(dets, device):
+    import torch
+    pts = np.ascontiguousarray(np.asarray(dets, dtype=np.float64)[:, :3])
+    return pts, torch.from_numpy(pts).to(device)
+
+
+def tomo_group_postprocess_device(dets_all, distance_cutoff=15, min_per_group=5, device="cuda"):
+    """tomo_group_postprocess with the components found on the device: the input rows (every column) of the components of more
+    than min_per_group members, component by ascending smallest index, then by index - the order the host function gives."""
+    import torch
+    from .. import hipops
+    dets = np.asarray(dets_all)
+    if dets.size == 0:
+        return []
+    _, d_pts = _upload_points(dets, device)
+    label, size = hipops.pick_components(d_pts, distance_cutoff)
+    label, size = torch.stack([label, size]).cpu().numpy()
+    keep = np.flatnonzero(size > min_per_group)
+    keep = keep[np.argsort(label[keep], kind="stable")]
+    return list(dets[keep])
+
+
+def tomo_fiber_postprocess_device(dets, distance_cutoff=15, res_cutoff=30, curvature_cutoff=0.03, scale=2, device="cuda"):
+    """tomo_fiber_postprocess with the components, the fits and the resampling on the device; rows [y', z, x] as there."""
+    import torch
+    from .. import hipops
+    dets = np.asarray(dets, dtype=np.float64)
+    if dets.size == 0:
+        return []
+    pts, d_pts = _upload_points(dets, device)
+    # every component's int(span // scale) is at most the whole set's, and at most n // 7 components have more than 6 members
+    global_span = pts[:, 0].max() - pts[:, 0].min()
+    cap_rows = (len(pts) // 7) * max(int(global_span // scale), 0)
+    label, size = hipops.pick_components(d_pts, distance_cutoff)
+    _, rows, n_rows = hipops.pick_fiber_fit(d_pts, label, size, res_cutoff, curvature_cutoff, scale, cap_rows)
+    flat = torch.cat([n_rows, rows.reshape(-1)]).cpu().numpy()
+    return flat[1:1 + 3 * int(flat[0])].reshape(-1, 3).tolist()

@@ -1108,6 +1108,51 @@ int mi_match_coordinates(const double* preds, const double* targets, const int* 
                          double radius, int* pred_to_target, double* dist, double* total_cost, void* workspace,
                          size_t workspace_bytes, mi_stream_t stream);
 
+/* Grouping and tracing the picks: the detector's --spike and --fiber post-processing (reference utils/post_process.py:31-113
+ * `tomo_group_postprocess`, `tomo_fiber_postprocess`; detectors/tomo_det_classify.py:196-216), DESIGN.md 4.23.
+ * At most 4096 points per call: MI_E_UNSUPPORTED above, returned before anything is enqueued - an input is never truncated.
+ * The source file is compiled with floating-point contraction off: d2, linspace and the Horner steps below are rounded
+ * operation by operation, as numpy rounds them, and no fused multiply-add stands in for two of them.
+ *   mi_pick_workspace_bytes  the scratch of both entries below for n points (the adjacency bit matrix, n x ceil(n / 64) words,
+ *                            and the per-component fit table); 0 beyond the limit (and for n < 0).  Needs no device.
+ *   mi_pick_components  pts (n, 3) float64.  i and j are joined where sqrt(d2) <= cutoff, d2 = (dx dx + dy dy) + dz dz in
+ *                       float64, every product and sum rounded on its own: a pair at exactly the cutoff is decided as numpy
+ *                       decides it.  label[i] = the smallest index of i's connected component, size[i] = its member count.
+ *                       Two launches: the bit matrix by many workgroups, then one workgroup that merges labels in LDS with
+ *                       integer atomics only - the same input gives the same bytes.  n == 0 is a no-op that returns MI_OK.
+ *   mi_pick_fiber_fit   label, size as mi_pick_components wrote them for the same pts.  Column 0 of pts is the abscissa t,
+ *                       columns 1 and 2 the ordinates u and v (the reference swaps columns 0 and 1 before it fits).  Every
+ *                       component of MORE THAN 6 members, in ascending label order, members in index order:
+ *                         lo, hi = min, max of t; span = hi - lo; m2 = int(span // 2), m_out = int(span // scale) (numpy's
+ *                         floor_divide); a component with m2 == 0 is skipped (record written, not accepted, no rows).
+ *                         u(t) and v(t) are fitted by a t^2 + b t + c in float64: least squares by the normal equations on
+ *                         s = (t - (lo + hi) / 2) / (span / 2) and ordinates less their mean, solved twice (the second solve
+ *                         fits the residual of the first), then carried back to powers of t.
+ *                         res = (sum of squared residuals) / members.
+ *                         k = max over y in linspace(lo - 1, hi + 1, m2) of 2 a / (1 + (2 a y + b)^2)^(2/3): the signed
+ *                         maximum and the exponent 2/3 are the reference's.
+ *                         accepted where, with tot = res_u + res_v: tot < res_cutoff and |k_u|, |k_v| < curvature_cutoff, or
+ *                         res_cutoff <= tot < 3 res_cutoff and |k_u|, |k_v| < curvature_cutoff / 10.
+ *                         An accepted component gives m_out rows [(int)y_j, (int)v_fit(y_j), (int)u_fit(y_j)], y =
+ *                         linspace(lo - 1, hi + 1, m_out) exactly as numpy builds it (step = (stop - start) / (m_out - 1),
+ *                         y_j = j step + start with the product and the sum rounded separately, the last element stop, a
+ *                         single element start), the fits by Horner (a y + b) y + c, each step rounded, (int) toward zero.
+ *                       THE ONE DIFFERENCE from the reference: a component whose t takes fewer than 3 distinct values gets
+ *                       res_u = res_v = 10000 (numpy's empty residual), zero coefficients and is never accepted; the
+ *                       reference would accept it, on a minimum-norm fit, where 3 res_cutoff > 20000.
+ *                       comp: one record of 16 doubles per component of more than 6 members, room for n / 7 records: label,
+ *                       members, lo, hi, a_u, b_u, c_u, res_u, a_v, b_v, c_v, res_v, k_u, k_v, accepted (0 / 1), rows written.
+ *                       rows (cap_rows, 3) int32; *n_rows (device) = the total number of rows.  If they do not fit cap_rows
+ *                       the entry writes none and returns MI_E_UNSUPPORTED, *n_rows the needed count.  The status depends
+ *                       on that count, so this entry waits for the stream before it returns.  MI_E_ARG (*n_rows = -1) where
+ *                       label / size describe more components than n / 7, or a component spans more than 2^24 in t. */
+size_t mi_pick_workspace_bytes(int n);
+int mi_pick_components(const double* pts, int n, double cutoff, int32_t* label, int32_t* size, void* ws, size_t ws_bytes,
+                       mi_stream_t stream);
+int mi_pick_fiber_fit(const double* pts, int n, const int32_t* label, const int32_t* size, double res_cutoff,
+                      double curvature_cutoff, double scale, double* comp, int32_t* rows, int cap_rows, int32_t* n_rows, void* ws,
+                      size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
