@@ -262,6 +262,12 @@ SIGNATURES = {
     "mi_pick_workspace_bytes": (_Z, [_I]),
     "mi_pick_components": (_I, [_P, _I, _D, _P, _P, _P, _Z, _S]),
     "mi_pick_fiber_fit": (_I, [_P, _I, _P, _P, _D, _D, _D, _P, _P, _I, _P, _P, _Z, _S]),
+    # per-class mean, deviation, count and exemplars of the picks' patches, and their picture (csrc/class_gallery.hip)
+    "mi_gallery_workspace_bytes": (_Z, [_L, _I, _I, _I]),
+    "mi_gallery_moments": (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _Z, _S]),
+    "mi_gallery_exemplars": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _Z, _S]),
+    "mi_gallery_raster_workspace_bytes": (_Z, [_I, _I]),
+    "mi_gallery_raster": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _Z, _S]),
 }
 
 _lib = None

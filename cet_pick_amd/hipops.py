@@ -2812,3 +2812,137 @@ def pick_fiber_fit(pts, label, size, res_cutoff, curvature_cutoff, scale, cap_ro
     L.call("mi_pick_fiber_fit", pts, n, label, size, float(res_cutoff), float(curvature_cutoff), float(scale), comp, rows, cap_rows,
            n_rows, ws, ws.numel())
     return comp, rows, n_rows
+
+
+# ---- the class gallery of plot_2d --class_gallery (csrc/class_gallery.hip) -------------------------------------
+
+GALLERY_MAX_EXEMPLARS = 64   # m of gallery_exemplars (the running best sits in LDS)
+GALLERY_MAX_CLASSES = 4096
+GALLERY_MAX_PICKS = 1 << 24
+GALLERY_PAD, GALLERY_TEXT_W, GALLERY_TEXT_H = 4, 94, 32          # the fixed sizes of the picture, in pixels
+
+
+def _gallery_tensor(t, name, dtype, shape):
+    """A refusal of this kind is the caller's mistake and needs no device: ValueError."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != dtype:
+        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError("%s must be %s, got %s" % (name, tuple("*" if s is None else s for s in shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return t
+
+
+def _gallery_range(t, name, hi):
+    """Every element of the int32 tensor t in [0, hi): looked at on a host copy, so that no kernel starts for a bad input."""
+    v = t.detach().cpu().numpy()
+    if v.size and (int(v.min()) < 0 or int(v.max()) >= hi):
+        bad = int(v.min()) if int(v.min()) < 0 else int(v.max())
+        raise ValueError("%s holds %d, outside [0, %d)" % (name, bad, hi))
+
+
+def _gallery_sizes(n, k_classes, m=1):
+    if n == 0:
+        raise ValueError("the class gallery needs at least one pick (n == 0)")
+    if n > GALLERY_MAX_PICKS:
+        raise ValueError("at most %d picks, got %d" % (GALLERY_MAX_PICKS, n))
+    if not 1 <= int(k_classes) <= GALLERY_MAX_CLASSES:
+        raise ValueError("k_classes must be in 1..%d, got %d" % (GALLERY_MAX_CLASSES, k_classes))
+    if not 1 <= int(m) <= GALLERY_MAX_EXEMPLARS:
+        raise ValueError("m must be in 1..%d, got %d" % (GALLERY_MAX_EXEMPLARS, m))
+
+
+def gallery_moments(patches, labels, k_classes):
+    """Per class of labels (n,) int32 in [0, k_classes): (mean (k, h, w) fp32, std (k, h, w) fp32, count (k,) int32) of the patches
+    (n, h, w) fp32 - the per-pixel mean and population deviation in float64, two passes, members in ascending pick index.  A class
+    without members has count 0 and zeros.  The same input gives the same bytes.  Raises ValueError for a label outside the range,
+    a non-contiguous input and n == 0, before any launch."""
+    patches = _gallery_tensor(patches, "patches", torch.float32, (None, None, None))
+    n, h, w = (int(s) for s in patches.shape)
+    labels = _gallery_tensor(labels, "labels", torch.int32, (n,))
+    k = int(k_classes)
+    _gallery_sizes(n, k)
+    if h * w == 0 or h * w > 1 << 20:
+        raise ValueError("a patch has 1..2^20 pixels, got %d x %d" % (h, w))
+    _gallery_range(labels, "labels", k)
+    L.require_cuda(patches, "patches")
+    L.require_cuda(labels, "labels", torch.int32)
+    dev = patches.device
+    mean = torch.empty((k, h, w), dtype=torch.float32, device=dev)
+    std = torch.empty((k, h, w), dtype=torch.float32, device=dev)
+    count = torch.empty((k,), dtype=torch.int32, device=dev)
+    ws = L.workspace(L.lib().mi_gallery_workspace_bytes(n, k, h * w, 1), dev, "gallery")
+    L.call("mi_gallery_moments", patches, labels, n, h, w, k, mean, std, count, ws, ws.numel())
+    return mean, std, count
+
+
+def gallery_exemplars(emb, centroids, assign, labels, k_classes, m):
+    """Per class the m members nearest to the centroid they are assigned to: (idx (k, m) int32, d2 (k, m) float64), ascending by
+    (d2, pick index), padded with -1 and +inf.  emb (n, dim) fp32, centroids (k_centroids, dim) fp32, assign (n,) int32 in
+    [0, k_centroids), labels (n,) int32 in [0, k_classes); d2 = sum_j (emb - centroid)^2 in float64, j ascending.  Raises
+    ValueError for m outside 1..64, a label or an assignment outside its range, a non-contiguous input and n == 0, before any
+    launch."""
+    emb = _gallery_tensor(emb, "emb", torch.float32, (None, None))
+    n, dim = (int(s) for s in emb.shape)
+    centroids = _gallery_tensor(centroids, "centroids", torch.float32, (None, dim))
+    assign = _gallery_tensor(assign, "assign", torch.int32, (n,))
+    labels = _gallery_tensor(labels, "labels", torch.int32, (n,))
+    k, kc, m = int(k_classes), int(centroids.shape[0]), int(m)
+    _gallery_sizes(n, k, m)
+    if dim == 0 or dim > 65536 or kc == 0:
+        raise ValueError("emb (n, dim) and centroids (k_centroids, dim) need 1 <= dim <= 65536 and a centroid")
+    _gallery_range(labels, "labels", k)
+    _gallery_range(assign, "assign", kc)
+    for t, name in ((emb, "emb"), (centroids, "centroids")):
+        L.require_cuda(t, name)
+    for t, name in ((assign, "assign"), (labels, "labels")):
+        L.require_cuda(t, name, torch.int32)
+    dev = emb.device
+    idx = torch.empty((k, m), dtype=torch.int32, device=dev)
+    d2 = torch.empty((k, m), dtype=torch.float64, device=dev)
+    ws = L.workspace(L.lib().mi_gallery_workspace_bytes(n, k, 0, m), dev, "gallery")
+    L.call("mi_gallery_exemplars", emb, centroids, assign, labels, n, dim, kc, k, m, idx, d2, ws, ws.numel())
+    return idx, d2
+
+
+def gallery_canvas(k_classes, h, w, m_show, scale):
+    """(H, W) of the picture gallery_raster draws (include/cetpick_hip.h has the layout)."""
+    row = max(h * scale, GALLERY_TEXT_H)
+    return (GALLERY_PAD + k_classes * (row + GALLERY_PAD),
+            2 * GALLERY_PAD + GALLERY_TEXT_W + (2 + m_show) * (w * scale + GALLERY_PAD))
+
+
+def gallery_raster(mean, std, count, idx, patches, glyphs, m_show=None, scale=2):
+    """The picture of the gallery: (rgb (H, W, 3) uint8, order (k,) int32 - the class of every row: descending count, ascending
+    class among equal counts), both on the device.  mean, std (k, h, w) fp32 and count (k,) int32 as gallery_moments returns them,
+    idx (k, m) int32 as gallery_exemplars does, patches (n, h, w) fp32, glyphs (10, 7) uint8 (utils/plot2d.DIGITS_5X7).  The first
+    m_show (default: all m) exemplars are drawn, every patch enlarged `scale` times."""
+    mean = _gallery_tensor(mean, "mean", torch.float32, (None, None, None))
+    k, h, w = (int(s) for s in mean.shape)
+    std = _gallery_tensor(std, "std", torch.float32, (k, h, w))
+    count = _gallery_tensor(count, "count", torch.int32, (k,))
+    idx = _gallery_tensor(idx, "idx", torch.int32, (k, None))
+    patches = _gallery_tensor(patches, "patches", torch.float32, (None, h, w))
+    glyphs = _gallery_tensor(glyphs, "glyphs", torch.uint8, (10, 7))
+    n, m = int(patches.shape[0]), int(idx.shape[1])
+    m_show = m if m_show is None else int(m_show)
+    scale = int(scale)
+    _gallery_sizes(n, k, m)
+    if not 0 <= m_show <= m or not 1 <= scale <= 64 or h * w == 0 or h * w > 1 << 20 or max(h, w) * scale > 65536:
+        raise ValueError("m_show must be in 0..%d and scale in 1..64 (patches of at most 2^20 pixels, 65536 enlarged), got %d and %d"
+                         % (m, m_show, scale))
+    H_, W_ = gallery_canvas(k, h, w, m_show, scale)
+    if H_ * W_ > 0x3fffffff:
+        raise ValueError("a picture of %d x %d pixels is too large" % (H_, W_))
+    for t, name, dt in ((mean, "mean", torch.float32), (std, "std", torch.float32), (count, "count", torch.int32),
+                        (idx, "idx", torch.int32), (patches, "patches", torch.float32), (glyphs, "glyphs", torch.uint8)):
+        L.require_cuda(t, name, dt)
+    dev = mean.device
+    rgb = torch.empty((H_, W_, 3), dtype=torch.uint8, device=dev)
+    order = torch.empty((k,), dtype=torch.int32, device=dev)
+    ws = L.workspace(L.lib().mi_gallery_raster_workspace_bytes(k, m_show), dev, "gallery_raster")
+    L.call("mi_gallery_raster", mean, std, count, idx, patches, n, h, w, k, m, m_show, scale, glyphs, order, rgb, H_, W_, ws,
+           ws.numel())
+    return rgb, order

@@ -5,7 +5,7 @@ plot_2d.py; its pictures and thumbnails with --min_dist_vis):
                                    [--seed 1234] [--gpus 0] [--host 7000] [--num_neighbor K] [--mode umap | --mode tsne]
                                    [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy] [--umap_init random | spectral]
                                    [--label_map] [--target_weight 0.5] [--min_dist_vis 1.3e-3] [--save_out_img 1]
-                                   [--plot_size 1500]
+                                   [--plot_size 1500] [--class_gallery [--gallery_exemplars 8]]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -73,6 +73,19 @@ also hold `subvol` (N, C, b, b), and utils/plot2d.py with csrc/plot2d.hip (DESIG
 Without a map --min_dist_vis writes the imgs/ only.  Not made here: the Phoenix interactive session, and
 matplotlib's own figure layout - the pictures have no axes, ticks, fonts or tight bounding box; their layout is fixed in
 utils/plot2d.py.
+
+With --class_gallery (this project's own; it stands in for looking at the classes in the Phoenix session) the
+input must hold `subvol` (N, C, h, w), and utils/plot2d.class_gallery with csrc/class_gallery.hip make on the MI355X, for the
+final classes (`label` of kmeans_labels.npz: the merged classes where --n_cluster merges, the centroids otherwise):
+
+    OUT/class_gallery.npz                 mean, std (k, h, w) f32: per pixel the mean and population deviation of channel 0 of the
+                                          class's patches; count (k,) i32; exemplar_index (k, m) i32: the m = --gallery_exemplars
+                                          members nearest to their own k-means centroid (squared L2 over `pred`, ties by pick
+                                          index), -1 where a class has fewer; exemplar_d2 (k, m) f64, +inf there; order (k,) i32:
+                                          the class of every row of the picture, by descending count, then ascending class
+    OUT/class_gallery.png (.webp)         one row per class: its number over its count, the mean patch, the deviation patch (one
+                                          grey scale for all classes) and the exemplars - what --labels of
+                                          interactive_to_training_coords is chosen from
 """
 import argparse
 import os
@@ -115,6 +128,10 @@ def add_arguments(parser):
                         "leaves them out")
     parser.add_argument("--plot_size", type=int, default=1500, help="side of the pictures in pixels, at least 128 (the "
                         "reference: 15 in at 100 dpi)")
+    parser.add_argument("--class_gallery", action="store_true", help="also write class_gallery.npz and class_gallery.png: per "
+                        "class the mean patch, the spread and number of its members and its most typical members (needs subvol)")
+    parser.add_argument("--gallery_exemplars", type=int, default=8, help="with --class_gallery: members shown per class, 1..64, "
+                        "the nearest to their centroid first")
     return parser
 
 
@@ -269,6 +286,18 @@ def write_picture(stem, pic):
         return False
 
 
+def write_class_gallery(path, patches, projs, centroids, assign, label, n_classes, m, device):
+    """class_gallery.npz (mean, std, count, exemplar_index, exemplar_d2, order) and class_gallery.png (.webp) under `path`: the
+    classes of `label` as a gallery, made on the device (utils/plot2d.class_gallery)."""
+    from .utils.plot2d import class_gallery
+    g = class_gallery(patches, projs, np.asarray(centroids, np.float32), assign, label, n_classes, m=m, device=device)
+    pic = g.pop("picture")
+    np.savez(os.path.join(path, "class_gallery.npz"), **g)
+    write_picture(os.path.join(path, "class_gallery"), pic)
+    print("[cet_pick_amd] plot_2d: gallery of %d classes (%d with members), %d exemplars each, %d x %d -> %s and class_gallery.npz"
+          % (n_classes, int((g["count"] > 0).sum()), m, pic.shape[1], pic.shape[0], os.path.join(path, "class_gallery.png")))
+
+
 def unit_square(y):
     """(y - min) / (max - min) per axis, as the reference normalises its map (an axis of one value maps to 0)."""
     lo, hi = y.min(0), y.max(0)
@@ -321,6 +350,16 @@ def main(args):
             args.min_dist_vis, "imgs/{i}.png of %d picks" % len(projs) if args.save_out_img == 1 else "no imgs/ (--save_out_img "
             "%d)" % args.save_out_img, (", " + ", ".join(pictures) + " (%d x %d) and plot_2d_shown.npz" % (args.plot_size,
             args.plot_size)) if pictures else " only: without a map (--mode umap | tsne with --num_neighbor K) there is no picture"))
+    if args.class_gallery:
+        if "subvol" not in data.files:
+            raise ValueError("--class_gallery averages the picks' patches: %s holds no 'subvol' (it has %s)"
+                             % (args.input, ", ".join(data.files)))
+        if not 1 <= args.gallery_exemplars <= 64:
+            raise ValueError("--gallery_exemplars is 1..64, got %d" % args.gallery_exemplars)
+        gallery_patches = np.asarray(data["subvol"])
+        if gallery_patches.ndim != 4 or len(gallery_patches) != len(projs) or 0 in gallery_patches.shape:
+            raise ValueError("'subvol' of %s must be (%d, C, h, w), got %s" % (args.input, len(projs), gallery_patches.shape))
+        gallery_patches = np.ascontiguousarray(gallery_patches[:, 0], dtype=np.float32)       # channel 0, as the pictures show it
     if with_vis:
         pass                                               # the line above says what is written
     elif with_umap:
@@ -359,6 +398,10 @@ def main(args):
         print("[cet_pick_amd] plot_2d: %d grey PNGs -> %s" % (n_img, os.path.join(args.path, "imgs")))
     print("[cet_pick_amd] plot_2d: %d picks, %d centroids, %d classes, objective %.6g -> %s"
           % (len(assign), args.k, len(set(label.tolist())), float(km.obj[-1]) if len(km.obj) else float("nan"), args.path))
+    if args.class_gallery:
+        n_classes = args.n_cluster if 0 < args.n_cluster < args.k else args.k      # the final labels: merged classes, or centroids
+        write_class_gallery(args.path, gallery_patches, projs, centroids, assign, label, n_classes, args.gallery_exemplars,
+                            torch.device("cuda", gpu))
     if args.num_neighbor is not None:
         if with_umap:
             if args.umap_init == "spectral":

@@ -7,6 +7,8 @@ reference's plot_2d.py:96-103 and :121-218.
     out = draw_out(y01, idx, thumbs, colours, P)         # (P, P, 3) uint8: 2d_visualization_out
     lab = draw_labels(y01, idx, thumbs, labels, P)       # (P, P, 3) uint8: 2d_visualization_labels
     write_png(path, array)                               # host: 8-bit grey, RGB or RGBA
+    g = class_gallery(patches, emb, centroids, assign, labels, k)   # per class: mean, std, count, exemplars, and their picture
+                                                         # (csrc/class_gallery.hip, DESIGN.md 4.24: this project's own)
 
 What is drawn, in which order and at which data-unit sizes is the reference's; the layout of the canvas (below) is this
 project's own: no axes, ticks or tight bounding box.  There is no CPU path.
@@ -186,6 +188,35 @@ def draw_labels(y01, idx, thumbs, labels, P=PLOT_SIZE, glyphs=None):
     """2d_visualization_labels as a (P, P, 3) uint8 device tensor: per shown pick, in order, its framed thumbnail and then
     the box with its class number `labels[idx[k]]`, digits from `glyphs` (10, 7) uint8 (DIGITS_5X7 by default)."""
     return _draw(y01, idx, thumbs, P, 1, labels=labels, glyphs=glyphs)
+
+
+def class_gallery(patches, emb, centroids, assign, labels, k_classes, m=8, scale=2, device=None):
+    """The class gallery (csrc/class_gallery.hip) of the picks: per class of `labels` (N,) in [0, k_classes) the
+    mean and the population deviation of the patches (N, h, w), the member count, and the m members whose embedding emb (N, d) is
+    nearest to the centroid `assign` (N,) gives them among `centroids` (k, d); numpy in, numpy out.  Returns a dictionary with
+    mean, std (k_classes, h, w) fp32, count (k_classes,) int32, exemplar_index (k_classes, m) int32 (-1 where a class has fewer
+    members), exemplar_d2 (k_classes, m) float64 (+inf there), order (k_classes,) int32 - the class of every row of the picture,
+    by descending count, then ascending class - and picture (H, W, 3) uint8: per row the class number over its count, the mean
+    (min-max scaled), the deviation (scaled by the largest deviation of all classes) and the m exemplars (min-max scaled each),
+    every patch enlarged `scale` times.  There is no CPU path."""
+    from .. import hipops as H
+    if not torch.cuda.is_available():
+        raise L.HipExtensionError("the class gallery is made on the MI355X (cuda) device; there is no CPU path")
+    if device is None:
+        from . import loader as Ld
+        device = Ld._dev()
+    dev = torch.device(device)
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+    with torch.cuda.device(dev):
+        x, lab = up(patches, np.float32), up(labels, np.int32)
+        mean, std, count = H.gallery_moments(x, lab, k_classes)
+        idx, d2 = H.gallery_exemplars(up(emb, np.float32), up(centroids, np.float32), up(assign, np.int32), lab, k_classes, m)
+        pic, order = H.gallery_raster(mean, std, count, idx, x, up(DIGITS_5X7, np.uint8), scale=scale)
+        return dict(mean=mean.cpu().numpy(), std=std.cpu().numpy(), count=count.cpu().numpy(), exemplar_index=idx.cpu().numpy(),
+                    exemplar_d2=d2.cpu().numpy(), order=order.cpu().numpy(), picture=pic.cpu().numpy())
 
 
 def write_png(path, array):

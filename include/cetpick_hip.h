@@ -1153,6 +1153,49 @@ int mi_pick_fiber_fit(const double* pts, int n, const int32_t* label, const int3
                       double curvature_cutoff, double scale, double* comp, int32_t* rows, int cap_rows, int32_t* n_rows, void* ws,
                       size_t ws_bytes, mi_stream_t stream);
 
+/* The class gallery of plot_2d --class_gallery: per class the average patch, the spread of its members, their number and the
+ * members nearest to their centroid, and the picture of all that (this project's own; nothing of it is in the reference),
+ * DESIGN.md 4.24.  n <= 2^24 picks, k_classes <= 4096, 1 <= m <= 64, h w <= 2^20: MI_E_ARG outside, before anything is enqueued.
+ * The kernels never read or write out of bounds for a label or an assignment outside its range (such a pick is in no class, such
+ * an assignment is at distance +inf), but the counts then do not add up to n: the Python wrappers refuse both.
+ * Both reductions first sort the picks by class on the device (histogram, exclusive scan, scatter in ascending pick index) and
+ * add in that order with no floating-point atomic: the same input gives the same bytes.  The source file is compiled with
+ * floating-point contraction off.
+ *   mi_gallery_workspace_bytes  the scratch of mi_gallery_moments for patches of b = h w pixels, and of mi_gallery_exemplars
+ *                         (which needs no more than b = 0); 0 outside the limits above.  Needs no device.
+ *   mi_gallery_moments    patches (n, h, w) fp32, labels (n) int32.  count_out[c] = members of class c; mean_out[c], std_out[c]
+ *                         (h, w) fp32 = the per-pixel mean and population deviation (divided by the count) of the members,
+ *                         summed in float64 over the members in ascending pick index, 256 at a time into one partial sum each,
+ *                         the partial sums added in order; the deviation in a second pass, sqrt(sum (x - mean)^2 / count) with
+ *                         the float64 mean.  A class without members: count 0, mean and deviation 0.
+ *   mi_gallery_exemplars  emb (n, dim) fp32, centroids (k_centroids, dim) fp32, assign (n) int32.  d2(i) = sum_j (emb[i][j] -
+ *                         centroids[assign[i]][j])^2 in float64, j ascending, every difference, product and sum rounded on its
+ *                         own.  idx_out (k_classes, m) int32: the m members of every class with the smallest d2, ascending by
+ *                         (d2, pick index), -1 where the class has fewer; d2_out (k_classes, m) float64 their d2, +inf there.
+ *                         A NaN distance counts as +inf.
+ *   mi_gallery_raster     out_rgb (H, W, 3) uint8, white.  Row r shows class order_out[r]: descending count, ascending class
+ *                         among equal counts (order_out (k_classes) int32 is written).  With PAD = 4 and the 5 x 7 digits of
+ *                         glyphs (10, 7) uint8 drawn 2 pixels per bit, 2 pixels apart, in black: rows are max(h scale, 32) high
+ *                         and start at y = 4 + r (row height + 4); the class number stands at x = 4 at the top of the row, the
+ *                         count 18 pixels below it; the cells, h scale x w scale pixels each, start at x = 102 + j (w scale + 4):
+ *                         j = 0 the mean, j = 1 the deviation, j = 2 + e exemplar e < m_show <= m of idx (k_classes, m) - a row
+ *                         of patches (n, h, w); an idx outside [0, n) leaves the cell white.  H = 4 + k_classes (row height + 4),
+ *                         W = 102 + (2 + m_show)(w scale + 4): MI_E_ARG for another canvas.  Source pixel (y / scale, x / scale).
+ *                         Grey byte, all in float32, every operation rounded: span = max - min of the patch; 0 where span is
+ *                         not positive, else rint(((v - min) / span) 255) (half to even), held in 0..255.  The deviation cell
+ *                         takes min = 0 and span = the largest deviation of all classes and pixels.
+ *   mi_gallery_raster_workspace_bytes  its scratch (the extremes of every cell); 0 outside the limits.  Needs no device. */
+size_t mi_gallery_workspace_bytes(long n, int k_classes, int b, int m);
+int mi_gallery_moments(const float* patches, const int32_t* labels, long n, int h, int w, int k_classes, float* mean_out,
+                       float* std_out, int32_t* count_out, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_gallery_exemplars(const float* emb, const float* centroids, const int32_t* assign, const int32_t* labels, long n, int dim,
+                         int k_centroids, int k_classes, int m, int32_t* idx_out, double* d2_out, void* ws, size_t ws_bytes,
+                         mi_stream_t stream);
+size_t mi_gallery_raster_workspace_bytes(int k_classes, int m_show);
+int mi_gallery_raster(const float* mean, const float* std, const int32_t* count, const int32_t* idx, const float* patches, long n,
+                      int h, int w, int k_classes, int m, int m_show, int scale, const uint8_t* glyphs, int32_t* order_out,
+                      uint8_t* out_rgb, int H, int W, void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
