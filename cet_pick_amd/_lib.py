@@ -268,6 +268,11 @@ SIGNATURES = {
     "mi_gallery_exemplars": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _Z, _S]),
     "mi_gallery_raster_workspace_bytes": (_Z, [_I, _I]),
     "mi_gallery_raster": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _Z, _S]),
+    # the SCAN loss over all heads, its gradient, and the class assignment (csrc/scan_loss.hip)
+    "mi_scan_loss_workspace_bytes": (_Z, [_I, _I, _I]),
+    "mi_scan_loss_fwd": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _S]),
+    "mi_scan_loss_bwd": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _S]),
+    "mi_scan_assign": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _S]),
 }
 
 _lib = None

@@ -2946,3 +2946,84 @@ def gallery_raster(mean, std, count, idx, patches, glyphs, m_show=None, scale=2)
     L.call("mi_gallery_raster", mean, std, count, idx, patches, n, h, w, k, m, m_show, scale, glyphs, order, rgb, H_, W_, ws,
            ws.numel())
     return rgb, order
+
+
+# ---- the SCAN loss over all heads and the class assignment (csrc/scan_loss.hip) -----------------------------
+
+SCAN_CHUNK = 256             # MI_SCAN_CHUNK: rows per partial sum of mi_scan_loss_fwd
+SCAN_MAX_CLASSES, SCAN_MAX_HEADS, SCAN_MAX_ROWS = 64, 16, 65536
+
+
+def _scan_logits(t, name, nheads, max_rows=None):
+    """(rows, classes per head) of the logits t (rows, nheads C) fp32, after every check the kernels rely on: ValueError before any
+    launch for a wrong rank, dtype, layout, head or class count, or no rows."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("%s must be a (rows, nheads x nclusters) tensor" % name)
+    if t.dtype != torch.float32:
+        raise ValueError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    nheads = int(nheads)
+    if not 1 <= nheads <= SCAN_MAX_HEADS:
+        raise ValueError("nheads must be in 1..%d, got %d" % (SCAN_MAX_HEADS, nheads))
+    rows, width = (int(s) for s in t.shape)
+    if width == 0 or width % nheads or width // nheads > SCAN_MAX_CLASSES:
+        raise ValueError("%s has %d columns: %d heads need the same 1..%d classes each" % (name, width, nheads, SCAN_MAX_CLASSES))
+    if rows == 0 or (max_rows is not None and rows > max_rows):
+        raise ValueError("%s must have 1..%s rows, got %d" % (name, max_rows if max_rows is not None else "any", rows))
+    return rows, width // nheads
+
+
+class _ScanLossFn(torch.autograd.Function):
+    """mi_scan_loss_fwd / _bwd: (sum of the heads' totals, stats (H, 3) = total, consistency, entropy per head)."""
+
+    @staticmethod
+    def forward(ctx, anchors, neighbours, nheads, entropy_weight):
+        b, c = _scan_logits(anchors, "anchors", nheads, SCAN_MAX_ROWS)
+        if neighbours.shape != anchors.shape:
+            raise ValueError("anchors are %s, neighbours %s" % (tuple(anchors.shape), tuple(neighbours.shape)))
+        _scan_logits(neighbours, "neighbours", nheads, SCAN_MAX_ROWS)
+        L.require_cuda(anchors, "anchors")
+        L.require_cuda(neighbours, "neighbours")
+        h, dev = int(nheads), anchors.device
+        ws = L.workspace(L.lib().mi_scan_loss_workspace_bytes(b, c, h), dev, "scanloss")
+        stats = torch.empty((h, 3), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        mean = torch.empty((h, c), dtype=torch.float64, device=dev)
+        L.call("mi_scan_loss_fwd", anchors, neighbours, b, c, h, float(entropy_weight), stats, loss, mean, ws, ws.numel())
+        ctx.save_for_backward(anchors, neighbours, mean)
+        ctx.dims, ctx.entropy_weight = (b, c, h), float(entropy_weight)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        anchors, neighbours, mean = ctx.saved_tensors
+        b, c, h = ctx.dims
+        dl = dloss.contiguous().float()                    # read on the device: no host sync
+        da, db = torch.empty_like(anchors), torch.empty_like(neighbours)
+        L.call("mi_scan_loss_bwd", anchors, neighbours, b, c, h, ctx.entropy_weight, mean, dl, da, db)
+        return da, db, None, None
+
+
+def scan_loss(anchors, neighbours, nheads=1, entropy_weight=2.0):
+    """The SCAN loss of every head at once: anchors, neighbours (B, nheads C) fp32 logits, contiguous, head h in columns
+    h C .. h C + C - 1, 1 <= C <= 64, nheads <= 16, B <= 65536.  -> (loss (): the sum over the heads of total_h, differentiable with
+    respect to both logits tensors; stats (nheads, 3): total, consistency, entropy of every head, no gradient).  The same input
+    gives the same bytes, forward and backward.  ValueError, before any launch, outside the limits or for non-contiguous logits."""
+    return _ScanLossFn.apply(anchors, neighbours, int(nheads), float(entropy_weight))
+
+
+def scan_assign(logits, nheads=1, with_prob=False):
+    """Per row and head of logits (N, nheads C) fp32, any N >= 1: (label (N, nheads) int32, the argmax with the lowest index on an
+    exact tie; conf (N, nheads) fp32, its softmax probability; counts (nheads, C) int32, the rows per class; prob (N, nheads C) fp32
+    with with_prob, else None)."""
+    n, c = _scan_logits(logits, "logits", nheads)
+    L.require_cuda(logits, "logits")
+    h, dev = int(nheads), logits.device
+    label = torch.empty((n, h), dtype=torch.int32, device=dev)
+    conf = torch.empty((n, h), dtype=torch.float32, device=dev)
+    counts = torch.empty((h, c), dtype=torch.int32, device=dev)
+    prob = torch.empty((n, h * c), dtype=torch.float32, device=dev) if with_prob else None
+    L.call("mi_scan_assign", logits.detach(), n, c, h, label, conf, prob, counts)
+    return label, conf, counts, prob

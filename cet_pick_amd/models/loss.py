@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import hipops as H
 
 
 def _flat(t, name):
@@ -269,6 +270,33 @@ class SupConLossV2_more(nn.Module):
         feat = _pad_features(torch.cat([all_features, all_features_cr], dim=0).float())
         cls = (pos.to(torch.uint8) | (un.to(torch.uint8) << 1)).contiguous()
         return _SupConPNFn.apply(feat, cls, 1.0 / self.base_temperature)
+
+
+class SCANLoss(nn.Module):
+    """loss.py:87-119, one head: forward(anchors, neighbors) -> (total, consistency, entropy) from two (b, num_classes) logits
+    tensors, 1 <= num_classes <= 64, b <= 65536 (csrc/scan_loss.hip).  `total` carries the gradient; the other two
+    are figures to log, as the reference's trainer uses them."""
+
+    def __init__(self, entropy_weight=2.0):
+        super().__init__()
+        self.entropy_weight = entropy_weight
+
+    def forward(self, anchors, neighbors):
+        total, stats = H.scan_loss(anchors, neighbors, 1, self.entropy_weight)
+        return total, stats[0, 1], stats[0, 2]
+
+
+class MultiHeadSCANLoss(nn.Module):
+    """The reference's TomoSCANLoss over a ClusteringModel's list of heads, in one launch: anchors, neighbors (b, nheads x
+    num_classes), head h in columns h num_classes .. -> (the sum of the heads' totals - the scalar that is differentiated -, stats
+    (nheads, 3): total, consistency, entropy per head, no gradient)."""
+
+    def __init__(self, nheads, entropy_weight=2.0):
+        super().__init__()
+        self.nheads, self.entropy_weight = int(nheads), entropy_weight
+
+    def forward(self, anchors, neighbors):
+        return H.scan_loss(anchors, neighbors, self.nheads, self.entropy_weight)
 
 
 class UnbiasedConLoss(nn.Module):

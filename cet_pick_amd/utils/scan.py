@@ -1,0 +1,184 @@
+"""The SCAN step ("learning to classify by nearest neighbours") on stored embeddings: the reference's head-only mode
+(`--cluster_head`: ClusteringModel's list of nn.Linear heads, simsiam_model_2d.py:885-921, trained by TomoSCANTrainer with SCANLoss
+on (pick, random graph neighbour) pairs of its `scan` datasets), DESIGN.md 4.25.
+
+All heads are ONE `hipops.HipLinear(d, nheads x nclusters)` - the product and the weight gradient are the MFMA path every other
+Linear of the package takes - and the loss of all heads with its gradient is csrc/scan_loss.hip.  HipLinear takes widths that are
+multiples of 16: the embeddings get zero columns and the stacked heads zero rows up to the next one, and the logits are cut back to
+nheads x nclusters columns in front of the loss (no -inf ever enters a softmax).  torch.optim.Adam is the optimiser; the
+pairs of an epoch are drawn on the host, copied once, and gathered on the device.  There is no CPU path.
+"""
+import numpy as np
+import torch
+
+from .. import _lib as L
+from .. import hipops as H
+
+
+def draw_neighbours(index, seed, epoch, batch_size):
+    """One epoch of (anchor, neighbour) picks: index (N, k) holds the k graph neighbours of every pick.  With a Generator seeded
+    from (seed, epoch): a permutation of the N picks, cut to whole batches, and for every pick one of the k + 1 entries
+    [the pick itself, neighbour 1 .. k], uniformly (the reference's neighbour table keeps the pick in column 0, so a pick can be its
+    own neighbour).  -> anchor (m,), neighbour (m,) int64 with m = (N // batch_size) batch_size."""
+    index = np.asarray(index)
+    if index.ndim != 2 or index.shape[0] == 0:
+        raise ValueError("index must be (N, k) with N >= 1, got %s" % (index.shape,))
+    n, k = index.shape
+    batch_size = int(batch_size)
+    if not 1 <= batch_size <= n:
+        raise ValueError("batch_size must be in 1..%d (the number of picks), got %d" % (n, batch_size))
+    rng = np.random.default_rng([int(seed), int(epoch)])
+    perm = rng.permutation(n)
+    column = rng.integers(0, k + 1, size=n)
+    table = np.concatenate([np.arange(n, dtype=np.int64)[:, None], index.astype(np.int64)], axis=1)
+    anchor = perm[:(n // batch_size) * batch_size].astype(np.int64)
+    return anchor, table[anchor, column[anchor]]
+
+
+def check_sizes(nclusters, nheads):
+    if not 1 <= int(nclusters) <= H.SCAN_MAX_CLASSES:
+        raise ValueError("--nclusters must be in 1..%d, got %d" % (H.SCAN_MAX_CLASSES, nclusters))
+    if not 1 <= int(nheads) <= H.SCAN_MAX_HEADS:
+        raise ValueError("--nheads must be in 1..%d, got %d" % (H.SCAN_MAX_HEADS, nheads))
+
+
+def initial_heads(d, nclusters, nheads, seed):
+    """(weight (nheads nclusters, d), bias (nheads nclusters,)) fp32: nn.Linear's U(-1 / sqrt(d), 1 / sqrt(d)) from a host Generator."""
+    g = torch.Generator().manual_seed(int(seed))
+    bound = 1.0 / d ** 0.5
+    w = (torch.rand(nheads * nclusters, d, generator=g) * 2 - 1) * bound
+    b = (torch.rand(nheads * nclusters, generator=g) * 2 - 1) * bound
+    return w, b
+
+
+def state_keys(nheads):
+    return [k for h in range(nheads) for k in ("cluster_head.%d.weight" % h, "cluster_head.%d.bias" % h)]
+
+
+def checkpoint(state_dict, epoch, optimizer, best_loss, best_loss_head):
+    """The reference's save_model_scan layout."""
+    return {"epoch": int(epoch), "state_dict": state_dict, "optimizer": optimizer, "best_loss": float(best_loss),
+            "best_loss_head": int(best_loss_head)}
+
+
+def _pad16(v):
+    return (v + 15) // 16 * 16
+
+
+class ScanHeads:
+    """nheads linear heads of nclusters classes on d-dimensional embeddings."""
+
+    def __init__(self, d, nclusters, nheads=1, seed=317, device="cuda"):
+        check_sizes(nclusters, nheads)
+        if int(d) < 1:
+            raise ValueError("embedding dimension must be >= 1, got %d" % d)
+        self.d, self.nclusters, self.nheads, self.seed = int(d), int(nclusters), int(nheads), int(seed)
+        self.width = self.nheads * self.nclusters
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.HipExtensionError("ScanHeads live on the MI355X (cuda) device; there is no CPU path")
+        self.lin = H.HipLinear(_pad16(self.d), _pad16(self.width)).to(self.device)
+        w, b = initial_heads(self.d, self.nclusters, self.nheads, self.seed)
+        with torch.no_grad():
+            self.lin.weight.zero_()
+            self.lin.bias.zero_()
+            self.lin.weight[:self.width, :self.d].copy_(w)
+            self.lin.bias[:self.width].copy_(b)
+        self.epoch, self.best_loss, self.best_loss_head = 0, float("inf"), 0
+        self.optimizer = None
+        self.history = []                                  # per epoch: (nheads, 3) mean total, consistency, entropy
+
+    # -- the reference's names ------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """cluster_head.{h}.weight (nclusters, d) and .bias (nclusters,): slices of the stacked HipLinear, not copies."""
+        c, out = self.nclusters, {}
+        for h in range(self.nheads):
+            out["cluster_head.%d.weight" % h] = self.lin.weight.detach()[h * c:(h + 1) * c, :self.d]
+            out["cluster_head.%d.bias" % h] = self.lin.bias.detach()[h * c:(h + 1) * c]
+        return out
+
+    def load_state_dict(self, sd):
+        mine = self.state_dict()
+        if sorted(sd) != sorted(mine):
+            raise ValueError("state dict holds %s, these heads %s" % (sorted(sd), sorted(mine)))
+        with torch.no_grad():
+            for k, v in mine.items():
+                if tuple(sd[k].shape) != tuple(v.shape):
+                    raise ValueError("%s is %s in the state dict, %s here" % (k, tuple(sd[k].shape), tuple(v.shape)))
+                v.copy_(sd[k])
+
+    def save(self, path):
+        sd = {k: v.cpu().contiguous().clone() for k, v in self.state_dict().items()}
+        torch.save(checkpoint(sd, self.epoch, self.optimizer.state_dict() if self.optimizer is not None else None,
+                              self.best_loss, self.best_loss_head), path)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        ck = torch.load(path, map_location="cpu", weights_only=False)
+        sd = ck["state_dict"]
+        nheads = len([k for k in sd if k.endswith(".weight")])
+        if nheads == 0 or sorted(sd) != sorted(state_keys(nheads)):
+            raise ValueError("%s holds no cluster_head.{h}.weight / .bias state" % path)
+        nclusters, d = (int(s) for s in sd["cluster_head.0.weight"].shape)
+        heads = cls(d, nclusters, nheads, device=device)
+        heads.load_state_dict(sd)
+        heads.epoch, heads.best_loss, heads.best_loss_head = int(ck["epoch"]), float(ck["best_loss"]), int(ck["best_loss_head"])
+        return heads
+
+    # -- the device work --------------------------------------------------------------------------------------------------------
+    def _embeddings(self, x):
+        """x (N, d) -> fp32 on the device with zero columns up to the HipLinear's width"""
+        x = torch.as_tensor(x, dtype=torch.float32)
+        if x.dim() != 2 or x.shape[1] != self.d or x.shape[0] == 0:
+            raise ValueError("embeddings must be (N, %d) with N >= 1, got %s" % (self.d, tuple(x.shape)))
+        x = x.to(self.device)
+        return torch.nn.functional.pad(x, (0, self.lin.in_f - self.d)).contiguous()
+
+    def _logits(self, xp):
+        z = self.lin(xp)
+        return z if z.shape[1] == self.width else z[:, :self.width]
+
+    def fit(self, x, index, num_epochs=100, batch_size=1024, lr=1e-3, weight_decay=1e-4, entropy_weight=2.0, log=None):
+        """Train every head so that a pick and a random entry of [itself, its graph neighbours index (N, k)] get the same class while
+        the classes stay balanced.  -> history (num_epochs, nheads, 3): per epoch and head the mean total, consistency, entropy over the
+        epoch's batches.  best_loss_head is the head with the lowest mean total of the last epoch."""
+        with torch.cuda.device(self.device):
+            xp = self._embeddings(x)
+            index = np.asarray(index)
+            if index.ndim != 2 or index.shape[0] != xp.shape[0]:
+                raise ValueError("the graph has %s rows, the embeddings %d" % (index.shape[:1], xp.shape[0]))
+            if index.size and (index.min() < 0 or index.max() >= xp.shape[0]):
+                raise ValueError("the graph names a pick outside 0..%d" % (xp.shape[0] - 1))
+            bs = int(batch_size)
+            if bs > H.SCAN_MAX_ROWS:
+                raise ValueError("batch_size is at most %d, got %d" % (H.SCAN_MAX_ROWS, bs))
+            self.optimizer = torch.optim.Adam(self.lin.parameters(), lr=lr, weight_decay=weight_decay)
+            for _ in range(int(num_epochs)):
+                anchor, neighbour = draw_neighbours(index, self.seed, self.epoch, bs)
+                pairs = torch.from_numpy(np.stack([anchor.reshape(-1, bs), neighbour.reshape(-1, bs)], axis=1)).to(self.device)
+                acc = torch.zeros((self.nheads, 3), dtype=torch.float32, device=self.device)
+                for rows in pairs:                         # (2, bs): the anchors, then their neighbours
+                    z = self._logits(xp.index_select(0, rows.reshape(-1)))
+                    loss, stats = H.scan_loss(z[:bs].contiguous(), z[bs:].contiguous(), self.nheads, entropy_weight)
+                    self.optimizer.zero_grad(set_to_none=True)
+                    loss.backward()
+                    self.optimizer.step()
+                    acc += stats
+                mean = (acc / len(pairs)).cpu().numpy()    # the epoch's one host read
+                self.history.append(mean)
+                self.epoch += 1
+                if log is not None:
+                    log(self.epoch, mean)
+            last = self.history[-1][:, 0]
+            self.best_loss_head = int(np.argmin(last))
+            self.best_loss = float(last[self.best_loss_head])
+            return np.stack(self.history)
+
+    def predict(self, x, with_prob=False):
+        """-> label (N, nheads) int32, conf (N, nheads) fp32, counts (nheads, nclusters) int32 [, prob (N, nheads nclusters) fp32]
+        as numpy arrays: every pick classified by every head."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            z = self._logits(self._embeddings(x)).contiguous()
+            label, conf, counts, prob = H.scan_assign(z, self.nheads, with_prob=with_prob)
+            out = (label.cpu().numpy(), conf.cpu().numpy(), counts.cpu().numpy())
+            return out + (prob.cpu().numpy(),) if with_prob else out

@@ -1196,6 +1196,34 @@ int mi_gallery_raster(const float* mean, const float* std, const int32_t* count,
                       int h, int w, int k_classes, int m, int m_show, int scale, const uint8_t* glyphs, int32_t* order_out,
                       uint8_t* out_rgb, int H, int W, void* ws, size_t ws_bytes, mi_stream_t stream);
 
+/* The SCAN step on stored embeddings, head-only form (the reference's SCANLoss and entropy, models/loss.py:68-119, summed over the
+ * heads as its TomoSCANLoss does), DESIGN.md 4.25.  Logits are (B, H C) fp32, contiguous; head h owns columns h C .. h C + C - 1.
+ * 1 <= C <= 64, 1 <= H <= 16, 1 <= B <= 65536 for the loss: MI_E_ARG outside, before anything is enqueued.  Per head, with
+ * p = softmax(anchor row), q = softmax(neighbour row) (max-subtracted), s_i = p_i . q_i, m = (1 / B) sum_i p_i, x = max(m, 1e-8):
+ *   consistency = -(1 / B) sum_i max(log s_i, -100)      entropy = -sum_c x_c log x_c      total = consistency - entropy_weight entropy
+ * After the fp32 row maximum the arithmetic is float64; results are rounded to fp32 where they are stored.  No floating-point
+ * atomic: the same input gives the same bytes.
+ *   mi_scan_loss_workspace_bytes  the scratch of mi_scan_loss_fwd; 0 outside the limits.  Needs no device.
+ *   mi_scan_loss_fwd    stats_out (H, 3) fp32 = total, consistency, entropy per head; *loss_out = the sum of the totals, heads in
+ *                       ascending order; mean_out (H, C) float64 = m, kept for the backward pass.  Two launches: workgroup
+ *                       (chunk, head) sums p and the clamped logs over MI_SCAN_CHUNK rows, then one workgroup adds the chunks in
+ *                       ascending order and finishes every head.
+ *   mi_scan_loss_bwd    d_anchors, d_neighbours (B, H C) fp32 = *dloss (device) times the gradient of *loss_out, one launch:
+ *                       d total / d s_i = (s_i - 1) / max((1 - s_i) s_i, 1e-12) / B (0 at s = 1, finite at s = 0; the -100 clamp
+ *                       passes no gradient test: torch's BCELoss), d total / d m_c = entropy_weight (log m_c + 1) where
+ *                       m_c >= 1e-8, else 0, d m_c / d p_ic = 1 / B, and dz = p (g - p . g) through each softmax.
+ *   mi_scan_assign      logits (n, H C) for any n >= 1: class_out (n, H) int32 = the argmax of the row's logits of head h, the
+ *                       lowest index on an exact tie (0 for a row of NaNs); conf_out (n, H) fp32 its probability; prob_out
+ *                       (n, H C) fp32 every probability, or NULL; counts_out (H, C) int32 the rows per class (integer atomics). */
+#define MI_SCAN_CHUNK 256
+size_t mi_scan_loss_workspace_bytes(int B, int C, int H);
+int mi_scan_loss_fwd(const float* anchors, const float* neighbours, int B, int C, int H, double entropy_weight, float* stats_out,
+                     float* loss_out, double* mean_out, void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_scan_loss_bwd(const float* anchors, const float* neighbours, int B, int C, int H, double entropy_weight, const double* mean,
+                     const float* dloss, float* d_anchors, float* d_neighbours, mi_stream_t stream);
+int mi_scan_assign(const float* logits, long n, int C, int H, int32_t* class_out, float* conf_out, float* prob_out,
+                   int32_t* counts_out, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
