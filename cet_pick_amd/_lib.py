@@ -77,6 +77,9 @@ SIGNATURES = {
     "mi_crop_normalize": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _S]),
     "mi_crop_normalize_table": (_I, [_P, _P, _P, _P, _P, _c.c_int64, _I, _I, _I, _I, _I, _I, _P, _S]),
     "mi_u8_roundtrip_normalize": (_I, [_P, _P, _Z, _F, _F, _S]),
+    # pose crops and pose pooling of the MoCo-3D exploration inference (csrc/crop_pose.hip)
+    "mi_crop_znorm_poses": (_I, [_P, _P, _P, _c.c_int64, _I, _I, _I, _I, _P, _I, _P, _S]),
+    "mi_embed_pool": (_I, [_P, _L, _I, _I, _P, _S]),
     "mi_aug2d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _I] + [_F] * 7 + [_P, _S]),
     "mi_aug2d_apply": (_I, [_P, _c.c_int64, _I, _P, _P, _c.c_int64, _I, _F, _F, _P, _S]),
     "mi_aug2d3d_params": (_I, [_P, _c.c_int64, _c.c_uint64, _I, _I, _R, _R, _P, _S]),

@@ -5,6 +5,7 @@ the reference datasets, without their per-pick Python loops.
 for a whole list of picks at once; `crop_znorm` makes the z-normalised 3-D crops the MoCo-3D encoder
 consumes.  The volume stays resident on the device; centres are (x, y, z) like the picker returns.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -90,6 +91,23 @@ class CropTable:
                cz, cy, cx, int(mode), int(bool(flip_x)), out)
         return out
 
+    def cut_poses(self, first, n, size, poses, out=None):
+        """the z-normalised crops of samples first .. first + n - 1 in every pose of `poses` -> (n, P, 1, cz, cy, cx): pose p is
+        the crop turned `p & 3` quarter turns (torch.rot90 over (y, x)) and then, with `p & 4`, mirrored along x.  One launch;
+        the library refuses cy != cx, a pose outside 0..7, a repeated pose and a list of none or more than eight."""
+        cz, cy, cx = [int(v) for v in size]
+        poses = [int(p) for p in poses]
+        if first < 0 or n < 0 or first + n > self.n:
+            raise L.HipExtensionError("CropTable.cut_poses: samples [%d, %d) outside the table's %d" % (first, first + n, self.n))
+        shape = (n, len(poses), 1, cz, cy, cx)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.desc.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise L.HipExtensionError("CropTable.cut_poses: `out` must be a contiguous float32 %s tensor" % (shape,))
+        L.call("mi_crop_znorm_poses", self.desc, self.owner, self.centres, int(first), int(n), cz, cy, cx,
+               L.host_array(poses, ctypes.c_int32), len(poses), out)
+        return out
+
 
 def extract_subvols(v, tomo_coords, subvol_size):
     """:117-128 for every pick: (n, 1, sy, sx) float32 = min-max(sum_z v[z-sz//2 : z+sz//2+1, ...]).
@@ -107,6 +125,17 @@ def extract_subvols_3d(v, tomo_coords, subvol_size):
 def crop_znorm(v, tomo_coords, size, flip_x=False):
     """(n, 1, cz, cy, cx) z-normalised crops (mean 0, unbiased std 1), optionally mirrored along x."""
     return _crop(v, tomo_coords, size, ZNORM, flip_x).unsqueeze(1)
+
+
+def crop_znorm_poses(table_or_vol, centres, size, poses):
+    """`crop_znorm` in the in-plane lattice poses `poses` (CropTable.cut_poses) -> (n, P, 1, cz, cy, cx).  With a CropTable,
+    `centres` is the sample range (first, n) or None for every sample; with a (D, H, W) volume, the (n, 3) centres (x, y, z)."""
+    if isinstance(table_or_vol, CropTable):
+        first, n = (0, table_or_vol.n) if centres is None else (int(centres[0]), int(centres[1]))
+        return table_or_vol.cut_poses(first, n, size, poses)
+    L.require_cuda(table_or_vol, "vol")
+    n = len(centres)
+    return CropTable([table_or_vol], np.zeros(n, np.int32), centres).cut_poses(0, n, size, poses)
 
 
 def extract_3d_tomo(rec, tomo_coords, crop_size_x, crop_size_y):

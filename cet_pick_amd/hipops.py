@@ -2477,6 +2477,22 @@ def knn_search(q, x, k, metric="ip", exclude_self=False, n_split=0, out=None):
     return index, value
 
 
+def embed_pool(x, out=None):
+    """(n, dim) unit rows from the (n, P, dim) embeddings of P poses of every pick (csrc/crop_pose.hip): F.normalize of every
+    row, the mean over P, F.normalize again.  P == 1 is F.normalize(x[:, 0], dim=1): the rows the k-NN search and the
+    memory bank take."""
+    L.require_cuda(x, "x")
+    if x.dim() != 3 or not x.is_contiguous():
+        raise L.HipExtensionError("x must be a contiguous (n, P, dim) tensor, got %s" % (tuple(x.shape),))
+    n, p, d = x.shape
+    if out is None:
+        out = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    elif tuple(L.require_cuda(out, "out").shape) != (n, d) or not out.is_contiguous():
+        raise L.HipExtensionError("out must be a contiguous (%d, %d) tensor" % (n, d))
+    L.call("mi_embed_pool", x, n, p, d, out)
+    return out
+
+
 # ---- the neighbour graph of the t-SNE, UMAP and spectral kernels (csrc/knn_graph.h) ----------------------------------------
 
 def _table(t, name, shape, dtype=torch.float32):

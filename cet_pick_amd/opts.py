@@ -74,6 +74,9 @@ _FLAGS = [
     # moco loaders the crop and its shifted mirror image (default) or two draws of the reference's 3-D chain on the box around
     # the crop (blur, noise, rotation, margin crop, normalisation, flip, erasure: csrc/augment3d.hip)
     ("--augment", dict(default="mirror", choices=["mirror", "reference"])),
+    # MI355X build only: in-plane lattice poses of every pick that moco_test_3d pools the embedding over - the crop itself (1),
+    # + its mirror image (2), the four quarter turns (4), or all eight (default)
+    ("--tta", dict(type=int, default=8, choices=[1, 2, 4, 8])),
 ]
 
 # task -> heads (opts.py:285-304); lambdas see the parsed opt

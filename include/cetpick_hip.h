@@ -169,6 +169,23 @@ int mi_crop_normalize_table(const mi_vol_desc* vols, const int32_t* owner, const
  * Normalize; mean / std = the dataset statistics of tomo_pre_proj_angle_select_new3d_vol.py:238-239).  y may alias x. */
 int mi_u8_roundtrip_normalize(const float* x, float* y, size_t n, float mean, float std, mi_stream_t stream);
 
+/* The mode-2 (z-normalised) crop of samples first .. first + n - 1 of a table (vols, owner, centres_xyz as for
+ * mi_crop_normalize_table) in n_poses of the eight in-plane lattice poses of a box with cy == cx (moco_test_3d.py, DESIGN.md
+ * 4.26): out (n, n_poses, cz, cy, cx).  Pose p: the crop turned `p & 3` quarter turns as torch.rot90(crop, p & 3, (-2, -1)),
+ * then, with `p & 4`, mirrored as torch.flip(crop, (-1,)).  The source window is read once and the statistics are computed
+ * once per sample (mi_crop_normalize's, summed in the order of its kernel for these shapes; zero variance divides by zero as
+ * it does there): every pose holds the same values, pose q is bit for bit the rotation / mirror image of pose 0.
+ * poses: a HOST array of n_poses distinct values in 0..7.  MI_E_ARG: cy != cx, n_poses outside 1..8, a pose outside 0..7 or
+ * repeated.  MI_E_UNSUPPORTED: cx > 64, or a window that does not fit the workgroup's LDS (cz cy (cx | 1) floats <= 136 KiB:
+ * 32^3 fits, 64^3 does not).  Nothing is launched on either. */
+int mi_crop_znorm_poses(const mi_vol_desc* vols, const int32_t* owner, const int32_t* centres_xyz, int64_t first, int n,
+                        int cz, int cy, int cx, const int32_t* poses, int n_poses, float* out, mi_stream_t stream);
+
+/* Pose pooling of embeddings: x (n, P, dim) fp32 -> out (n, dim) = normalize(mean over P of normalize(x[i, p, :])), normalize
+ * being F.normalize's x / max(|x|, 1e-12).  P == 1: F.normalize(x, dim=1).  One wave per row of out, every sum in a fixed
+ * order: the same input gives the same bytes.  P >= 1, 1 <= dim <= 1024 (MI_E_UNSUPPORTED above). */
+int mi_embed_pool(const float* x, long n, int P, int dim, float* out, mi_stream_t stream);
+
 /* Random view augmentation of the `simsiam3d` dataset (datasets/tomo_pre_proj_angle_select_new3d_vol.py:49-89: ToPILImage,
  * RandomHorizontalFlip, RandomVerticalFlip, ColorJitter, RandomResizedCrop(aspect 1), ToTensor, FixedRotation
  * (utils/image.py:195-201), Normalize; datasets/particle_pre_3d_vol.py:70-85: the second view is the crop of one of four
