@@ -276,6 +276,12 @@ SIGNATURES = {
     "mi_scan_loss_fwd": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _S]),
     "mi_scan_loss_bwd": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _S]),
     "mi_scan_assign": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _S]),
+    # the heads scored over the whole graph and the self-labelling loss (csrc/scan_selflabel.hip)
+    "mi_scan_graph_eval_workspace_bytes": (_Z, [_L, _I, _I]),
+    "mi_scan_graph_eval": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P, _P, _Z, _S]),
+    "mi_scan_selflabel_workspace_bytes": (_Z, [_I, _I]),
+    "mi_scan_selflabel_fwd": (_I, [_P, _P, _I, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _S]),
+    "mi_scan_selflabel_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S]),
 }
 
 _lib = None

@@ -3043,3 +3043,87 @@ def scan_assign(logits, nheads=1, with_prob=False):
     prob = torch.empty((n, h * c), dtype=torch.float32, device=dev) if with_prob else None
     L.call("mi_scan_assign", logits.detach(), n, c, h, label, conf, prob, counts)
     return label, conf, counts, prob
+
+
+# ---- the heads scored over the whole graph, and the self-labelling loss (csrc/scan_selflabel.hip) ------------
+
+SCAN_MAX_NEIGHBOURS = 64
+
+
+def scan_graph_eval(logits, index, nheads=1, with_self=True, validate=True):
+    """The reference's scan_evaluate on the device: logits (N, nheads C) fp32 of every pick, index (N, k) int32 graph neighbours,
+    1 <= k <= 64, entries in 0..N-1; with_self adds the pick itself in front of its row ([self, neighbour 1..k]: the table
+    utils/scan.draw_neighbours draws from).  -> (stats (nheads, 3) fp32: total = consistency - entropy, consistency over every
+    (pick, entry) pair, entropy of the mean distribution; best (1,) int32: the head with the lowest total, the lowest index on an
+    exact tie).  The kernel does not check the table: `validate` does here, with one host read (a caller that has checked passes
+    False)."""
+    n, c = _scan_logits(logits, "logits", nheads)
+    L.require_cuda(logits, "logits")
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2 or index.shape[0] != n or not index.is_contiguous():
+        raise ValueError("index must be a contiguous (%d, k) tensor, got %s" % (n, tuple(index.shape)))
+    k = int(index.shape[1])
+    if not 1 <= k <= SCAN_MAX_NEIGHBOURS:
+        raise ValueError("index must have 1..%d columns, got %d" % (SCAN_MAX_NEIGHBOURS, k))
+    if validate:
+        lo, hi = (int(v) for v in torch.aminmax(index))
+        if lo < 0 or hi >= n:
+            raise ValueError("the graph names a pick outside 0..%d" % (n - 1))
+    h, dev = int(nheads), logits.device
+    ws = L.workspace(L.lib().mi_scan_graph_eval_workspace_bytes(n, c, h), dev, "scangraph")
+    stats = torch.empty((h, 3), dtype=torch.float32, device=dev)
+    best = torch.empty((1,), dtype=torch.int32, device=dev)
+    L.call("mi_scan_graph_eval", logits.detach(), n, c, h, index, k, int(bool(with_self)), stats, best, ws, ws.numel())
+    return stats, best
+
+
+class _ScanSelflabelFn(torch.autograd.Function):
+    """mi_scan_selflabel_fwd / _bwd: (loss, info (3,), count (C,), target (B,), mask (B,)); the gradient goes to `strong` alone."""
+
+    @staticmethod
+    def forward(ctx, weak, strong, threshold, balance):
+        b, c = _scan_logits(weak, "weak", 1, SCAN_MAX_ROWS)
+        if strong.shape != weak.shape:
+            raise ValueError("weak is %s, strong %s" % (tuple(weak.shape), tuple(strong.shape)))
+        _scan_logits(strong, "strong", 1, SCAN_MAX_ROWS)
+        L.require_cuda(weak, "weak")
+        L.require_cuda(strong, "strong")
+        dev = strong.device
+        ws = L.workspace(L.lib().mi_scan_selflabel_workspace_bytes(b, c), dev, "scanselflabel")
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        info = torch.empty((3,), dtype=torch.int32, device=dev)
+        count = torch.empty((c,), dtype=torch.int32, device=dev)
+        target = torch.empty((b,), dtype=torch.int32, device=dev)
+        mask = torch.empty((b,), dtype=torch.uint8, device=dev)
+        denom = torch.empty((), dtype=torch.float64, device=dev)
+        L.call("mi_scan_selflabel_fwd", weak, strong, b, c, float(threshold), int(bool(balance)), loss, info, count, target, mask,
+               denom, ws, ws.numel())
+        ctx.save_for_backward(strong, info, count, target, mask, denom)
+        ctx.dims, ctx.balance = (b, c), int(bool(balance))
+        ctx.mark_non_differentiable(info, count, target, mask)
+        return loss, info, count, target, mask
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        strong, info, count, target, mask, denom = ctx.saved_tensors
+        b, c = ctx.dims
+        dl = dloss.contiguous().float()                    # read on the device: no host sync
+        ds = torch.empty_like(strong)
+        L.call("mi_scan_selflabel_bwd", strong, b, c, ctx.balance, info, count, target, mask, denom, dl, ds)
+        return None, ds, None, None
+
+
+def scan_selflabel(weak, strong, threshold, balance=True):
+    """scan_selflabel_loss with the rows' targets and mask as well: -> (loss, info, count, target (B,) int32, mask (B,) uint8)."""
+    return _ScanSelflabelFn.apply(weak.detach(), strong, float(threshold), bool(balance))
+
+
+def scan_selflabel_loss(weak, strong, threshold, balance=True):
+    """SCAN's self-labelling loss of one head (the reference's ConfidenceBasedCE): weak, strong (B, C) fp32 logits, contiguous,
+    1 <= C <= 64, B <= 65536.  A row whose largest softmax(weak) probability exceeds `threshold` is confident; its target is that
+    class; the loss is the cross-entropy of softmax(strong) against the targets over the confident rows, each weighted - with
+    `balance` - by the inverse share of its class among them, divided by the sum of the weights.
+    -> (loss (), differentiable with respect to `strong` only; info (3,) int32 = confident rows, classes present, B; count (C,)
+    int32 = confident rows per class).  No confident row: loss 0 and a zero gradient, nothing raised (the module
+    models.loss.ConfidenceBasedCE raises as the reference does).  The same input gives the same bytes, forward and backward."""
+    return scan_selflabel(weak, strong, threshold, balance)[:3]

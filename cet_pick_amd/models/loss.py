@@ -299,6 +299,56 @@ class MultiHeadSCANLoss(nn.Module):
         return H.scan_loss(anchors, neighbors, self.nheads, self.entropy_weight)
 
 
+class MaskedCrossEntropyLoss(nn.Module):
+    """loss.py:55-66: forward(input, target, mask, weight, reduction='mean') - the cross-entropy of the rows of `input` (b,
+    num_classes) where `mask` is set against `target`, each row weighted by weight[target] (None: 1) and the sum divided by the sum
+    of the weights; ValueError on an all-zero mask, as the reference (one host read).  On the device this is the self-label kernel
+    fed with logits that reproduce the given target and mask (csrc/scan_selflabel.hip); `weight` may only be the
+    reference's own: None, or the inverse class shares ConfidenceBasedCE forms - any other weight vector is refused."""
+
+    def forward(self, input, target, mask, weight, reduction="mean"):
+        if reduction != "mean":
+            raise ValueError("MaskedCrossEntropyLoss is built for reduction='mean', got %r" % (reduction,))
+        L.require_cuda(input, "input")
+        if not bool((mask != 0).any()):
+            raise ValueError("Mask in MaskedCrossEntropyLoss is all zeros.")
+        b, c = input.shape
+        # weak logits whose softmax has the given target and mask: 100 on the target of a masked row (probability 1 > 0.5 in
+        # float64 for c <= 64), 0 everywhere on an unmasked row (probability 1 / c <= 0.5, or c = 1: handled by the bias below)
+        weak = torch.zeros((b, c), dtype=torch.float32, device=input.device)
+        rows = torch.nonzero(mask.reshape(-1) != 0).reshape(-1)
+        weak[rows, target.reshape(-1)[rows].long()] = 100.0
+        if c == 1 and not bool((mask != 0).all()):
+            raise ValueError("MaskedCrossEntropyLoss with one class needs every row masked")
+        loss, info, count, got_target, _ = H.scan_selflabel(weak, input.contiguous(), 0.5, weight is not None)
+        if weight is not None:
+            n = int(info[0])                               # (the reference's own weights: 1 / (counts.float() / n), else 1)
+            want = torch.ones(c, dtype=torch.float32, device=input.device)
+            present = count > 0
+            want[present] = 1 / (count[present].float() / n)
+            if not torch.allclose(want, weight.to(want), rtol=1e-6, atol=0):
+                raise ValueError("MaskedCrossEntropyLoss takes the class-balancing weights of ConfidenceBasedCE or None")
+        return loss
+
+
+class ConfidenceBasedCE(nn.Module):
+    """loss.py:15-53, SCAN's self-labelling loss: forward(anchors_weak, anchors_strong) -> the cross-entropy of the strong logits
+    against the classes the weak logits are confident of (largest probability above `threshold`), with `apply_class_balancing`
+    each class weighted by its inverse share among the confident rows.  ValueError when no row is confident, as the reference
+    (one host read); hipops.scan_selflabel_loss is the form that never reads the host and gives loss 0 there."""
+
+    def __init__(self, threshold, apply_class_balancing):
+        super().__init__()
+        self.threshold = threshold
+        self.apply_class_balancing = apply_class_balancing
+
+    def forward(self, anchors_weak, anchors_strong):
+        loss, info, _ = H.scan_selflabel_loss(anchors_weak, anchors_strong, self.threshold, self.apply_class_balancing)
+        if int(info[0]) == 0:
+            raise ValueError("Mask in MaskedCrossEntropyLoss is all zeros.")
+        return loss
+
+
 class UnbiasedConLoss(nn.Module):
     """loss.py:571-699: debiased contrastive regularisation; returns (supervised, unsupervised) terms."""
 

@@ -4,7 +4,9 @@ stored exploration embeddings (utils/scan.py, csrc/scan_loss.hip, DESIGN.md 4.25
     python -m cet_pick_amd.scan_main --input exp/.../all_output_info.npz --path OUT --nclusters 10 [--nheads 1]
                                      [--num_neighbor 20] [--graph OUT/knn_graph.npz] [--num_epochs 100] [--batch_size 1024]
                                      [--lr 1e-3] [--weight_decay 1e-4] [--entropy_weight 2.0] [--seed 317] [--min_conf 0]
-                                     [--load_model OUT/scan_heads.pth] [--gpus 0]
+                                     [--load_model OUT/scan_heads.pth] [--gpus 0] [--select_head epoch|graph]
+                                     [--selflabel_epochs 0] [--selflabel_threshold 0.99] [--selflabel_lr 1e-4]
+                                     [--no_class_balancing]
 
 --nheads linear heads on the rows of `pred` are trained so that a pick and a random one of [itself, its --num_neighbor graph
 neighbours] get the same class while the classes stay balanced.  --graph takes the `index` of a knn_graph.npz that plot_2d wrote
@@ -19,8 +21,25 @@ pick itself excluded).  --load_model classifies with stored heads and trains not
                             consistency, entropy per head, the mean over the last epoch's batches (with --load_model: the stored
                             best loss, NaN elsewhere); prob (N, nclusters) f32 of the best head.  interactive_to_training_coords --input OUT/scan_labels.npz --labels ... reads it.
 
-The optimiser defaults (Adam, lr 1e-3, weight decay 1e-4, 100 epochs, batch 1024) are the reference's SCAN settings and are
-unmeasured on real data here.  Not made: the backbone-in-the-loop `scan` / `scan2d3d` tasks and SCAN's self-labelling step.
+--select_head graph chooses the best head as the reference's scan_evaluate does (csrc/scan_selflabel.hip): every
+head is scored on every pick against all entries of [itself, its graph neighbours] under the final weights, total = consistency
+- entropy, and `stats` holds these figures for every head; also with --load_model (which then needs --graph or searches).  The
+default, epoch, is the lowest mean training loss of the last epoch.
+
+--selflabel_epochs E > 0 adds SCAN's third step: the best head alone is trained on with the confidence-based cross-entropy (a
+pick whose class probability exceeds --selflabel_threshold is its own label; the graph-neighbour draw stands in for the strong
+view; classes weighted by their inverse share unless --no_class_balancing; Adam, --selflabel_lr, --weight_decay).  With
+--load_model the stored best head is self-labelled and nothing is clustered.  scan_heads.pth and scan_labels.npz are the
+clustering step's, as without the flag; in addition
+
+    OUT/scan_heads_selflabel.pth   the same layout with the one head (cluster_head.0.*): --load_model reads it with --nheads 1
+    OUT/scan_labels_selflabel.npz  the keys of scan_labels.npz from that head (head 0; stats: its graph figures), and
+                                   selflabel_stats (E, 3) f32: per epoch the mean loss, the share of confident picks, the mean
+                                   number of classes present in a batch
+
+The optimiser defaults (Adam, lr 1e-3, weight decay 1e-4, 100 epochs, batch 1024) are the reference's SCAN settings, and
+--selflabel_threshold 0.99 and --selflabel_lr 1e-4 are SCAN's published self-labelling settings; all are unmeasured on real data
+here.  Not made: the backbone-in-the-loop `scan` / `scan2d3d` tasks (with them the image augmentation of the strong view).
 """
 import argparse
 import os
@@ -44,6 +63,13 @@ def add_arguments(parser):
     parser.add_argument("--min_conf", type=float, default=0.0, help="picks whose class probability is below this get label -1")
     parser.add_argument("--load_model", default=None, help="scan_heads.pth: classify only")
     parser.add_argument("--gpus", default="0", help="GPU index; -1 (CPU) is refused")
+    parser.add_argument("--select_head", choices=("epoch", "graph"), default="epoch",
+                        help="best head: lowest mean loss of the last epoch, or lowest total over the whole graph (scan_evaluate)")
+    parser.add_argument("--selflabel_epochs", type=int, default=0, help="self-labelling epochs on the best head; 0: none")
+    parser.add_argument("--selflabel_threshold", type=float, default=0.99,
+                        help="a pick above this class probability labels itself, in [0, 1) (SCAN's 0.99; unmeasured on real data)")
+    parser.add_argument("--selflabel_lr", type=float, default=1e-4, help="Adam's rate of the self-labelling (SCAN's 1e-4; unmeasured)")
+    parser.add_argument("--no_class_balancing", action="store_true", help="self-labelling without the inverse-share class weights")
     return parser
 
 
@@ -76,12 +102,18 @@ def main(args):
         raise RuntimeError("the MI355X path has no CPU mode (--gpus -1)")
     from .utils import scan as S
     S.check_sizes(args.nclusters, args.nheads)
+    if args.selflabel_epochs < 0:
+        raise ValueError("--selflabel_epochs must be >= 0, got %d" % args.selflabel_epochs)
+    if not 0.0 <= args.selflabel_threshold < 1.0:
+        raise ValueError("--selflabel_threshold must be in [0, 1), got %g" % args.selflabel_threshold)
     data = np.load(args.input)
     projs = np.ascontiguousarray(data["pred"], dtype=np.float32)
     projs = projs.reshape(projs.shape[0], -1)
     names, coords = data["name"], data["coords"]
     n = len(projs)
-    index = load_graph(args.graph, n) if args.graph and not args.load_model else None
+    by_graph, selflabel = args.select_head == "graph", args.selflabel_epochs > 0
+    need_graph = not args.load_model or by_graph or selflabel
+    index = load_graph(args.graph, n) if args.graph and need_graph else None
     import torch
     device = torch.device("cuda", gpu)
     os.makedirs(args.path, exist_ok=True)
@@ -95,6 +127,8 @@ def main(args):
         stats[heads.best_loss_head, 0] = heads.best_loss
         print("[cet_pick_amd] scan_main: %s: %d heads of %d classes after %d epochs, best head %d (loss %.6g); classifying %d picks"
               % (args.load_model, heads.nheads, heads.nclusters, heads.epoch, heads.best_loss_head, heads.best_loss, n))
+        if index is None and need_graph:
+            index = search_graph(projs, args.num_neighbor, device)
     else:
         batch_size = args.batch_size
         if batch_size > n:
@@ -111,14 +145,40 @@ def main(args):
         history = heads.fit(projs, index, num_epochs=args.num_epochs, batch_size=batch_size, lr=args.lr,
                             weight_decay=args.weight_decay, entropy_weight=args.entropy_weight, log=log)
         stats = history[-1]
+    if by_graph:
+        stats = graph_stats(heads, projs, index)
+    if not args.load_model:
         heads.save(os.path.join(args.path, "scan_heads.pth"))
+    out = write_labels(args, heads, projs, names, coords, stats, "scan_labels.npz")
+    if selflabel:
+        def log_selflabel(epoch, mean):
+            print("[cet_pick_amd] scan_main: self-label epoch %d: loss %.5f confident %.4f classes present %.2f"
+                  % (epoch, mean[0], mean[1], mean[2]))
+
+        one, sl_stats = heads.selflabel(projs, index, heads.best_loss_head, num_epochs=args.selflabel_epochs,
+                                        batch_size=min(args.batch_size, n), lr=args.selflabel_lr, threshold=args.selflabel_threshold,
+                                        balance=not args.no_class_balancing, log=log_selflabel, weight_decay=args.weight_decay)
+        stats = graph_stats(one, projs, index)             # (best_loss of the checkpoint: this head's total over the graph)
+        one.save(os.path.join(args.path, "scan_heads_selflabel.pth"))
+        write_labels(args, one, projs, names, coords, stats, "scan_labels_selflabel.npz", selflabel_stats=sl_stats.astype(np.float32))
+    return out
+
+
+def graph_stats(heads, projs, index):
+    stats = heads.evaluate(projs, index)
+    print("[cet_pick_amd] scan_main: over the graph: %s; best head %d" % ("  ".join(
+        "head %d total %.5f consistency %.5f entropy %.5f" % (h, m[0], m[1], m[2]) for h, m in enumerate(stats)), heads.best_loss_head))
+    return stats
+
+
+def write_labels(args, heads, projs, names, coords, stats, file_name, **more):
     label, conf, counts, prob = heads.predict(projs, with_prob=True)
     head, c = heads.best_loss_head, heads.nclusters
     out = labels_file(names, coords, label, conf, head, counts, stats, prob[:, head * c:(head + 1) * c], args.min_conf)
-    np.savez(os.path.join(args.path, "scan_labels.npz"), **out)
+    np.savez(os.path.join(args.path, file_name), **out, **more)
     print("[cet_pick_amd] scan_main: %d picks, head %d of %d, %d below --min_conf %g; picks per class: %s -> %s"
-          % (n, head, heads.nheads, int((out["label"] < 0).sum()), args.min_conf, " ".join(str(int(v)) for v in counts[head]),
-             os.path.join(args.path, "scan_labels.npz")))
+          % (len(projs), head, heads.nheads, int((out["label"] < 0).sum()), args.min_conf,
+             " ".join(str(int(v)) for v in counts[head]), os.path.join(args.path, file_name)))
     return out
 
 

@@ -7,6 +7,9 @@ Linear of the package takes - and the loss of all heads with its gradient is csr
 multiples of 16: the embeddings get zero columns and the stacked heads zero rows up to the next one, and the logits are cut back to
 nheads x nclusters columns in front of the loss (no -inf ever enters a softmax).  torch.optim.Adam is the optimiser; the
 pairs of an epoch are drawn on the host, copied once, and gathered on the device.  There is no CPU path.
+
+After the clustering step (csrc/scan_selflabel.hip): ScanHeads.evaluate scores every head over the whole graph
+as the reference's scan_evaluate does, ScanHeads.selflabel trains the best head on alone with the confidence-based cross-entropy.
 """
 import numpy as np
 import torch
@@ -33,6 +36,13 @@ def draw_neighbours(index, seed, epoch, batch_size):
     table = np.concatenate([np.arange(n, dtype=np.int64)[:, None], index.astype(np.int64)], axis=1)
     anchor = perm[:(n // batch_size) * batch_size].astype(np.int64)
     return anchor, table[anchor, column[anchor]]
+
+
+def selflabel_draws(index, seed, first_epoch, num_epochs, batch_size):
+    """The draws of the self-labelling epochs: draw_neighbours with the epoch numbering continued after the `first_epoch`
+    clustering epochs, so no self-label epoch repeats a clustering epoch's pairs.  Yields (epoch, anchor, strong row)."""
+    for epoch in range(int(first_epoch), int(first_epoch) + int(num_epochs)):
+        yield (epoch,) + draw_neighbours(index, seed, epoch, batch_size)
 
 
 def check_sizes(nclusters, nheads):
@@ -173,6 +183,78 @@ class ScanHeads:
             self.best_loss_head = int(np.argmin(last))
             self.best_loss = float(last[self.best_loss_head])
             return np.stack(self.history)
+
+    def _graph(self, index, n):
+        """index (N, k) checked once on the host -> int32 on the device"""
+        index = np.asarray(index)
+        if index.ndim != 2 or index.shape[0] != n:
+            raise ValueError("the graph has %s rows, the embeddings %d" % (index.shape[:1], n))
+        if not 1 <= index.shape[1] <= H.SCAN_MAX_NEIGHBOURS:
+            raise ValueError("the graph must have 1..%d neighbours per pick, got %d" % (H.SCAN_MAX_NEIGHBOURS, index.shape[1]))
+        if index.min() < 0 or index.max() >= n:
+            raise ValueError("the graph names a pick outside 0..%d" % (n - 1))
+        return torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(self.device)
+
+    def evaluate(self, x, index):
+        """The reference's scan_evaluate: every head scored on every pick against all entries of [itself, its graph neighbours
+        index (N, k)] under the weights as they stand.  -> stats (nheads, 3): total = consistency - entropy, consistency, entropy;
+        sets best_loss_head (lowest total, lowest index on a tie) and best_loss.  One host read."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            xp = self._embeddings(x)
+            table = self._graph(index, xp.shape[0])
+            stats, best = H.scan_graph_eval(self._logits(xp).contiguous(), table, self.nheads, with_self=True, validate=False)
+            both = torch.cat([stats.reshape(-1), best.float()]).cpu().numpy()
+            stats = both[:-1].reshape(self.nheads, 3)
+            self.best_loss_head = int(both[-1])
+            self.best_loss = float(stats[self.best_loss_head, 0])
+            return stats
+
+    def selflabel(self, x, index, head, num_epochs=10, batch_size=1024, lr=1e-4, threshold=0.99, balance=True, log=None,
+                  weight_decay=1e-4):
+        """SCAN's third step on head `head` alone (the reference's load_model_selflabel keeps the best head only): a one-head
+        ScanHeads is rebuilt from that slice and trained with the confidence-based cross-entropy.  Per step ONE HipLinear call on
+        [anchors; strong rows]: the weak logits are the anchors' own, detached; the strong rows are an entry of [the pick, its
+        graph neighbours], the draw of fit() with the epoch numbering continued - stored embeddings have no image augmentation, so
+        the graph neighbour stands in for the reference's strong view.  Adam.
+        -> (the one-head ScanHeads, stats (num_epochs, 3): per epoch the mean loss, the share of confident picks and the mean number
+        of classes present over the epoch's batches - one host read per epoch)."""
+        if not 0 <= int(head) < self.nheads:
+            raise ValueError("head must be in 0..%d, got %d" % (self.nheads - 1, head))
+        if not 0.0 <= float(threshold) < 1.0:
+            raise ValueError("the confidence threshold must be in [0, 1), got %g" % threshold)
+        with torch.cuda.device(self.device):
+            one = ScanHeads(self.d, self.nclusters, 1, seed=self.seed, device=self.device)
+            sd = self.state_dict()
+            one.load_state_dict({"cluster_head.0.weight": sd["cluster_head.%d.weight" % head],
+                                 "cluster_head.0.bias": sd["cluster_head.%d.bias" % head]})
+            one.epoch = self.epoch
+            xp = one._embeddings(x)
+            index = one._graph(index, xp.shape[0]).cpu().numpy()
+            bs = int(batch_size)
+            if bs > H.SCAN_MAX_ROWS:
+                raise ValueError("batch_size is at most %d, got %d" % (H.SCAN_MAX_ROWS, bs))
+            one.optimizer = torch.optim.Adam(one.lin.parameters(), lr=lr, weight_decay=weight_decay)
+            history = []
+            for epoch, anchor, strong in selflabel_draws(index, one.seed, one.epoch, num_epochs, bs):
+                pairs = torch.from_numpy(np.stack([anchor.reshape(-1, bs), strong.reshape(-1, bs)], axis=1)).to(self.device)
+                acc = torch.zeros((3,), dtype=torch.float32, device=self.device)
+                for rows in pairs:                         # (2, bs): the anchors, then their strong rows
+                    z = one._logits(xp.index_select(0, rows.reshape(-1)))
+                    loss, info, _ = H.scan_selflabel_loss(z[:bs].detach().contiguous(), z[bs:].contiguous(), threshold, balance)
+                    one.optimizer.zero_grad(set_to_none=True)
+                    loss.backward()
+                    one.optimizer.step()
+                    acc[0] += loss.detach()
+                    acc[1:] += info[:2]
+                mean = (acc / len(pairs)).cpu().numpy()    # the epoch's one host read
+                mean[1] /= bs
+                history.append(mean)
+                one.epoch = epoch + 1
+                if log is not None:
+                    log(one.epoch, mean)
+            if history:
+                one.best_loss = float(history[-1][0])
+            return one, np.stack(history) if history else np.zeros((0, 3), np.float32)
 
     def predict(self, x, with_prob=False):
         """-> label (N, nheads) int32, conf (N, nheads) fp32, counts (nheads, nclusters) int32 [, prob (N, nheads nclusters) fp32]

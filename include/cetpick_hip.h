@@ -1241,6 +1241,42 @@ int mi_scan_loss_bwd(const float* anchors, const float* neighbours, int B, int C
 int mi_scan_assign(const float* logits, long n, int C, int H, int32_t* class_out, float* conf_out, float* prob_out,
                    int32_t* counts_out, mi_stream_t stream);
 
+/* After SCAN's clustering step (csrc/scan_selflabel.hip): the heads scored over the whole neighbour graph (the
+ * reference's scan_evaluate, trains/eval_utils.py) and the self-labelling loss (ConfidenceBasedCE with MaskedCrossEntropyLoss,
+ * models/loss.py:15-66).  Layout, limits on C and H, float64 after the fp32 row maximum and the fixed order of every sum are those
+ * of the entries above: no floating-point atomic, the same input gives the same bytes.  MI_E_ARG outside the limits, before anything
+ * is enqueued; the *_workspace_bytes functions need no device and return 0 outside the limits.
+ *   mi_scan_graph_eval  logits (N, H C), 1 <= N < 2^31; index (N, k) int32, 1 <= k <= 64, entries in 0..N-1 (NOT checked on the
+ *                       device: the caller validates the table); with_self != 0 makes the pick itself one more table entry, in
+ *                       front, so K = k + 1, else K = k.  stats_out (H, 3) fp32 = total, consistency, entropy per head with
+ *                         consistency = -(1 / (N K)) sum_i sum_j max(log(p_i . p_j), -100)   over the K entries j of row i
+ *                         entropy = -sum_c x_c log x_c, x = max((1 / N) sum_i p_i, 1e-8)       total = consistency - entropy
+ *                       (weight 1, as scan_evaluate); *best_out int32 = the head with the lowest total, the lowest index on an
+ *                       exact tie.  Three launches: the float64 probabilities of every row into the workspace (N H C doubles) with
+ *                       their sums per chunk of MI_SCAN_CHUNK rows; the pairs, a neighbour's probabilities read from the workspace;
+ *                       one workgroup that adds the chunks in ascending order and finishes every head.
+ *   mi_scan_selflabel_fwd  one head: weak, strong (B, C) fp32, 1 <= B <= 65536.  Per row p = softmax(weak), target = its argmax
+ *                       (the lowest index on a tie), mask = max p > threshold compared in float64; n = masked rows, count_c = masked
+ *                       rows with target c; w_c = 1 / (count_c / n), formed in fp32 with two correctly rounded divisions, where
+ *                       balance != 0 and count_c > 0, else 1;
+ *                         loss = sum_masked w_t (-log softmax(strong)_t) / sum_masked w_t   (F.cross_entropy's weighted mean)
+ *                       loss_out fp32; info_out (3,) int32 = n, classes present, B; count_out (C,) int32; target_out (B,) int32;
+ *                       mask_out (B,) uint8; *denom_out float64 = sum_masked w_t for the backward pass.  n = 0: loss 0, denom 0,
+ *                       nothing divided.  Three launches: targets, mask and counts (integer atomics); the weighted sums per chunk;
+ *                       one wave that adds the chunks in ascending order.
+ *   mi_scan_selflabel_bwd  d_strong (B, C) fp32 = *dloss (device) mask_i w_t / denom (softmax(strong_i) - onehot(t_i)), one launch;
+ *                       zeros for n = 0.  The weak logits get no gradient: target and mask are not differentiable. */
+size_t mi_scan_graph_eval_workspace_bytes(long N, int C, int H);
+int mi_scan_graph_eval(const float* logits, long N, int C, int H, const int32_t* index, int k, int with_self, float* stats_out,
+                       int32_t* best_out, void* ws, size_t ws_bytes, mi_stream_t stream);
+size_t mi_scan_selflabel_workspace_bytes(int B, int C);
+int mi_scan_selflabel_fwd(const float* weak, const float* strong, int B, int C, double threshold, int balance, float* loss_out,
+                          int32_t* info_out, int32_t* count_out, int32_t* target_out, uint8_t* mask_out, double* denom_out, void* ws,
+                          size_t ws_bytes, mi_stream_t stream);
+int mi_scan_selflabel_bwd(const float* strong, int B, int C, int balance, const int32_t* info, const int32_t* count,
+                          const int32_t* target, const uint8_t* mask, const double* denom, const float* dloss, float* d_strong,
+                          mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
