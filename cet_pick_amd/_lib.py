@@ -282,6 +282,12 @@ SIGNATURES = {
     "mi_scan_selflabel_workspace_bytes": (_Z, [_I, _I]),
     "mi_scan_selflabel_fwd": (_I, [_P, _P, _I, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _S]),
     "mi_scan_selflabel_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S]),
+    # the exact silhouette of a clustering and the contingency table of two (csrc/cluster_quality.hip)
+    "mi_silhouette_workspace_bytes": (_Z, [_L, _I, _I]),
+    "mi_silhouette_sums": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _Z, _S]),
+    "mi_silhouette_finalise_workspace_bytes": (_Z, [_L, _I, _I]),
+    "mi_silhouette_finalise": (_I, [_P, _P, _P, _L, _I, _I] + [_P] * 10 + [_Z, _S]),
+    "mi_label_contingency": (_I, [_P, _P, _L, _I, _I, _P, _S]),
 }
 
 _lib = None

@@ -94,16 +94,9 @@ __device__ __forceinline__ void tile_product(f32x16 (&acc)[RM], const unsigned c
     }
 }
 
-namespace {     // a kernel of the including file: every code object registers a host stub of its own
-
-// One wave per column j of x (cols, d): its cut into the image and its squared norm, pad_norm for the columns past the end
-// (their planes are zeros).  Any whole number of waves per workgroup; the grid covers KT 32 columns.
-__global__ __launch_bounds__(256) void prep_kernel(const float* x, long cols, int d, int KS, float pad_norm, unsigned char* img,
-                                                   float* norm) {
-    const long j = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const bool ok = j < cols;
-    const float* row = x + (size_t)j * d;
+// One wave cuts `row` (d features; zeros when !ok) into column j of the image and returns its squared norm in every lane: the
+// body of prep_kernel, and of a kernel that gathers its columns in an order of its own (cluster_quality.hip).
+__device__ __forceinline__ float cut_column(const float* row, bool ok, long j, int d, int KS, int lane, unsigned char* img) {
     const bool vec = (d & 3) == 0;
     float s = 0.f;
     for (int g = lane; g < 2 * KS; g += 64) {
@@ -119,7 +112,19 @@ __global__ __launch_bounds__(256) void prep_kernel(const float* x, long cols, in
         for (int pl = 0; pl < 3; ++pl)
             *reinterpret_cast<u32x4*>(img + ((((size_t)ct * KS + ks) * 3 + pl) * 64 + h * 32 + l32) * 16) = o[pl];
     }
-    s = wave_sum(s);
+    return wave_sum(s);
+}
+
+namespace {     // a kernel of the including file: every code object registers a host stub of its own
+
+// One wave per column j of x (cols, d): its cut into the image and its squared norm, pad_norm for the columns past the end
+// (their planes are zeros).  Any whole number of waves per workgroup; the grid covers KT 32 columns.
+__global__ __launch_bounds__(256) void prep_kernel(const float* x, long cols, int d, int KS, float pad_norm, unsigned char* img,
+                                                   float* norm) {
+    const long j = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const bool ok = j < cols;
+    const float s = cut_column(x + (size_t)j * d, ok, j, d, KS, lane, img);
     if (lane == 0) norm[j] = ok ? s : pad_norm;
 }
 

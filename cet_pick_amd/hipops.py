@@ -3127,3 +3127,95 @@ def scan_selflabel_loss(weak, strong, threshold, balance=True):
     int32 = confident rows per class).  No confident row: loss 0 and a zero gradient, nothing raised (the module
     models.loss.ConfidenceBasedCE raises as the reference does).  The same input gives the same bytes, forward and backward."""
     return scan_selflabel(weak, strong, threshold, balance)[:3]
+
+
+# ---- how good a clustering is: exact silhouette and contingency table (csrc/cluster_quality.hip, DESIGN.md 4.28) -------------
+
+SILHOUETTE_MAX_K = 1024                   # fine clusters of silhouette_sums, classes of silhouette_finalise
+
+
+def _quality_labels(t, name, n, device, hi, validate):
+    """labels (n,) int32, contiguous, on `device`; with `validate` their range [0, hi) is checked on the device (one host read)."""
+    L.require_cuda(t, name, torch.int32)
+    if t.dim() != 1 or t.shape[0] != n or not t.is_contiguous() or t.device != device:
+        raise L.HipExtensionError("%s must be a contiguous (%d,) int32 tensor on %s, got %s on %s"
+                                  % (name, n, device, tuple(t.shape), t.device))
+    if validate and n:
+        lo, top = (int(v) for v in torch.aminmax(t))
+        if lo < 0 or top >= hi:
+            raise ValueError("%s holds %d, outside 0..%d" % (name, lo if lo < 0 else top, hi - 1))
+    return t
+
+
+def silhouette_sums(x, labels, k, validate=True):
+    """sums (N, k) float64 on the device: sums[i][c] = the sum over the members j != i of fine cluster c of |x_i - x_j|, the
+    squared distance formed as knn_search's "l2" value (bf16x3 on the matrix cores), its square root and the sums in float64; the
+    N x N distances are never stored.  x (N, d) fp32 contiguous, labels (N,) int32 in [0, k), k <= 1024.  `validate` checks the
+    labels' range here, with one host read: a label outside it is a ValueError that names it (the kernel would leave such a pick
+    out).  The same input gives the same bytes."""
+    x = _km_x(x)
+    n, d = x.shape
+    k = int(k)
+    labels = _quality_labels(labels, "labels", n, x.device, k, validate)
+    what = "(N=%d, d=%d, k=%d)" % (n, d, k)
+    nbytes = L.lib().mi_silhouette_workspace_bytes(n, d, k)
+    if nbytes == 0:
+        L.check(-3, "mi_silhouette_workspace_bytes" + what)
+    order = torch.sort(labels, stable=True)[1].to(torch.int32)          # plumbing: picks by label, ascending index within one
+    sums = torch.empty((n, k), dtype=torch.float64, device=x.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    L.call("mi_silhouette_sums", x, labels, order, n, d, k, sums, ws, ws.numel())
+    return sums
+
+
+def silhouette_finalise(sums, labels, class_of=None):
+    """The silhouette of every pick from silhouette_sums' table: sums (N, k) float64, labels (N,) int32 fine labels in [0, k),
+    class_of (k,) int32 -> [0, C) the class of every fine cluster (None: the identity, C = k).  -> dict of device tensors: s, a,
+    b (N,) float64 (a: mean distance to the own class, b: to the nearest other non-empty class, s = (b - a) / max(a, b); a = s =
+    0 for the only member of a class), nearest (N,) int32 (the class attaining b, the lowest on a tie), class_mean (C,) float64
+    (NaN for a class without members), class_count (C,) int32, mean () float64, confusion (C, C) int32 [own][nearest].  Fewer than
+    two non-empty classes, or no class with two members, is a ValueError (sklearn raises there too); this reads three integers
+    from the device."""
+    L.require_cuda(sums, "sums", torch.float64)
+    if sums.dim() != 2 or not sums.is_contiguous():
+        raise L.HipExtensionError("sums must be a contiguous (N, k) float64 tensor, got %s" % (tuple(sums.shape),))
+    n, k = sums.shape
+    dev = sums.device
+    labels = _quality_labels(labels, "labels", n, dev, k, True)
+    if class_of is None:
+        class_of, c = torch.arange(k, dtype=torch.int32, device=dev), k
+    else:
+        class_of = _quality_labels(class_of, "class_of", k, dev, SILHOUETTE_MAX_K, True)
+        c = int(class_of.max()) + 1
+    if c < 2:
+        raise ValueError("the silhouette needs at least 2 classes, got %d" % c)
+    nbytes = L.lib().mi_silhouette_finalise_workspace_bytes(n, k, c)
+    if nbytes == 0:
+        L.check(-3, "mi_silhouette_finalise_workspace_bytes(N=%d, k=%d, C=%d)" % (n, k, c))
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    out = dict(s=torch.empty(n, **f64), a=torch.empty(n, **f64), b=torch.empty(n, **f64), nearest=torch.empty(n, **i32),
+               class_mean=torch.empty(c, **f64), class_count=torch.empty(c, **i32), mean=torch.empty((), **f64),
+               confusion=torch.empty((c, c), **i32))
+    info = torch.empty(3, **i32)
+    ws = L.workspace(nbytes, dev, "silhouette")
+    L.call("mi_silhouette_finalise", sums, labels, class_of, n, k, c, out["s"], out["a"], out["b"], out["nearest"],
+           out["class_mean"], out["class_count"], out["mean"], out["confusion"], info, ws, ws.numel())
+    nonempty, largest, status = (int(v) for v in info.cpu())
+    if status:
+        raise ValueError("the silhouette needs 2 classes with members and one class with 2 members: %d classes have members, the "
+                         "largest has %d" % (nonempty, largest))
+    return out
+
+
+def label_contingency(a, b, ca, cb):
+    """table (ca, cb) int64 on the device: the picks with labels (a_i, b_i); a, b (N,) int32 in [0, ca) and [0, cb)."""
+    L.require_cuda(a, "a", torch.int32)
+    n, ca, cb = a.shape[0] if a.dim() == 1 else -1, int(ca), int(cb)
+    if n < 1 or not isinstance(b, torch.Tensor) or tuple(b.shape) != (n,):
+        raise ValueError("a and b must be (N,) label arrays of one length, N >= 1, got %s and %s"
+                         % (tuple(a.shape), tuple(getattr(b, "shape", ()))))
+    a = _quality_labels(a, "a", n, a.device, ca, True)
+    b = _quality_labels(b, "b", n, a.device, cb, True)
+    table = torch.empty((ca, cb), dtype=torch.int64, device=a.device)
+    L.call("mi_label_contingency", a, b, n, ca, cb, table)
+    return table

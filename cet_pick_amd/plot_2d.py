@@ -6,6 +6,7 @@ plot_2d.py; its pictures and thumbnails with --min_dist_vis):
                                    [--min_dist_umap 0.5] [--map_seed 42] [--colormap FILE.npy] [--umap_init random | spectral]
                                    [--label_map] [--target_weight 0.5] [--min_dist_vis 1.3e-3] [--save_out_img 1]
                                    [--plot_size 1500] [--class_gallery [--gallery_exemplars 8]]
+                                   [--quality] [--sweep_n_cluster 4,8,16] [--compare_labels FILE.npz]
 
 `pred` of the input is over-clustered by k-means on the MI355X (utils/kmeans.py: k = 256 centroids, 300 iterations, as the
 reference runs faiss), the centroids are merged into --n_cluster classes on the host (sklearn's SpectralClustering with the
@@ -86,6 +87,28 @@ final classes (`label` of kmeans_labels.npz: the merged classes where --n_cluste
     OUT/class_gallery.png (.webp)         one row per class: its number over its count, the mean patch, the deviation patch (one
                                           grey scale for all classes) and the exemplars - what --labels of
                                           interactive_to_training_coords is chosen from
+
+With --quality (this project's own: the file that says how good a clustering is) utils/cluster_quality.py with
+csrc/cluster_quality.hip make on the MI355X, in ONE pass over the N x N pairs of picks (no N x N matrix is stored):
+
+    OUT/cluster_quality.npz               the exact silhouette (scikit-learn's silhouette_samples, Euclidean over `pred`) under the
+                                          final classes (`label`): s, a, b (N,) f64 in pick order (a: mean distance to the own
+                                          class, b: to the nearest other class, s = (b - a) / max(a, b); a = s = 0 for the only
+                                          member of a class), nearest (N,) i32 (the class attaining b), class_mean (C,) f64 (NaN
+                                          for a class without members), class_count (C,) i32, confusion (C, C) i32
+                                          [own][nearest], mean; and the same under the k-means assignment itself (`assign`):
+                                          fine_s, fine_a, ... fine_mean.  One stdout line gives the two means.
+                                          --sweep_n_cluster 4,8,16 (implies --quality; each value in 2..k-1) merges the centroids
+                                          to every listed class count as --n_cluster does and scores each from the SAME pass:
+                                          sweep_n_cluster, sweep_mean, sweep_min_class_mean (the worst class), sweep_smallest_class
+                                          (its member count), and a printed table.  It does not change which --n_cluster the other
+                                          outputs use.  Needs sklearn, as --n_cluster does.
+                                          --compare_labels FILE.npz (implies --quality) reads `label` of another labeling of the
+                                          same picks (scan_labels.npz; what interactive_to_training_coords reads; -1 is a class of
+                                          its own) and adds compare_table (classes of `label` x classes of the file, i64),
+                                          compare_ids, compare_ids_other (the class ids of its rows and columns), compare_ari
+                                          (adjusted Rand index) and compare_nmi (normalised mutual information, arithmetic mean).
+                                          Another number of picks is a ValueError.
 """
 import argparse
 import os
@@ -132,6 +155,13 @@ def add_arguments(parser):
                         "class the mean patch, the spread and number of its members and its most typical members (needs subvol)")
     parser.add_argument("--gallery_exemplars", type=int, default=8, help="with --class_gallery: members shown per class, 1..64, "
                         "the nearest to their centroid first")
+    parser.add_argument("--quality", action="store_true", help="also write cluster_quality.npz: the exact silhouette of every pick "
+                        "under the final classes and under the k-means assignment")
+    parser.add_argument("--sweep_n_cluster", default=None, help="comma-separated class counts, each in 2..k-1: merge the centroids "
+                        "to each and add its silhouette to cluster_quality.npz (implies --quality; --n_cluster still decides the outputs)")
+    parser.add_argument("--compare_labels", default=None, help="FILE.npz with `label` of the same picks (scan_labels.npz): add the "
+                        "contingency table, adjusted Rand index and normalised mutual information against the final classes to "
+                        "cluster_quality.npz (implies --quality)")
     return parser
 
 
@@ -298,6 +328,63 @@ def write_class_gallery(path, patches, projs, centroids, assign, label, n_classe
           % (n_classes, int((g["count"] > 0).sum()), m, pic.shape[1], pic.shape[0], os.path.join(path, "class_gallery.png")))
 
 
+def quality_plan(args, n):
+    """The checks of --quality, --sweep_n_cluster and --compare_labels that need no device: (sweep list or None, the labels to
+    compare with or None), or None where none of the three flags is given."""
+    if not (args.quality or args.sweep_n_cluster is not None or args.compare_labels is not None):
+        return None
+    from .utils.cluster_quality import parse_sweep
+    sweep = None
+    if args.sweep_n_cluster is not None:
+        sweep = parse_sweep(args.sweep_n_cluster)
+        if max(sweep) >= args.k:
+            raise ValueError("--sweep_n_cluster merges the %d centroids into fewer classes, got %d" % (args.k, max(sweep)))
+    other = None
+    if args.compare_labels is not None:
+        held = np.load(args.compare_labels)
+        if "label" not in held.files:
+            raise ValueError("--compare_labels %s holds no 'label' (it has %s)" % (args.compare_labels, ", ".join(held.files)))
+        other = np.asarray(held["label"]).ravel()
+        if len(other) != n:
+            raise ValueError("--compare_labels %s labels %d picks, the input has %d" % (args.compare_labels, len(other), n))
+    return sweep, other
+
+
+def write_quality(path, projs, assign, label, class_of, centroids, k, plan, device):
+    """cluster_quality.npz under `path` (the module docstring lists its keys) and its stdout lines: one pass over the pairs of
+    picks on the device (utils/cluster_quality.SilhouetteSums) serves the final classes, the k-means assignment
+    and every class count of the sweep."""
+    import torch
+    from .utils.cluster_quality import SilhouetteSums, compare_labelings
+    sweep, other = plan
+    with torch.cuda.device(device):
+        sums = SilhouetteSums(projs, assign, k, device=device)
+        fine = sums.score()
+        final = fine if class_of is None else sums.score(class_of)
+        out = dict(final.arrays(), **fine.arrays("fine_"))
+        print("[cet_pick_amd] plot_2d: mean silhouette %.6f over the %d final classes, %.6f over the k-means assignment (%d "
+              "clusters with members) -> %s" % (final.mean, int((final.class_count > 0).sum()), fine.mean,
+                                                int((fine.class_count > 0).sum()), os.path.join(path, "cluster_quality.npz")))
+        if sweep is not None:
+            rows = []
+            for v in sweep:
+                r = sums.score(merge_centroids(centroids, v))
+                rows.append((v, r.mean, float(np.nanmin(r.class_mean)), int(r.class_count[r.class_count > 0].min())))
+            out.update(sweep_n_cluster=np.asarray([r[0] for r in rows], np.int32), sweep_mean=np.asarray([r[1] for r in rows]),
+                       sweep_min_class_mean=np.asarray([r[2] for r in rows]),
+                       sweep_smallest_class=np.asarray([r[3] for r in rows], np.int32))
+            print("[cet_pick_amd] plot_2d: n_cluster  mean silhouette  lowest class mean  smallest class")
+            for r in rows:
+                print("[cet_pick_amd] plot_2d: %9d  %15.6f  %17.6f  %14d" % r)
+        if other is not None:
+            cmp = compare_labelings(label, other, device=device)
+            out.update(compare_table=cmp.table, compare_ari=np.float64(cmp.ari), compare_nmi=np.float64(cmp.nmi),
+                       compare_ids=cmp.ids_a, compare_ids_other=cmp.ids_b)
+            print("[cet_pick_amd] plot_2d: against the other labels: %d x %d classes, adjusted Rand index %.6f, normalised mutual "
+                  "information %.6f" % (cmp.table.shape[0], cmp.table.shape[1], cmp.ari, cmp.nmi))
+    np.savez(os.path.join(path, "cluster_quality.npz"), **out)
+
+
 def unit_square(y):
     """(y - min) / (max - min) per axis, as the reference normalises its map (an axis of one value maps to 0)."""
     lo, hi = y.min(0), y.max(0)
@@ -360,6 +447,7 @@ def main(args):
         if gallery_patches.ndim != 4 or len(gallery_patches) != len(projs) or 0 in gallery_patches.shape:
             raise ValueError("'subvol' of %s must be (%d, C, h, w), got %s" % (args.input, len(projs), gallery_patches.shape))
         gallery_patches = np.ascontiguousarray(gallery_patches[:, 0], dtype=np.float32)       # channel 0, as the pictures show it
+    quality = quality_plan(args, len(projs))
     if with_vis:
         pass                                               # the line above says what is written
     elif with_umap:
@@ -384,8 +472,9 @@ def main(args):
         D, I = km.assign(projs)
     assign = I[:, 0].astype(np.int32)
     centroids = km.centroids
+    class_of = None                                        # of every centroid, where --n_cluster merges
     if 0 < args.n_cluster < args.k:
-        y = merge_centroids(centroids, args.n_cluster)
+        y = class_of = merge_centroids(centroids, args.n_cluster)
         print("Actual number of clusters is:", len(set(y.tolist())))
         label = y[assign].astype(np.int32)
     else:
@@ -402,6 +491,8 @@ def main(args):
         n_classes = args.n_cluster if 0 < args.n_cluster < args.k else args.k      # the final labels: merged classes, or centroids
         write_class_gallery(args.path, gallery_patches, projs, centroids, assign, label, n_classes, args.gallery_exemplars,
                             torch.device("cuda", gpu))
+    if quality is not None:
+        write_quality(args.path, projs, assign, label, class_of, centroids, args.k, quality, torch.device("cuda", gpu))
     if args.num_neighbor is not None:
         if with_umap:
             if args.umap_init == "spectral":

@@ -6,7 +6,7 @@ stored exploration embeddings (utils/scan.py, csrc/scan_loss.hip, DESIGN.md 4.25
                                      [--lr 1e-3] [--weight_decay 1e-4] [--entropy_weight 2.0] [--seed 317] [--min_conf 0]
                                      [--load_model OUT/scan_heads.pth] [--gpus 0] [--select_head epoch|graph]
                                      [--selflabel_epochs 0] [--selflabel_threshold 0.99] [--selflabel_lr 1e-4]
-                                     [--no_class_balancing]
+                                     [--no_class_balancing] [--quality]
 
 --nheads linear heads on the rows of `pred` are trained so that a pick and a random one of [itself, its --num_neighbor graph
 neighbours] get the same class while the classes stay balanced.  --graph takes the `index` of a knn_graph.npz that plot_2d wrote
@@ -36,6 +36,14 @@ clustering step's, as without the flag; in addition
     OUT/scan_labels_selflabel.npz  the keys of scan_labels.npz from that head (head 0; stats: its graph figures), and
                                    selflabel_stats (E, 3) f32: per epoch the mean loss, the share of confident picks, the mean
                                    number of classes present in a batch
+
+--quality (this project's own) scores the classes of every head by their exact silhouette over `pred`
+(utils/cluster_quality.py, csrc/cluster_quality.hip); also with --load_model.  `stats` of scan_labels.npz then has a fourth column,
+the mean silhouette of every head (NaN for a head that leaves fewer than two classes with members), and
+
+    OUT/scan_quality.npz    of the best head: head; s, a, b (N,) f64 and nearest (N,) i32 per pick (a: mean distance to the own
+                            class, b: to the nearest other class, s = (b - a) / max(a, b)); class_mean (C,) f64 (NaN: no member),
+                            class_count (C,) i32, mean, confusion (C, C) i32 [own][nearest] - the classes BEFORE --min_conf
 
 The optimiser defaults (Adam, lr 1e-3, weight decay 1e-4, 100 epochs, batch 1024) are the reference's SCAN settings, and
 --selflabel_threshold 0.99 and --selflabel_lr 1e-4 are SCAN's published self-labelling settings; all are unmeasured on real data
@@ -70,6 +78,8 @@ def add_arguments(parser):
                         help="a pick above this class probability labels itself, in [0, 1) (SCAN's 0.99; unmeasured on real data)")
     parser.add_argument("--selflabel_lr", type=float, default=1e-4, help="Adam's rate of the self-labelling (SCAN's 1e-4; unmeasured)")
     parser.add_argument("--no_class_balancing", action="store_true", help="self-labelling without the inverse-share class weights")
+    parser.add_argument("--quality", action="store_true", help="also score every head's classes by their exact silhouette over "
+                        "`pred`: a fourth column of stats, and scan_quality.npz for the best head")
     return parser
 
 
@@ -149,6 +159,8 @@ def main(args):
         stats = graph_stats(heads, projs, index)
     if not args.load_model:
         heads.save(os.path.join(args.path, "scan_heads.pth"))
+    if args.quality:
+        stats = head_quality(args, heads, projs, stats, device)
     out = write_labels(args, heads, projs, names, coords, stats, "scan_labels.npz")
     if selflabel:
         def log_selflabel(epoch, mean):
@@ -169,6 +181,27 @@ def graph_stats(heads, projs, index):
     print("[cet_pick_amd] scan_main: over the graph: %s; best head %d" % ("  ".join(
         "head %d total %.5f consistency %.5f entropy %.5f" % (h, m[0], m[1], m[2]) for h, m in enumerate(stats)), heads.best_loss_head))
     return stats
+
+
+def head_quality(args, heads, projs, stats, device):
+    """--quality: the exact silhouette (utils/cluster_quality.py, DESIGN.md 4.28) of every head's classes over the embeddings;
+    -> stats with the per-head mean as a fourth column (NaN for a head that leaves fewer than two classes with members); the
+    best head's full record goes to scan_quality.npz."""
+    from .utils.cluster_quality import silhouette
+    label = heads.predict(projs)[0]
+    means = np.full((heads.nheads, 1), np.nan, np.float32)
+    for h in range(heads.nheads):
+        try:
+            q = silhouette(projs, label[:, h], device=device)
+        except ValueError as e:
+            print("[cet_pick_amd] scan_main: head %d has no silhouette: %s" % (h, e))
+            continue
+        means[h, 0] = q.mean
+        if h == heads.best_loss_head:
+            np.savez(os.path.join(args.path, "scan_quality.npz"), head=np.int32(h), **q.arrays())
+    print("[cet_pick_amd] scan_main: mean silhouette per head: %s; best head %d -> %s" % (
+        " ".join("%.6f" % v for v in means[:, 0]), heads.best_loss_head, os.path.join(args.path, "scan_quality.npz")))
+    return np.concatenate([np.asarray(stats, np.float32).reshape(heads.nheads, -1), means], axis=1)
 
 
 def write_labels(args, heads, projs, names, coords, stats, file_name, **more):

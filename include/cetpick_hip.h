@@ -1277,6 +1277,48 @@ int mi_scan_selflabel_bwd(const float* strong, int B, int C, int balance, const 
                           const int32_t* target, const uint8_t* mask, const double* denom, const float* dloss, float* d_strong,
                           mi_stream_t stream);
 
+/* How good a clustering of the picks is (csrc/cluster_quality.hip).  The reference has no counterpart (it judges
+ * classes by eye in an interactive session); what is restated is scikit-learn's sklearn.metrics.silhouette_samples (Euclidean
+ * metric), silhouette_score and contingency_matrix.  No allocation, no synchronisation, no floating-point atomic, every sum in a
+ * fixed order: the same input gives the same bytes.  Rows and table entries are addressed with 64-bit offsets (the (n, k) float64
+ * table passes 2 GiB near n = 10^6 at k = 256).  MI_E_UNSUPPORTED outside the limits, before anything is enqueued; the
+ * *_workspace_bytes functions need no device and return 0 outside the limits.
+ *   mi_silhouette_sums  x (n, d) fp32 rows, 2 <= n < 2^31, 1 <= d <= 512 (the limits of mi_knn_search); labels (n,) int32 fine
+ *                       labels in [0, k), 1 <= k <= 1024; order (n,) int32 = the picks sorted by label, picks of one label in
+ *                       ascending index (a stable sort; the caller's plumbing).  sums_out (n, k) float64:
+ *                         sums_out[i][c] = sum over the members j != i of fine cluster c of sqrt(max(d2(i, j), 0))
+ *                       d2(i, j) = |x_i|^2 + (|x_j|^2 - 2 x_i.x_j) in fp32, the bytes of mi_knn_search's MI_KNN_L2 value before its
+ *                       clamp (the row-product tile of rowdot.h, bf16x3 on the matrix cores); the pair (i, i) is left out by
+ *                       index; the square root and every sum are float64.  The n x n distances are never stored.  Columns are
+ *                       laid out cluster by cluster, each cluster padded to whole tiles of 32 columns; a wave takes 64 rows (32
+ *                       where the rows' cut passes 160 KB of LDS) against one chunk of a cluster's tiles (chunks of
+ *                       max(32, ceil((n / 32 + k) / 64)) tiles), adds a lane's column over the chunk's tiles in ascending order,
+ *                       then the 32 lanes in a fixed tree; a last launch adds a cluster's chunks in ascending order.  A label
+ *                       outside [0, k), or an order that is not that sort, is NOT detected (the caller validates): such picks
+ *                       are left out of every sum, never read or written out of bounds.
+ *   mi_silhouette_finalise  sums (n, k) float64 as above, labels as above, class_of (k,) int32 in [0, C), 2 <= C <= 1024 (the
+ *                       identity when nothing is merged).  A class's sum is the sum of its fine clusters' columns in ascending
+ *                       fine index, its count the integer sum of theirs.  Per pick, float64: a = own-class sum / (count - 1),
+ *                       b = min over the other non-empty classes of sum / count, s = (b - a) / max(a, b) (0 where that is 0 / 0);
+ *                       a = s = 0 for the only member of its class (as sklearn); nearest_out int32 = the class attaining b, the
+ *                       lowest index on a tie.  class_count_out (C,) int32; class_mean_out (C,) float64 = mean of s over the
+ *                       class, NaN for a class without members; *mean_out = mean of s over all picks (per chunk of 256 picks the
+ *                       sum in pick order, the chunks in ascending order); confusion_out (C, C) int32 [own][nearest] (integer
+ *                       atomics).  info_out (3,) int32 = non-empty classes, the largest class count, status: 0 ok, 1 fewer than
+ *                       two non-empty classes or every class a singleton, 2 a class_of entry outside [0, C).  With a status
+ *                       other than 0 only info_out and class_count_out are written: the caller reads info_out and raises.
+ *   mi_label_contingency  a, b (n,) int32, labels outside [0, ca) x [0, cb) left out; table_out (ca, cb) int64 counts (integer
+ *                       atomics), 1 <= ca, cb and ca cb <= 2^24. */
+size_t mi_silhouette_workspace_bytes(long n, int d, int k);
+int mi_silhouette_sums(const float* x, const int32_t* labels, const int32_t* order, long n, int d, int k, double* sums_out, void* ws,
+                       size_t ws_bytes, mi_stream_t stream);
+size_t mi_silhouette_finalise_workspace_bytes(long n, int k, int C);
+int mi_silhouette_finalise(const double* sums, const int32_t* labels, const int32_t* class_of, long n, int k, int C, double* s_out,
+                           double* a_out, double* b_out, int32_t* nearest_out, double* class_mean_out, int32_t* class_count_out,
+                           double* mean_out, int32_t* confusion_out, int32_t* info_out, void* ws, size_t ws_bytes,
+                           mi_stream_t stream);
+int mi_label_contingency(const int32_t* a, const int32_t* b, long n, int ca, int cb, int64_t* table_out, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
