@@ -288,6 +288,13 @@ SIGNATURES = {
     "mi_silhouette_finalise_workspace_bytes": (_Z, [_L, _I, _I]),
     "mi_silhouette_finalise": (_I, [_P, _P, _P, _L, _I, _I] + [_P] * 10 + [_Z, _S]),
     "mi_label_contingency": (_I, [_P, _P, _L, _I, _I, _P, _S]),
+    # label spreading over the neighbour graph and the seed matching (csrc/label_spread.hip)
+    "mi_spread_weights": (_I, [_P, _P, _L, _I, _I, _P, _P, _S]),
+    "mi_spread_csr_count": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _S]),
+    "mi_spread_csr_fill": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _L, _P, _P, _S]),
+    "mi_spread_step": (_I, [_P, _P, _P, _L, _I, _D, _P, _P, _P, _P, _S]),
+    "mi_spread_decide": (_I, [_P, _L, _I, _D, _P, _P, _P, _S]),
+    "mi_seed_nearest": (_I, [_P, _P, _L, _P, _P, _L, _D, _P, _P, _S]),
 }
 
 _lib = None

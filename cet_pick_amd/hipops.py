@@ -3219,3 +3219,117 @@ def label_contingency(a, b, ca, cb):
     table = torch.empty((ca, cb), dtype=torch.int64, device=a.device)
     L.call("mi_label_contingency", a, b, n, ca, cb, table)
     return table
+
+
+# ---- label spreading over the neighbour graph and the seed matching (csrc/label_spread.hip) ------------------
+
+SPREAD_MAX_C = 64                         # classes of spread_step and spread_decide, 2 at least
+
+
+def _spread_table(t, name, shape, dtype, device=None):
+    L.require_cuda(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or (device is not None and t.device != device):
+        raise L.HipExtensionError("%s must be a contiguous %s %s tensor%s, got %s on %s"
+                                  % (name, tuple(shape), dtype, "" if device is None else " on %s" % device, tuple(t.shape), t.device))
+    return t
+
+
+def spread_weights(index, dist=None, mode=1):
+    """w (N, K) fp32 on the device, the weight of every forward edge of index (N, K) int32: mode 0 is 1 per valid edge, mode 1 the
+    self-tuning Gaussian exp(-d2 / sqrt(s_i s_j)) of dist (N, K) fp32 squared L2, s_i the largest finite dist of row i; 0 for an edge
+    that points at its own row or outside [0, N).  -> (w, scale (N,) fp32 or None)."""
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2 or not index.is_contiguous():
+        raise L.HipExtensionError("index must be a contiguous (N, K) int32 tensor, got %s" % (tuple(index.shape),))
+    n, k = index.shape
+    mode = int(mode)
+    scale = None
+    if mode == 1:
+        if dist is None:
+            raise ValueError("the Gaussian edge weight needs the graph's distances")
+        _spread_table(dist, "dist", (n, k), torch.float32, index.device)
+        scale = torch.empty(n, dtype=torch.float32, device=index.device)
+    w = torch.empty((n, k), dtype=torch.float32, device=index.device)
+    L.call("mi_spread_weights", index, dist if mode == 1 else None, n, k, mode, scale, w)
+    return w, scale
+
+
+def spread_csr(index, rev_ptr, rev_edge, w):
+    """The symmetric, degree-normalised graph of label spreading in CSR form, on the device: row i lists its valid forward edges
+    in column order, then the edges that end in i and have no opposite edge; val = w_sym / sqrt(deg_i deg_j), w_sym = max(w_ij,
+    w_ji).  index (N, K) int32, (rev_ptr, rev_edge) = utils.graph.reverse_graph(index) on the device, w (N, K) fp32.
+    -> row_ptr (N + 1,) int64, col (nnz,) int32, val (nnz,) float64, deg (N,) float64.  One host read (nnz).  The same input gives
+    the same bytes."""
+    L.require_cuda(index, "index", torch.int32)
+    if index.dim() != 2 or not index.is_contiguous():
+        raise L.HipExtensionError("index must be a contiguous (N, K) int32 tensor, got %s" % (tuple(index.shape),))
+    n, k = index.shape
+    dev = index.device
+    _spread_table(rev_ptr, "rev_ptr", (n + 1,), torch.int32, dev)
+    _spread_table(rev_edge, "rev_edge", (n * k,), torch.int32, dev)
+    _spread_table(w, "w", (n, k), torch.float32, dev)
+    count = torch.empty(n, dtype=torch.int64, device=dev)
+    deg = torch.empty(n, dtype=torch.float64, device=dev)
+    L.call("mi_spread_csr_count", index, rev_ptr, rev_edge, w, n, k, count, deg)
+    row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    row_ptr[1:] = torch.cumsum(count, 0)                                 # plumbing: the exclusive scan
+    nnz = int(row_ptr[-1])
+    col = torch.empty(nnz, dtype=torch.int32, device=dev)
+    val = torch.empty(nnz, dtype=torch.float64, device=dev)
+    if nnz:
+        L.call("mi_spread_csr_fill", index, rev_ptr, rev_edge, w, n, k, row_ptr, deg, nnz, col, val)
+    return row_ptr, col, val, deg
+
+
+def spread_step(row_ptr, col, val, alpha, f_in, y, f_out, residual=None):
+    """One sweep of label spreading: f_out[i] = alpha sum_e val_e f_in[col_e] + (1 - alpha) y[i].  f_in, y, f_out (N, C) float64,
+    2 <= C <= 64, f_out another buffer than f_in and y.  residual: a (1,) int64 device tensor that receives the bits of the
+    float64 max |f_out - f_in| (read it with .view(torch.float64)); None skips that."""
+    L.require_cuda(f_in, "f_in", torch.float64)
+    if f_in.dim() != 2 or not f_in.is_contiguous():
+        raise L.HipExtensionError("f_in must be a contiguous (N, C) float64 tensor, got %s" % (tuple(f_in.shape),))
+    n, c = f_in.shape
+    dev = f_in.device
+    _spread_table(y, "y", (n, c), torch.float64, dev)
+    _spread_table(f_out, "f_out", (n, c), torch.float64, dev)
+    _spread_table(row_ptr, "row_ptr", (n + 1,), torch.int64, dev)
+    nnz = col.shape[0] if isinstance(col, torch.Tensor) and col.dim() == 1 else -1
+    _spread_table(col, "col", (nnz,), torch.int32, dev)
+    _spread_table(val, "val", (nnz,), torch.float64, dev)
+    if residual is not None:
+        _spread_table(residual, "residual", (1,), torch.int64, dev)
+    L.call("mi_spread_step", row_ptr, col, val, n, c, float(alpha), f_in, y, f_out, residual)
+    return f_out
+
+
+def spread_decide(f, min_conf):
+    """label (N,) int32 = argmax_c f[i, c] (ties to the lowest c), -1 where the row's mass is 0 or its confidence below min_conf;
+    conf (N,) float64 = f[i, label] / mass; mass (N,) float64 = sum_c f[i, c].  f (N, C) float64, 2 <= C <= 64."""
+    L.require_cuda(f, "f", torch.float64)
+    if f.dim() != 2 or not f.is_contiguous():
+        raise L.HipExtensionError("f must be a contiguous (N, C) float64 tensor, got %s" % (tuple(f.shape),))
+    n, c = f.shape
+    label = torch.empty(n, dtype=torch.int32, device=f.device)
+    conf = torch.empty(n, dtype=torch.float64, device=f.device)
+    mass = torch.empty(n, dtype=torch.float64, device=f.device)
+    L.call("mi_spread_decide", f, n, c, float(min_conf), label, conf, mass)
+    return label, conf, mass
+
+
+def seed_nearest(picks, pick_tomo, seeds, seed_tomo, radius):
+    """For every seed the nearest pick of its tomogram: picks (N, 3), seeds (M, 3) float64, pick_tomo (N,), seed_tomo (M,) int32.
+    -> pick (M,) int32 (-1: none within radius), dist (M,) float64 (the least distance, +inf where the tomogram has no pick)."""
+    L.require_cuda(picks, "picks", torch.float64)
+    L.require_cuda(seeds, "seeds", torch.float64)
+    if picks.dim() != 2 or picks.shape[1] != 3 or seeds.dim() != 2 or seeds.shape[1] != 3:
+        raise L.HipExtensionError("picks and seeds must be (N, 3) and (M, 3), got %s and %s" % (tuple(picks.shape), tuple(seeds.shape)))
+    n, m = picks.shape[0], seeds.shape[0]
+    dev = picks.device
+    _spread_table(picks, "picks", (n, 3), torch.float64, dev)
+    _spread_table(seeds, "seeds", (m, 3), torch.float64, dev)
+    _spread_table(pick_tomo, "pick_tomo", (n,), torch.int32, dev)
+    _spread_table(seed_tomo, "seed_tomo", (m,), torch.int32, dev)
+    pick = torch.empty(m, dtype=torch.int32, device=dev)
+    dist = torch.empty(m, dtype=torch.float64, device=dev)
+    L.call("mi_seed_nearest", picks, pick_tomo, n, seeds, seed_tomo, m, float(radius), pick, dist)
+    return pick, dist

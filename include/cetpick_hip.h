@@ -1319,6 +1319,50 @@ int mi_silhouette_finalise(const double* sums, const int32_t* labels, const int3
                            mi_stream_t stream);
 int mi_label_contingency(const int32_t* a, const int32_t* b, long n, int ca, int cb, int64_t* table_out, mi_stream_t stream);
 
+/* Label spreading over the neighbour graph (csrc/label_spread.hip): Zhou et al. 2004, "Learning with local and
+ * global consistency", as scikit-learn's LabelSpreading states it.  The reference gets from a few examples to all similar picks by
+ * hand in its interactive session.  The graph is index (n, k) int32 with its transpose rev_ptr (n + 1), rev_edge (n k) as
+ * csrc/knn_graph.h describes them (n k < 2^31; MI_E_UNSUPPORTED outside, before anything is enqueued); damaged entries are passed
+ * over by that header's guards.  No allocation, no synchronisation, no floating-point atomic, every sum in an order the graph
+ * fixes: the same input gives the same bytes.
+ *   mi_spread_weights    dist (n, k) fp32 squared L2 as mi_knn_search writes it.  w_out (n, k) fp32, 0 for an edge that is passed
+ *                        over.  mode 0: 1 for every valid edge (dist and scale_out may be NULL).  mode 1: the self-tuning Gaussian
+ *                        of Zelnik-Manor & Perona, w_ij = exp(-d2_ij / sqrt(s_i s_j)) in fp32 with sqrt(s_i s_j) formed as
+ *                        sqrt(s_i) sqrt(s_j); s_i = scale_out[i] = the largest finite dist of row i (0 where there is none); where
+ *                        s_i s_j = 0, w = 1 if d2 = 0, else 0; a d2 that is not finite gives 0.
+ *   mi_spread_csr_count  a wave per vertex walks its incident list: the valid forward edges in column order, then the edges of its
+ *                        reverse range that have no opposite edge, in range order.  count_out (n,) int64 = entries of the vertex;
+ *                        deg_out (n,) float64 = the sum of w_sym(i, j) = max(w_ij, w_ji), an absent direction 0, over the list (64
+ *                        entries in one fixed tree, the batches in list order).  The caller's exclusive scan of count_out is
+ *                        row_ptr (n + 1) int64.
+ *   mi_spread_csr_fill   the same walk: col_out (nnz,) int32 and val_out (nnz,) float64 = w_sym (dis_i dis_j), dis = 1 / sqrt(deg)
+ *                        and 0 where deg = 0; dis_i dis_j is formed first, so the matrix is symmetric to the bit.  nnz =
+ *                        row_ptr[n]; nothing is written outside [row_ptr[i], row_ptr[i + 1]) or [0, nnz).
+ *   mi_spread_step       F_out[i, :] = alpha sum_e val_e F_in[col_e, :] + (1 - alpha) Y[i, :] over the entries e of row i in
+ *                        order; F_in, Y, F_out (n, C) float64 row-major, 2 <= C <= 64 (MI_E_UNSUPPORTED outside, before anything is
+ *                        enqueued), 0 < alpha < 1 and F_out overlapping neither input (MI_E_ARG).  col must lie in [0, n): the
+ *                        CSR of the two entries above does.  residual_out, where not NULL, is one 64-bit device word that
+ *                        receives max |F_out - F_in| as the bits of that non-negative double (zeroed by the entry, then an integer
+ *                        atomicMax per workgroup); NULL skips it.
+ *   mi_spread_decide     label_out int32 = argmax_c F[i, c], ties to the lowest c; mass_out = sum_c F[i, c] in ascending c;
+ *                        conf_out = F[i, label] / mass (0 where the mass is 0); label -1 where the mass is 0 or conf < min_conf.
+ *   mi_seed_nearest      picks (n, 3), seeds (m, 3) float64 with pick_tomo (n,), seed_tomo (m,) int32.  One workgroup per seed:
+ *                        pick_out[s] int32 = the pick of the seed's tomogram with the least (dx dx + dy dy) + dz dz (float64,
+ *                        no contraction), ties to the lowest pick; -1 where its distance exceeds radius or the tomogram has no
+ *                        pick; dist_out[s] = that least distance (+inf without a pick).  No limit on n or m below 2^31. */
+int mi_spread_weights(const int32_t* index, const float* dist, long n, int k, int mode, float* scale_out, float* w_out,
+                      mi_stream_t stream);
+int mi_spread_csr_count(const int32_t* index, const int32_t* rev_ptr, const int32_t* rev_edge, const float* w, long n, int k,
+                        int64_t* count_out, double* deg_out, mi_stream_t stream);
+int mi_spread_csr_fill(const int32_t* index, const int32_t* rev_ptr, const int32_t* rev_edge, const float* w, long n, int k,
+                       const int64_t* row_ptr, const double* deg, long nnz, int32_t* col_out, double* val_out, mi_stream_t stream);
+int mi_spread_step(const int64_t* row_ptr, const int32_t* col, const double* val, long n, int C, double alpha, const double* F_in,
+                   const double* Y, double* F_out, uint64_t* residual_out, mi_stream_t stream);
+int mi_spread_decide(const double* F, long n, int C, double min_conf, int32_t* label_out, double* conf_out, double* mass_out,
+                     mi_stream_t stream);
+int mi_seed_nearest(const double* picks, const int32_t* pick_tomo, long n, const double* seeds, const int32_t* seed_tomo, long m,
+                    double radius, int32_t* pick_out, double* dist_out, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
