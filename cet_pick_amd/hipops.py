@@ -2990,17 +2990,24 @@ def _scan_logits(t, name, nheads, max_rows=None):
     return rows, width // nheads
 
 
+def _scan_logits_pair(first, second, names, differ, nheads):
+    """(rows, classes per head) of the two logits tensors of one training batch: the same shape (else ValueError(differ % both
+    shapes)), each through _scan_logits, both on the device."""
+    b, c = _scan_logits(first, names[0], nheads, SCAN_MAX_ROWS)
+    if second.shape != first.shape:
+        raise ValueError(differ % (tuple(first.shape), tuple(second.shape)))
+    _scan_logits(second, names[1], nheads, SCAN_MAX_ROWS)
+    L.require_cuda(first, names[0])
+    L.require_cuda(second, names[1])
+    return b, c
+
+
 class _ScanLossFn(torch.autograd.Function):
     """mi_scan_loss_fwd / _bwd: (sum of the heads' totals, stats (H, 3) = total, consistency, entropy per head)."""
 
     @staticmethod
     def forward(ctx, anchors, neighbours, nheads, entropy_weight):
-        b, c = _scan_logits(anchors, "anchors", nheads, SCAN_MAX_ROWS)
-        if neighbours.shape != anchors.shape:
-            raise ValueError("anchors are %s, neighbours %s" % (tuple(anchors.shape), tuple(neighbours.shape)))
-        _scan_logits(neighbours, "neighbours", nheads, SCAN_MAX_ROWS)
-        L.require_cuda(anchors, "anchors")
-        L.require_cuda(neighbours, "neighbours")
+        b, c = _scan_logits_pair(anchors, neighbours, ("anchors", "neighbours"), "anchors are %s, neighbours %s", nheads)
         h, dev = int(nheads), anchors.device
         ws = L.workspace(L.lib().mi_scan_loss_workspace_bytes(b, c, h), dev, "scanloss")
         stats = torch.empty((h, 3), dtype=torch.float32, device=dev)
@@ -3082,12 +3089,7 @@ class _ScanSelflabelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weak, strong, threshold, balance):
-        b, c = _scan_logits(weak, "weak", 1, SCAN_MAX_ROWS)
-        if strong.shape != weak.shape:
-            raise ValueError("weak is %s, strong %s" % (tuple(weak.shape), tuple(strong.shape)))
-        _scan_logits(strong, "strong", 1, SCAN_MAX_ROWS)
-        L.require_cuda(weak, "weak")
-        L.require_cuda(strong, "strong")
+        b, c = _scan_logits_pair(weak, strong, ("weak", "strong"), "weak is %s, strong %s", 1)
         dev = strong.device
         ws = L.workspace(L.lib().mi_scan_selflabel_workspace_bytes(b, c), dev, "scanselflabel")
         loss = torch.empty((), dtype=torch.float32, device=dev)

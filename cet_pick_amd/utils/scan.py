@@ -75,6 +75,18 @@ def _pad16(v):
     return (v + 15) // 16 * 16
 
 
+def _checked_graph(index, n, max_k=None):
+    """index (n, k) as an array, checked once on the host: n rows, entries in 0..n-1, and 1 <= k <= max_k where one is given"""
+    index = np.asarray(index)
+    if index.ndim != 2 or index.shape[0] != n:
+        raise ValueError("the graph has %s rows, the embeddings %d" % (index.shape[:1], n))
+    if max_k is not None and not 1 <= index.shape[1] <= max_k:
+        raise ValueError("the graph must have 1..%d neighbours per pick, got %d" % (max_k, index.shape[1]))
+    if index.size and (index.min() < 0 or index.max() >= n):
+        raise ValueError("the graph names a pick outside 0..%d" % (n - 1))
+    return index
+
+
 class ScanHeads:
     """nheads linear heads of nclusters classes on d-dimensional embeddings."""
 
@@ -154,45 +166,48 @@ class ScanHeads:
         epoch's batches.  best_loss_head is the head with the lowest mean total of the last epoch."""
         with torch.cuda.device(self.device):
             xp = self._embeddings(x)
-            index = np.asarray(index)
-            if index.ndim != 2 or index.shape[0] != xp.shape[0]:
-                raise ValueError("the graph has %s rows, the embeddings %d" % (index.shape[:1], xp.shape[0]))
-            if index.size and (index.min() < 0 or index.max() >= xp.shape[0]):
-                raise ValueError("the graph names a pick outside 0..%d" % (xp.shape[0] - 1))
-            bs = int(batch_size)
-            if bs > H.SCAN_MAX_ROWS:
-                raise ValueError("batch_size is at most %d, got %d" % (H.SCAN_MAX_ROWS, bs))
-            self.optimizer = torch.optim.Adam(self.lin.parameters(), lr=lr, weight_decay=weight_decay)
-            for _ in range(int(num_epochs)):
-                anchor, neighbour = draw_neighbours(index, self.seed, self.epoch, bs)
-                pairs = torch.from_numpy(np.stack([anchor.reshape(-1, bs), neighbour.reshape(-1, bs)], axis=1)).to(self.device)
-                acc = torch.zeros((self.nheads, 3), dtype=torch.float32, device=self.device)
-                for rows in pairs:                         # (2, bs): the anchors, then their neighbours
-                    z = self._logits(xp.index_select(0, rows.reshape(-1)))
-                    loss, stats = H.scan_loss(z[:bs].contiguous(), z[bs:].contiguous(), self.nheads, entropy_weight)
-                    self.optimizer.zero_grad(set_to_none=True)
-                    loss.backward()
-                    self.optimizer.step()
-                    acc += stats
-                mean = (acc / len(pairs)).cpu().numpy()    # the epoch's one host read
-                self.history.append(mean)
-                self.epoch += 1
-                if log is not None:
-                    log(self.epoch, mean)
+            index = _checked_graph(index, xp.shape[0])
+
+            def step(za, zn, acc):
+                loss, stats = H.scan_loss(za.contiguous(), zn.contiguous(), self.nheads, entropy_weight)
+                acc += stats
+                return loss
+
+            self._train(xp, index, num_epochs, batch_size, lr, weight_decay, step, (self.nheads, 3), self.history, log)
             last = self.history[-1][:, 0]
             self.best_loss_head = int(np.argmin(last))
             self.best_loss = float(last[self.best_loss_head])
             return np.stack(self.history)
 
+    def _train(self, xp, index, num_epochs, batch_size, lr, weight_decay, step, shape, history, log, divide=None):
+        """The epochs of fit and selflabel, Adam on these heads, the draws numbered on from self.epoch: per batch ONE index_select +
+        HipLinear call on [anchors; partners], step(anchor logits, partner logits, acc) -> loss adds the batch's row to acc (`shape`,
+        on the device); the mean over the epoch's batches (/ divide) - the epoch's one host read - goes to `history` and to
+        log(epochs done, mean)."""
+        bs = int(batch_size)
+        if bs > H.SCAN_MAX_ROWS:
+            raise ValueError("batch_size is at most %d, got %d" % (H.SCAN_MAX_ROWS, bs))
+        self.optimizer = torch.optim.Adam(self.lin.parameters(), lr=lr, weight_decay=weight_decay)
+        for epoch, anchor, partner in selflabel_draws(index, self.seed, self.epoch, num_epochs, bs):
+            pairs = torch.from_numpy(np.stack([anchor.reshape(-1, bs), partner.reshape(-1, bs)], axis=1)).to(self.device)
+            acc = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            for rows in pairs:                             # (2, bs): the anchors, then their partners
+                z = self._logits(xp.index_select(0, rows.reshape(-1)))
+                loss = step(z[:bs], z[bs:], acc)
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
+                self.optimizer.step()
+            mean = (acc / len(pairs)).cpu().numpy()        # the epoch's one host read
+            if divide is not None:
+                mean /= divide
+            history.append(mean)
+            self.epoch = epoch + 1
+            if log is not None:
+                log(self.epoch, mean)
+
     def _graph(self, index, n):
         """index (N, k) checked once on the host -> int32 on the device"""
-        index = np.asarray(index)
-        if index.ndim != 2 or index.shape[0] != n:
-            raise ValueError("the graph has %s rows, the embeddings %d" % (index.shape[:1], n))
-        if not 1 <= index.shape[1] <= H.SCAN_MAX_NEIGHBOURS:
-            raise ValueError("the graph must have 1..%d neighbours per pick, got %d" % (H.SCAN_MAX_NEIGHBOURS, index.shape[1]))
-        if index.min() < 0 or index.max() >= n:
-            raise ValueError("the graph names a pick outside 0..%d" % (n - 1))
+        index = _checked_graph(index, n, H.SCAN_MAX_NEIGHBOURS)
         return torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(self.device)
 
     def evaluate(self, x, index):
@@ -229,29 +244,17 @@ class ScanHeads:
                                  "cluster_head.0.bias": sd["cluster_head.%d.bias" % head]})
             one.epoch = self.epoch
             xp = one._embeddings(x)
-            index = one._graph(index, xp.shape[0]).cpu().numpy()
-            bs = int(batch_size)
-            if bs > H.SCAN_MAX_ROWS:
-                raise ValueError("batch_size is at most %d, got %d" % (H.SCAN_MAX_ROWS, bs))
-            one.optimizer = torch.optim.Adam(one.lin.parameters(), lr=lr, weight_decay=weight_decay)
+            index = _checked_graph(index, xp.shape[0], H.SCAN_MAX_NEIGHBOURS)
+
+            def step(weak, strong, acc):                   # acc: loss, confident rows, classes present
+                loss, info, _ = H.scan_selflabel_loss(weak.detach().contiguous(), strong.contiguous(), threshold, balance)
+                acc[0] += loss.detach()
+                acc[1:] += info[:2]
+                return loss
+
             history = []
-            for epoch, anchor, strong in selflabel_draws(index, one.seed, one.epoch, num_epochs, bs):
-                pairs = torch.from_numpy(np.stack([anchor.reshape(-1, bs), strong.reshape(-1, bs)], axis=1)).to(self.device)
-                acc = torch.zeros((3,), dtype=torch.float32, device=self.device)
-                for rows in pairs:                         # (2, bs): the anchors, then their strong rows
-                    z = one._logits(xp.index_select(0, rows.reshape(-1)))
-                    loss, info, _ = H.scan_selflabel_loss(z[:bs].detach().contiguous(), z[bs:].contiguous(), threshold, balance)
-                    one.optimizer.zero_grad(set_to_none=True)
-                    loss.backward()
-                    one.optimizer.step()
-                    acc[0] += loss.detach()
-                    acc[1:] += info[:2]
-                mean = (acc / len(pairs)).cpu().numpy()    # the epoch's one host read
-                mean[1] /= bs
-                history.append(mean)
-                one.epoch = epoch + 1
-                if log is not None:
-                    log(one.epoch, mean)
+            one._train(xp, index, num_epochs, batch_size, lr, weight_decay, step, (3,), history, log,
+                       divide=np.array([1, int(batch_size), 1], np.float32))
             if history:
                 one.best_loss = float(history[-1][0])
             return one, np.stack(history) if history else np.zeros((0, 3), np.float32)

@@ -64,6 +64,19 @@ def softmax(z):
     return e / e.sum(axis=-1, keepdims=True)
 
 
+def norm_value(got, want):
+    """the deviation of a figure v: |dv| / (1 + |v|), the largest over an array"""
+    want = np.asarray(want, np.float64)
+    return float((np.abs(np.asarray(got, np.float64) - want) / (1.0 + np.abs(want))).max())
+
+
+def norm_grad(got, want):
+    """the deviation of a gradient: max |dg| / max |g| over its case (several tensors of one case: stacked)"""
+    want = np.asarray(want, np.float64)
+    top = float(np.abs(want).max())
+    return float(np.abs(np.asarray(got, np.float64) - want).max()) / (top if top > 0 else 1.0)
+
+
 def loss(anchors, neighbours, nheads, entropy_weight=ENTROPY_WEIGHT):
     """-> stats (H, 3) float64: total, consistency, entropy per head; and the sum of the totals."""
     B = anchors.shape[0]

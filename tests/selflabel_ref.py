@@ -5,9 +5,8 @@ are made here from seeds, so the golden file (tests/golden/scan/selflabel_small.
 tests/golden/gen_golden_scan_selflabel.py) holds results only."""
 import numpy as np
 
-from scan_ref import softmax
+from scan_ref import CHUNK, norm_grad, norm_value, softmax  # noqa: F401  (the tests reach the norms through this module too)
 
-CHUNK = 256                                # MI_SCAN_CHUNK: rows per partial sum
 MARGIN = 1e-4                              # no row's largest probability lies this close to its case's threshold
 
 # name -> B, C, kind, threshold rule, balance, upstream gradient.  B crosses the chunk, C the half wave and the wave.
@@ -109,9 +108,7 @@ def selflabel(weak, strong, threshold, balance, upstream=1.0):
     n = int(mask.sum())
     count = np.bincount(target[mask], minlength=C)
     w = class_weights(count, n, balance)
-    z = np.asarray(strong, np.float64)
-    zs = z - z.max(1, keepdims=True)
-    logq = zs - np.log(np.exp(zs).sum(1, keepdims=True))
+    q = softmax(np.asarray(strong, np.float64))            # (no entry underflows in float64: the cases' logits span 400 at most)
     wt = w[target] * mask
     denom = float(wt.sum())
     onehot = np.zeros((B, C))
@@ -119,8 +116,8 @@ def selflabel(weak, strong, threshold, balance, upstream=1.0):
     if n == 0:
         loss, grad = 0.0, np.zeros((B, C))
     else:
-        loss = float((wt * -logq[np.arange(B), target]).sum() / denom)
-        grad = upstream * (wt / denom)[:, None] * (np.exp(logq) - onehot)
+        loss = float((wt * -np.log(q[np.arange(B), target])).sum() / denom)
+        grad = upstream * (wt / denom)[:, None] * (q - onehot)
     return dict(loss=loss, grad=grad, target=target, mask=mask.astype(np.uint8), count=count,
                 info=np.array([n, int((count > 0).sum()), B]), pmax=pmax, weight=w, denom=denom)
 
@@ -159,19 +156,6 @@ def graph_eval(logits, index, nheads, with_self=True):
     entropy = -(x * np.log(x)).sum(-1)
     total = consistency - entropy
     return np.stack([total, consistency, entropy], axis=1), int(np.argmin(total))
-
-
-def norm_value(got, want):
-    """the deviation of a figure v: |dv| / (1 + |v|), the largest over an array"""
-    want = np.asarray(want, np.float64)
-    return float((np.abs(np.asarray(got, np.float64) - want) / (1.0 + np.abs(want))).max())
-
-
-def norm_grad(got, want):
-    """the deviation of a gradient: max |dg| / max |g| over its case"""
-    want = np.asarray(want, np.float64)
-    top = float(np.abs(want).max())
-    return float(np.abs(np.asarray(got, np.float64) - want).max()) / (top if top > 0 else 1.0)
 
 
 def best_gap(stats):

@@ -46,6 +46,30 @@ def test_cases_reach_the_clamp_the_floor_and_a_dead_class():
     assert R.CASES["upstream"][4] != 1.0
 
 
+def test_the_limits_are_stated_once():
+    """MI_SCAN_CHUNK of the C header is the chunk of hipops and of the restatements, and the workspace functions (no device needed)
+    answer 0 exactly outside hipops' limits: at a limit they count bytes, one past it and at 0 they refuse."""
+    import re
+    import __graft_entry__ as ge
+    ge.build()
+    from cet_pick_amd import _lib as L, hipops as H
+    import selflabel_ref
+    header = open(os.path.join(os.path.dirname(HERE), "include", "cetpick_hip.h")).read()
+    chunk = int(re.search(r"^#define MI_SCAN_CHUNK (\d+)$", header, re.M).group(1))
+    assert H.SCAN_CHUNK == chunk and R.CHUNK == chunk and selflabel_ref.CHUNK is R.CHUNK
+    lib = L.lib()
+    C, NH, B = H.SCAN_MAX_CLASSES, H.SCAN_MAX_HEADS, H.SCAN_MAX_ROWS
+    assert lib.mi_scan_loss_workspace_bytes(B, C, NH) > 0 and lib.mi_scan_loss_workspace_bytes(1, 1, 1) > 0
+    assert lib.mi_scan_graph_eval_workspace_bytes(B + 1, C, NH) > 0 and lib.mi_scan_graph_eval_workspace_bytes(1, 1, 1) > 0
+    assert lib.mi_scan_selflabel_workspace_bytes(B, C) > 0 and lib.mi_scan_selflabel_workspace_bytes(1, 1) > 0
+    for b, c, h in ((B + 1, C, NH), (B, C + 1, NH), (B, C, NH + 1), (0, C, NH), (B, 0, NH), (B, C, 0)):
+        assert lib.mi_scan_loss_workspace_bytes(b, c, h) == 0, (b, c, h)
+        if b <= B:                                         # (the graph's rows are the picks: no batch limit)
+            assert lib.mi_scan_graph_eval_workspace_bytes(b, c, h) == 0, (b, c, h)
+        if h == NH:
+            assert lib.mi_scan_selflabel_workspace_bytes(b, c) == 0, (b, c)
+
+
 def test_neighbour_draws():
     from cet_pick_amd.utils.scan import draw_neighbours
     rng = np.random.default_rng(3)

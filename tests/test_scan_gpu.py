@@ -21,22 +21,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden", "scan", "scan_small.npz")
 
 
-def norm_value(got, want):
-    return float((np.abs(np.asarray(got, np.float64) - want) / (1.0 + np.abs(want))).max())
-
-
-def norm_grads(got, want):
-    """got, want: (da, db)"""
-    top = max(float(np.abs(w).max()) for w in want)
-    return max(float(np.abs(np.asarray(g, np.float64) - w).max()) for g, w in zip(got, want)) / (top if top > 0 else 1.0)
-
-
 @pytest.fixture(scope="module")
 def bounds():
     g = np.load(GOLDEN)
-    dev_v = max(max(norm_value(g[n + "_stats_f32"], g[n + "_stats_f64"]), norm_value(g[n + "_total_f32"], g[n + "_total_f64"]))
+    dev_v = max(max(R.norm_value(g[n + "_stats_f32"], g[n + "_stats_f64"]), R.norm_value(g[n + "_total_f32"], g[n + "_total_f64"]))
                 for n in R.CASES)
-    dev_g = max(norm_grads((g[n + "_da_f32"], g[n + "_db_f32"]), (g[n + "_da_f64"], g[n + "_db_f64"])) for n in R.CASES)
+    dev_g = max(R.norm_grad((g[n + "_da_f32"], g[n + "_db_f32"]), (g[n + "_da_f64"], g[n + "_db_f64"])) for n in R.CASES)
     print("reference float32 deviation: figures %.3e, gradients %.3e" % (dev_v, dev_g))
     assert 0 < dev_v < 1e-5 and 0 < dev_g < 1e-5          # a float32 rounding, not a broken fixture
     return 4 * dev_v, 4 * dev_g
@@ -68,8 +58,8 @@ def test_loss_and_gradients(bounds, name):
     want_grads = R.grads(a, b, nheads, upstream=up)
     for t in (loss, stats, da, db):
         assert bool(torch.isfinite(t).all())
-    ev = max(norm_value(stats.cpu().numpy(), want_stats), norm_value(loss.cpu().numpy(), np.float64(want_total)))
-    eg = norm_grads((da.cpu().numpy(), db.cpu().numpy()), want_grads)
+    ev = max(R.norm_value(stats.cpu().numpy(), want_stats), R.norm_value(loss.cpu().numpy(), np.float64(want_total)))
+    eg = R.norm_grad((da.cpu().numpy(), db.cpu().numpy()), want_grads)
     print("scan_loss %s: figures error / bound %.3f, gradients error / bound %.3f" % (name, ev / bound_v, eg / bound_g))
     assert ev <= bound_v
     assert eg <= bound_g
@@ -83,9 +73,9 @@ def test_single_head_module_has_the_reference_signature(bounds):
     c = a.shape[1] // nheads
     total, consistency, entropy = SCANLoss(entropy_weight=R.ENTROPY_WEIGHT)(dev(a[:, :c]), dev(b[:, :c]))
     want, _ = R.loss(a[:, :c], b[:, :c], 1)
-    assert norm_value(np.array([float(total), float(consistency), float(entropy)]), want[0]) <= bounds[0]
+    assert R.norm_value(np.array([float(total), float(consistency), float(entropy)]), want[0]) <= bounds[0]
     both, stats = MultiHeadSCANLoss(nheads)(dev(a), dev(b))
-    assert float(stats[0, 0]) == float(total) and norm_value(float(both), np.float64(R.loss(a, b, nheads)[1])) <= bounds[0]
+    assert float(stats[0, 0]) == float(total) and R.norm_value(float(both), np.float64(R.loss(a, b, nheads)[1])) <= bounds[0]
 
 
 @pytest.mark.parametrize("name", ["chunks_c3", "extreme", "chunk_more_h16"])
@@ -112,7 +102,7 @@ def test_assign(bounds, n):
     assert tuple(label.shape) == tuple(conf.shape) == (n, nheads) and tuple(counts.shape) == (nheads, c)
     assert np.array_equal(label.cpu().numpy(), want_label)
     assert np.array_equal(counts.cpu().numpy(), want_counts) and int(counts.sum()) == n * nheads
-    ec, ep = norm_value(conf.cpu().numpy(), want_conf), norm_value(prob.cpu().numpy(), want_prob)
+    ec, ep = R.norm_value(conf.cpu().numpy(), want_conf), R.norm_value(prob.cpu().numpy(), want_prob)
     print("scan_assign n = %d: conf error / bound %.3f, prob error / bound %.3f" % (n, ec / bounds[0], ep / bounds[0]))
     assert ec <= bounds[0] and ep <= bounds[0]
     label2, conf2, counts2, none = H.scan_assign(dev(z), nheads)

@@ -124,6 +124,28 @@ def test_selflabel_same_input_same_bytes(name):
         assert torch.equal(x, y)
 
 
+def test_assign_and_selflabel_share_one_argmax_and_one_softmax():
+    """mi_scan_assign (scan_loss.hip) and the self-label forward on the same weak logits, one index_select'ed batch: B = 257 is two
+    chunks with a ragged last chunk and a ragged wave, C = 33 leaves off-lanes, H = 1.  At threshold 0 every row is confident
+    (its largest probability is above 0 for any finite logits), so the targets are the labels; conf is the label's entry of prob
+    bit for bit; and two equal maxima go to the lower class at both entry points."""
+    import torch
+    from cet_pick_amd import hipops as H
+    rng = np.random.default_rng(257)
+    pool = dev((2.0 * rng.standard_normal((400, 33))).astype(np.float32))
+    weak = pool.index_select(0, dev(rng.permutation(400)[:257]))
+    strong = weak + 0.5 * dev(rng.standard_normal((257, 33)).astype(np.float32))
+    label, conf, _, prob = H.scan_assign(weak, 1, with_prob=True)
+    _, _, _, target, mask = H.scan_selflabel(weak, strong, 0.0)
+    assert tuple(target.shape) == (257,) and torch.equal(target, label[:, 0]) and bool((mask == 1).all())
+    assert torch.equal(conf, prob.gather(1, label.long()))
+    tied = weak.clone()
+    tied[256, 3] = tied[256, 17] = tied[256].max() + 1.0   # the ragged chunk's row: classes 3 and 17 equal, above the rest
+    assert int(np.argmax(tied[256].cpu().numpy())) == 3 and float(tied[256, 3]) == float(tied[256, 17])
+    assert int(H.scan_assign(tied, 1)[0][256, 0]) == 3
+    assert int(H.scan_selflabel(tied, strong, 0.0)[3][256]) == 3
+
+
 @pytest.mark.parametrize("name", ["n515_k5_h3_c33", "n257_k20_h16_c2", "x30"])
 def test_graph_eval_same_input_same_bytes(name):
     import torch
